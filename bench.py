@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the batched step() hot path on MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload snake_1m] [--path rollout|step]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload snake_1m] [--path rollout|step] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch: one env transition (with fused auto-reset) of every
 instance on the GPU, the full observation / reward / flags written to HBM.  Default workload = BASELINE.json
 configs[1]: SnakeEnv 10x10, 1,048,576 parallel envs per GPU (weak scaling: per-GPU batch fixed, global env
-indices sharded contiguously, no collective on the data path).  Two paths are measured in every run:
+indices sharded contiguously, no collective on the data path).
+
+A plain run measures the headline path only: set-up, W warm-up steps, ONE timed region of exactly K steps (`--repeats` to
+time more), the JSON line (`value`, `ms_per_step`, `spread`, `config`).  `--dump-outputs DIR` then writes what the last
+timed step returned to its caller (a fixed, seeded sample of the envs: dump_outputs) so that two builds can be compared
+output for output.  Everything below — the other path, the repeats' median (`--repeats` defaults to 9), the roofline,
+`phases`, `rollout_with_final_obs`, `steady_state`, `graph_step` and `cpu_baseline` — is `--full`.  Two paths are
+measured in a --full run:
 
   rollout (headline `value`)  the K timed steps fused, kc steps per launch (kc = K unless the [kc, N, obs] trajectory would
                               exceed --traj-gib): env state stays in registers, and EVERY step's observation, reward and
@@ -30,7 +37,7 @@ cores: reported, not the target).  roofline fields:
 The K-step timed region (barrier + synchronize on both sides, max over ranks) is run `--repeats` times (default 9; episodes restarted
 before each one where the workload fixes the episode phase): `value` / `ms_per_step` are the MEDIAN region, `spread` holds min, max and
 every region; the roofline's launch time is the tighter of two HIP-event brackets of the same K steps — the median region's own events and a
-second pass queued behind a primer copy (`first_pass_launch_us`, `second_pass_launch_us`, `roofline.timing`).  Every leg starts after half a second of idle.
+second pass queued behind a primer copy (`first_pass_launch_us`, `second_pass_launch_us`, `roofline.timing`).  Every leg of a --full run starts after half a second of idle.
 snake_1m's regions are not preceded by a reset, and W warm-up steps after the batch was reset together it is still leaving that state (every digit
 ring full; `spread.all_ms_per_step` shows the regions getting slower): `steady_state` times the same K steps again `--steady-steps` (2,000) steps later.
 Single-type workloads time the rollout once more with the
@@ -128,18 +135,27 @@ def make_env(cge, name, n, dev, env0):
             "fleet": cge.FleetVectorEnv, "manufacturing": cge.ManufacturingVectorEnv, "hospital": cge.HospitalVectorEnv}[name](n, **kw)
 
 
+ACTION_BYTES = 16 << 30         # cap on the step() leg's action stream; longer runs cycle through it (act_at)
+
+
 def make_actions(name, steps, n, dev):
-    """Synthetic action stream resident in HBM before the timed region."""
+    """Synthetic action stream resident in HBM before the timed region, seeded: the same arguments give the same actions."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    per_step = n * (8 if name == "climate" else 4 * int(np.prod(ENVS[name]["act_shape"])))
+    steps = max(1, min(steps, ACTION_BYTES // per_step))
     if name == "climate":
-        return (torch.rand((steps, n, 1), device=dev) * 16 + 16, torch.randint(0, 2, (steps, n, 4), dtype=torch.int8, device=dev))
+        return (torch.rand((steps, n, 1), device=dev, generator=g) * 16 + 16,
+                torch.randint(0, 2, (steps, n, 4), dtype=torch.int8, device=dev, generator=g))
     spec = ENVS[name]
-    return torch.randint(0, spec["n_act"], (steps, n) + spec["act_shape"], dtype=torch.int32, device=dev)
+    return torch.randint(0, spec["n_act"], (steps, n) + spec["act_shape"], dtype=torch.int32, device=dev, generator=g)
 
 
 def act_at(name, actions, t):
     if actions is None:                                  # dry run
         return None
-    return (actions[0][t], actions[1][t]) if name == "climate" else actions[t]
+    if name == "climate":
+        return actions[0][t % len(actions[0])], actions[1][t % len(actions[1])]
+    return actions[t % len(actions)]
 
 
 def cpu_baseline(name, budget_s=12.0):
@@ -255,6 +271,29 @@ def roofline(name, path, kernel, gpu_ms, launches, steps_per_launch, n, occupanc
     return r
 
 
+DUMP_BYTES = 60_000_000         # --dump-outputs: data bytes of all files of all ranks together (64 MB with the .npy headers)
+
+
+def _dump_dtype(dt):
+    """float32 / float64 stay; bools and narrow integers -> float32, 32/64-bit integers -> float64 (all exact)"""
+    return np.float64 if dt in (torch.float64, torch.int32, torch.int64) else np.float32
+
+
+def dump_outputs(out_dir, arrays, n, env0, budget, prefix=""):
+    """arrays: {env type: {name: tensor [n, ...]}} -> out_dir/<prefix><type>_<name>.npy.  Where all n rows would exceed the
+    type's share of `budget`, the same fixed, seeded sample of rows is written for every name; <prefix><type>_env_index.npy
+    holds the global env index of each row written."""
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, arrs in arrays.items():
+        row = 8 + sum(np.dtype(_dump_dtype(t.dtype)).itemsize * (t.numel() // n) for t in arrs.values())
+        m = min(n, budget // len(arrays) // row)
+        idx = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        np.save(os.path.join(out_dir, f"{prefix}{nm}_env_index.npy"), (idx + env0).astype(np.float64))
+        for key, t in arrs.items():
+            rows = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(out_dir, f"{prefix}{nm}_{key}.npy"), rows.cpu().numpy().astype(_dump_dtype(t.dtype)))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # N > 1 without a launcher: the parent starts the ranks itself, as fresh processes, before it makes any GPU call
 def self_launch(n_ranks):
@@ -332,13 +371,23 @@ def main():
                          "should be long enough to amortise the 1,200-byte window load — 125 steps per launch on the 288-GB part)")
     ap.add_argument("--manifest", default=None, help="write {kernel: env-steps launched} here (tools/profile.sh uses it to turn PMC bytes into bytes per env-step)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=9, help="the K-step timed region is run this many times; value / ms_per_step = the median region")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step timed region is run this many times; value / ms_per_step = the median region "
+                                                              "(default 1; 9 with --full)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the other path's leg, the roofline (second events pass, "
+                                                        "copy / fill bandwidth), phases, rollout_with_final_obs, steady_state, cpu_baseline and, "
+                                                        "with --graph, graph_step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline path returned in its last step as DIR/<env type>_<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the envs, at most 64 MB in all)")
     ap.add_argument("--graph", action="store_true", help="third leg: the step() calls captured in ONE HIP graph (torch.cuda.CUDAGraph) and replayed — "
                                                          "what the host-bound small batches gain when the per-call launch path is taken off the clock")
     ap.add_argument("--no-final-obs-leg", action="store_true", help="skip the second rollout leg (the same K steps with the terminal-observation side "
                                                                     "output registered): tools/profile.sh, so that a kernel's PMC bytes are the headline leg's")
     ap.add_argument("--episode", action="store_true", help="--steps := the workload's episode length (one whole episode per timed region)")
     args = ap.parse_args()
+    if args.graph and not args.full:
+        ap.error("--graph is a leg of --full")
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus)                       # never returns
@@ -371,7 +420,8 @@ def main():
     wl = WORKLOADS[args.workload]
     if args.episode and wl.get("episode"):
         args.steps = wl["episode"]
-    n, K, W, R = wl["n"], args.steps, args.warmup, max(1, args.repeats)
+    n, K, W = wl["n"], args.steps, args.warmup
+    R = max(1, args.repeats if args.repeats is not None else (9 if full else 1))
     dev = torch.device("cpu") if dry else torch.device("cuda", local_rank)
     if wl["env"] == "hetero":
         names = sorted(ENVS)
@@ -433,6 +483,7 @@ def main():
         launched[kern] = launched.get(kern, 0) + n * steps
 
     last_launch = {}
+    last_ret = {}                                        # env type -> what the last rollout() / step() call returned (--dump-outputs)
 
     def run_rollout(k_total, t0, marks=None):
         for nm in names:
@@ -440,7 +491,7 @@ def main():
                 done = 0
                 while done < k_total:
                     k = min(kc[nm], k_total - done)
-                    envs[nm].rollout(k, action_seed=123, t0=t0 + done, trajectory=True, per_step=True)
+                    last_ret[nm] = envs[nm].rollout(k, action_seed=123, t0=t0 + done, trajectory=True, per_step=True)
                     last_launch[nm] = k
                     count(nm, "rollout", k)
                     done += k
@@ -454,7 +505,7 @@ def main():
         for t in range(lo, hi):
             for nm in names:
                 with on_stream(nm):
-                    envs[nm].step(act_at(nm, actions[nm], t))
+                    last_ret[nm] = envs[nm].step(act_at(nm, actions[nm], t))
                     if marks is not None and not dry and ((t + 1 - lo) % seg == 0 or t + 1 == hi):
                         ev = torch.cuda.Event(enable_timing=True)
                         ev.record(streams[nm])
@@ -483,9 +534,10 @@ def main():
         return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
 
     def cool():
-        # every leg starts after half a second of idle, so that no leg is measured right behind another one's last launch
+        # every leg of a --full run starts after half a second of idle, so that no leg is measured right behind another one's last
+        # launch; a plain run has one leg, timed right behind its own warm-up (a region that starts on an idle card runs slower)
         sync()
-        if not dry:
+        if full and not dry:
             time.sleep(0.5)
 
     def timed(fn, tag, second_pass):
@@ -499,12 +551,12 @@ def main():
         cool()
         for rep in range(R):
             restart_episodes()
-            before = mean_occupancy()
+            before = mean_occupancy() if full else {}
             barrier()
             evs = {}
-            if not dry:
+            if full and not dry:
                 evs = {nm: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for nm in names}
-            marks = {nm: [] for nm in names}
+            marks = {nm: [] for nm in names} if full else None
             t0 = time.perf_counter()
             for nm in evs:
                 evs[nm][0].record(streams[nm])          # on the stream the kernels are launched on
@@ -513,7 +565,7 @@ def main():
                 evs[nm][1].record(streams[nm])
             barrier()
             walls.append(time.perf_counter() - t0)
-            after = mean_occupancy()
+            after = mean_occupancy() if full else {}
             occ.append({nm: 0.5 * (before[nm] + after[nm]) for nm in before})
             firsts.append({nm: (evs[nm][0].elapsed_time(evs[nm][1]) if evs else walls[-1] * 1e3) for nm in names})
             if evs:                                     # us per step of each segment of the region (a launch of the rollout leg, a tenth of the step() leg)
@@ -548,7 +600,7 @@ def main():
                        "all_ms_per_step": [w * 1e3 / K for w in walls]}
         first = {nm: median([f[nm] for f in firsts]) for nm in names}
         host_latency_ms[tag] = None
-        if second_pass and not dry:
+        if second_pass and full and not dry:
             seconds = []
             for rep in range(min(R, 3)):
                 ev2 = {nm: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for nm in names}
@@ -579,23 +631,48 @@ def main():
             return wall, {nm: min(first[nm], second[nm]) for nm in names}
         return wall, first
 
+    def dump(path):
+        """--dump-outputs: the arrays the last timed rollout() / step() call of `path` returned, one row per env"""
+        if not args.dump_outputs or dry:
+            return
+        arrays = {}
+        for nm in names:
+            if path == "rollout":
+                obs, rew, flags, rs, dc = last_ret[nm]
+                k = last_launch[nm]
+                arrays[nm] = {"obs": obs[k - 1], "reward": rew[k - 1], "flags": flags[k - 1], "reward_sum": rs, "done_count": dc}
+            else:
+                obs, rew, term, trunc, infos = last_ret[nm]
+                arrays[nm] = {"obs": obs, "reward": rew, "terminated": term, "truncated": trunc,
+                              **{key: v for key, v in infos.items() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == n}}
+                if "final_obs" in arrays[nm]:        # rows are defined only where _final_obs is set; the others hold what the buffer held
+                    fo = arrays[nm]["final_obs"]
+                    ended = arrays[nm]["_final_obs"].view((n,) + (1,) * (fo.dim() - 1))
+                    arrays[nm]["final_obs"] = torch.where(ended, fo, torch.zeros_like(fo))
+        sync()
+        dump_outputs(args.dump_outputs, arrays, n, 0 if split else rank * n, DUMP_BYTES // world, f"rank{rank}_" if world > 1 else "")
+
+    head = args.path
     sync()
     results = {}
-    # buffer priming, untimed and not counted as warm-up steps: one launch of the timed shape, so that the [kc, N, ...] trajectory
-    # (tens of GB) is allocated and touched before the timed region — on a fresh box the first hipMalloc of that size took ~0.5 s
-    for nm in names:
-        with on_stream(nm):
-            envs[nm].rollout(min(kc[nm], K), action_seed=123, t0=0, trajectory=True, per_step=True)
-        count(nm, "rollout", min(kc[nm], K))
-    sync()
-    run_rollout(max(W, 1), K)                                        # W untimed warm-up steps
     t_roll = 0 if wl.get("episode_start") else K + max(W, 1)
     # the events' second pass only where it repeats the first pass's work: snake (episodes of tens of steps: a steady state) and the
     # workloads that restart their episodes before every region
     same_work = len(names) == 1 and (names[0] == "snake" or bool(wl.get("episode_start")))
-    results["rollout"] = timed(lambda rep, marks: run_rollout(K, t_roll if wl.get("episode_start") else t_roll + rep * K, marks), "rollout", same_work)
+    if full or head == "rollout":
+        # buffer priming, untimed and not counted as warm-up steps: one launch of the timed shape, so that the [kc, N, ...] trajectory
+        # (tens of GB) is allocated and touched before the timed region — on a fresh box the first hipMalloc of that size took ~0.5 s
+        for nm in names:
+            with on_stream(nm):
+                envs[nm].rollout(min(kc[nm], K), action_seed=123, t0=0, trajectory=True, per_step=True)
+            count(nm, "rollout", min(kc[nm], K))
+        sync()
+        run_rollout(max(W, 1), K)                                    # W untimed warm-up steps
+        results["rollout"] = timed(lambda rep, marks: run_rollout(K, t_roll if wl.get("episode_start") else t_roll + rep * K, marks), "rollout", same_work)
+        if head == "rollout":
+            dump("rollout")
     withfin_raw = None
-    if not dry and len(names) == 1 and not args.no_final_obs_leg:
+    if full and not dry and len(names) == 1 and not args.no_final_obs_leg:
         nm = names[0]
         envs[nm].collect_final_obs(rows_per_env=fin_rows[nm])
         R_keep, R = R, min(R, 3)
@@ -616,19 +693,22 @@ def main():
     # profiles/r04_snake_warmup_sweep.txt).  The contract's W warm-up steps decide where `value` is measured; this leg says what a consumer
     # that never resets the batch sees: --steady-steps more untimed steps, then the same K steps, 3 regions.
     steady_raw = None
-    if not dry and len(names) == 1 and not wl.get("episode_start") and args.steady_steps > 0:
+    if full and not dry and len(names) == 1 and not wl.get("episode_start") and args.steady_steps > 0:
         t_ss = t_roll + (R + 8) * K
         run_rollout(args.steady_steps, t_ss)
         R_keep, R = R, min(R, 3)
         steady_raw = timed(lambda rep, marks: run_rollout(K, t_ss + args.steady_steps + rep * K, None), "rollout_steady", False)
         R = R_keep
-    if not dry:
+    if full and not dry:
         for e in envs.values():                                      # the trajectory buffers are not needed by the API leg
             e._bufs.pop("traj", None)
         torch.cuda.empty_cache()
-    actions = {nm: (None if dry else make_actions(nm, K + W, n, dev)) for nm in names}  # API path: K step() calls, HBM-resident actions
-    run_steps(actions, 0, W)
-    results["step"] = timed(lambda rep, marks: run_steps(actions, W, W + K, marks), "step", same_work)
+    if full or head == "step":
+        actions = {nm: (None if dry else make_actions(nm, K + W, n, dev)) for nm in names}  # API path: K step() calls, HBM-resident actions
+        run_steps(actions, 0, W)
+        results["step"] = timed(lambda rep, marks: run_steps(actions, W, W + K, marks), "step", same_work)
+        if head == "step":
+            dump("step")
     graph_leg = None
     if args.graph and len(names) == 1 and not dry:
         nm, Kg = names[0], min(K, 256)
@@ -653,7 +733,7 @@ def main():
     if "snake" in envs:
         assert envs["snake"].invalid_action_count() == 0
     measured = None
-    if not dry and rank == 0:
+    if full and not dry and rank == 0:
         del actions
         torch.cuda.empty_cache()
         measured = measure_copy_bandwidth(dev)
@@ -672,12 +752,14 @@ def main():
         graph_leg["value"] = n * world * graph_leg["steps_per_replay"] / gwall
         graph_leg["ms_per_step"] = gwall * 1e3 / graph_leg["steps_per_replay"]
     if rank == 0:
-        head, other = args.path, ("step" if args.path == "rollout" else "rollout")
+        other = "step" if head == "rollout" else "rollout"
         total_envs = n * len(ENVS) if split else n * len(names) * world
 
         def block(path):
             wall, gpu_ms = walls[path], results[path][1]
             b = {"path": path, "value": total_envs * K / wall, "unit": "env-steps/s", "ms_per_step": wall * 1e3 / K, "spread": spread[path]}
+            if not full:
+                return b
             if segments.get(path) and len(names) == 1:
                 sg = segments[path][names[0]]
                 if sg:
@@ -734,9 +816,10 @@ def main():
                                          + (f"; a whole episode is {wl['episode']} steps: --episode" if wl.get("episode") and K != wl["episode"] else "") + ")"
                                          if wl.get("episode_start")
                                          else f"the timed regions start {K + max(W, 1) + min(kc[names[0]], K)} steps after the batch was reset together (W warm-up steps + one priming launch); "
-                                              "the batch's steady state is the steady_state block")},
-            "roofline": hb["roofline"] if len(names) == 1 else hb["roofline_aggregate"],
+                                              "the batch's steady state is the steady_state block (--full)")},
         }
+        if full:
+            out["roofline"] = hb["roofline"] if len(names) == 1 else hb["roofline_aggregate"]
         if dry:
             out["data"] = "DRY RUN (CGE_BENCH_DRYRUN=1): no device work, numbers are meaningless"
             out["roofline"] = None
@@ -765,10 +848,11 @@ def main():
                         "`value` above is measured W warm-up steps after the reset, as the contract says, where every ring is still full"}
         if graph_leg:
             out["graph_step"] = graph_leg
-        if len(names) > 1:
+        if full and len(names) > 1:
             out["roofline_per_env_type"] = hb["roofline"]
-        out["api_step" if other == "step" else "fused_rollout"] = block(other)
-        if not args.no_cpu_baseline and world == 1 and not dry:            # the CPU port is timed at N=1 only
+        if full:
+            out["api_step" if other == "step" else "fused_rollout"] = block(other)
+        if full and not args.no_cpu_baseline and world == 1 and not dry:            # the CPU port is timed at N=1 only
             out["cpu_baseline"] = cpu_baseline(names[0] if len(names) == 1 else "snake")
         print(json.dumps(out), flush=True)
         if args.manifest:

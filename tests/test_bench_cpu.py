@@ -99,3 +99,33 @@ def test_episode_and_repeats_shape_the_line():
     assert out["steps"] == 800 and out["spread"]["repeats"] == 3 and len(out["spread"]["all_ms_per_step"]) == 3
     assert out["spread"]["min_ms_per_step"] <= out["ms_per_step"] <= out["spread"]["max_ms_per_step"]
     assert sorted(out["spread"]["all_ms_per_step"])[1] == out["ms_per_step"]
+
+
+def test_dump_outputs_writes_one_seeded_sample_within_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 files only, the same rows of every array of an env type, the same rows from call to call,
+    the data inside the byte budget; a batch that fits is written whole."""
+    import numpy as np
+    import torch
+    import bench
+    n, env0 = 1000, 5000
+    arrays = {"snake": {"obs": (torch.arange(n * 6) % 100).to(torch.int8).view(n, 2, 3), "reward": torch.arange(n, dtype=torch.float32),
+                        "flags": torch.arange(n) % 3 == 0, "reward_sum": torch.arange(n, dtype=torch.float64) * 0.5,
+                        "done_count": torch.arange(n, dtype=torch.int32)}}
+    row = 8 + 6 * 4 + 4 + 4 + 8 + 8
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, n, env0, 100 * row)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"snake_{k}.npy" for k in ("obs", "reward", "flags", "reward_sum", "done_count", "env_index"))
+    got = {f[len("snake_"):-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(x.nbytes for x in got.values()) <= 100 * row
+    for f in files:
+        assert np.array_equal(got[f[len("snake_"):-4]], np.load(tmp_path / "b" / f))
+    idx = got["env_index"].astype(np.int64) - env0
+    assert len(idx) == 100 and len(set(idx)) == 100 and idx.min() >= 0 and idx.max() < n
+    assert got["obs"].dtype == np.float32 and np.array_equal(got["obs"], arrays["snake"]["obs"].numpy()[idx].astype(np.float32))
+    assert got["reward"].dtype == np.float32 and np.array_equal(got["reward"], idx.astype(np.float32))
+    assert got["flags"].dtype == np.float32 and np.array_equal(got["flags"], (idx % 3 == 0).astype(np.float32))
+    assert got["reward_sum"].dtype == np.float64 and np.array_equal(got["reward_sum"], idx * 0.5)
+    assert got["done_count"].dtype == np.float64 and np.array_equal(got["done_count"], idx.astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "whole"), arrays, n, env0, 10 ** 9)
+    assert np.array_equal(np.load(tmp_path / "whole" / "snake_env_index.npy"), np.arange(env0, env0 + n))

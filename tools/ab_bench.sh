@@ -3,11 +3,12 @@
 # bench.py once per library, twice over; prints rollout / step() us per step and roofline fractions
 W=$1; K=$2; WU=$3; shift 3
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${OUT:-$R/out}; mkdir -p $OUT
 for RND in 1 2; do
 for L in "$@"; do
   T=$(basename $L .so)
-  CGE_AMD_LIBRARY=$R/$L timeout -k 10 ${ABTMO:-400} python3 $R/bench.py --workload $W --steps $K --warmup $WU --no-cpu-baseline > $R/gpurun_out/abb_$T.json 2> $R/gpurun_out/abb_$T.err || { echo "$T failed"; tail -3 $R/gpurun_out/abb_$T.err; continue; }
-  python3 - "$R/gpurun_out/abb_$T.json" "$T" <<'PY'
+  CGE_AMD_LIBRARY=$R/$L timeout -k 10 ${ABTMO:-400} python3 $R/bench.py --full --workload $W --steps $K --warmup $WU --no-cpu-baseline > $OUT/abb_$T.json 2> $OUT/abb_$T.err || { echo "$T failed"; tail -3 $OUT/abb_$T.err; continue; }
+  python3 - "$OUT/abb_$T.json" "$T" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 r=d["roofline"]; a=d["api_step"]["roofline"]

@@ -11,6 +11,6 @@ for W in snake_1m crypto_1m traffic_262k parking_131k climate_131k fleet_131k ma
     hetero*) EXTRA="--no-cpu-baseline --repeats 3" ;;
     *) EXTRA="--episode --repeats 5" ;;
   esac
-  timeout -k 10 900 python3 $R/bench.py --workload $W $EXTRA >> $OUT 2>> $R/gpurun_out/bench_all.err || echo "{\"workload\": \"$W\", \"failed\": true}" >> $OUT
+  timeout -k 10 900 python3 $R/bench.py --full --workload $W $EXTRA >> $OUT 2>> ${OUT%.jsonl}.err || echo "{\"workload\": \"$W\", \"failed\": true}" >> $OUT
   echo "$W done"
 done
