@@ -812,10 +812,14 @@ __global__ __launch_bounds__(BLOCK, MINW) void rollout_kernel(Params p) {
                     if ((int64_t)slot < p.fin.cap) fin_index_seg[slot] = (int64_t)t * p.fin.n + i;
                 }
                 uint32_t k = fin_used;
-                while (fm) {                                   // one coalesced 100-byte store per finishing env
+                while (fm) {                                   // per finishing env, its OBS_DW-dword row in coalesced passes of 64 dwords
                     const uint32_t rl = (uint32_t)__builtin_ctzll(fm);
                     fm &= fm - 1ull;
                     if ((int64_t)k < p.fin.cap && lane < (uint32_t)L::OBS_DW) fin_rows_seg[k * (uint32_t)L::OBS_DW + lane] = wave_rows[rl * L::OBS_DW + lane];
+                    if constexpr (L::OBS_DW > 64) {            // even G >= 18: 81..225 dwords, the rest of the row
+                        if ((int64_t)k < p.fin.cap)
+                            for (uint32_t q2 = lane + 64u; q2 < (uint32_t)L::OBS_DW; q2 += 64u) fin_rows_seg[k * (uint32_t)L::OBS_DW + q2] = wave_rows[rl * L::OBS_DW + q2];
+                    }
                     ++k;
                 }
             }

@@ -184,10 +184,17 @@ class DeviceVectorEnv(VectorEnvBase):
     def _final_obs_begin(self):
         pass                                     # every rollout call writes the segments' counts itself
 
+    def _fin_buffers(self):
+        fin = getattr(self, "_fin", None)
+        if fin is None:
+            raise RuntimeError(f"{type(self).__name__}: no terminal-row output is registered; call collect_final_obs(rows_per_env > 0) "
+                               "before rollout() and final_obs()")
+        return fin
+
     def final_obs(self):
         """(rows [m, *obs_shape], step [m], env [m]) delivered by the last rollout(), sorted by (step, env): row j is the terminal
         observation of env[j] at step step[j] of that call.  Gathers the segments' rows on the device (boolean indexing: synchronises)."""
-        rows, index, count, cap = self._fin
+        rows, index, count, cap = self._fin_buffers()
         nseg = count.shape[0]
         keep = (torch.arange(cap, device=self.device)[None, :] < count.clamp(max=cap)[:, None]).reshape(-1)
         idx = index[keep]
@@ -196,7 +203,8 @@ class DeviceVectorEnv(VectorEnvBase):
         return rows[keep][order], idx // self.num_envs, idx % self.num_envs
 
     def final_obs_dropped(self):
-        rows, _, count, cap = self._fin
+        """Terminal rows the last rollout() produced but could not store (its segments were full); synchronises."""
+        rows, _, count, cap = self._fin_buffers()
         return int((count - cap).clamp(min=0).sum().item())
 
     def snapshot(self):

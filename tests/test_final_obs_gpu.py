@@ -24,6 +24,10 @@ def _cases(cge):
         # name: (constructor, kwargs with a short time limit, actions(k, n) -> what rollout(actions=...) takes, action of step t)
         "snake": (cge.SnakeVectorEnv, dict(grid_size=10, max_steps=9), lambda k, n: ri(4, (k, n)), lambda a, t: a[t]),
         "snake15": (cge.SnakeVectorEnv, dict(grid_size=15, max_steps=40), lambda k, n: ri(4, (k, n)), lambda a, t: a[t]),
+        # obs rows wider than 64 dwords (even G >= 18; 20 is the constructor's default): the terminal-row copy takes several passes
+        "snake18": (cge.SnakeVectorEnv, dict(grid_size=18, max_steps=30), lambda k, n: ri(4, (k, n)), lambda a, t: a[t]),
+        "snake20": (cge.SnakeVectorEnv, dict(grid_size=20, max_steps=30), lambda k, n: ri(4, (k, n)), lambda a, t: a[t]),
+        "snake30": (cge.SnakeVectorEnv, dict(grid_size=30, max_steps=30), lambda k, n: ri(4, (k, n)), lambda a, t: a[t]),
         "crypto": (cge.CryptoVectorEnv, dict(action_type="discrete", max_steps=13), lambda k, n: ri(5, (k, n)), lambda a, t: a[t]),
         "traffic": (cge.TrafficVectorEnv, dict(max_steps=21), lambda k, n: ri(3, (k, n, 9)), lambda a, t: a[t]),
         "parking": (cge.ParkingVectorEnv, dict(max_steps=23), lambda k, n: ri(8, (k, n)), lambda a, t: a[t]),
@@ -36,7 +40,7 @@ def _cases(cge):
     }
 
 
-@pytest.mark.parametrize("name", ["snake", "snake15", "crypto", "traffic", "parking", "climate", "fleet", "manufacturing", "hospital"])
+@pytest.mark.parametrize("name", ["snake", "snake15", "snake18", "snake20", "snake30", "crypto", "traffic", "parking", "climate", "fleet", "manufacturing", "hospital"])
 def test_rollout_plus_final_rows_equals_k_step_calls(cge, name):
     Env, kw, make, at = _cases(cge)[name]
     n, k = 64 * 5 + 37, 70                                     # a ragged last segment; every env ends several episodes
@@ -76,3 +80,24 @@ def test_rollout_plus_final_rows_equals_k_step_calls(cge, name):
     env.collect_final_obs(rows_per_env=0)
     for e in (env, twin, nx):
         e.close()
+
+
+@pytest.mark.parametrize("name", ["snake", "crypto", "traffic", "parking", "climate", "fleet", "manufacturing", "hospital"])
+def test_reading_rows_without_the_output_registered_is_a_clear_error(cge, name):
+    """final_obs() / final_obs_dropped() before collect_final_obs(), and after collect_final_obs(0) turned the output off again."""
+    Env, kw, make, at = _cases(cge)[name]
+    n, k = 70, 5
+    env = Env(n, autoreset_mode="SameStep", **kw)
+    env.reset(seed=1)
+    for read in (env.final_obs, env.final_obs_dropped):
+        with pytest.raises(RuntimeError, match="collect_final_obs"):
+            read()
+    env.collect_final_obs(rows_per_env=2)
+    env.rollout(k, actions=make(k, n))
+    assert env.final_obs()[0].shape[0] + env.final_obs_dropped() >= 0
+    env.collect_final_obs(rows_per_env=0)
+    env.rollout(k, actions=make(k, n))
+    for read in (env.final_obs, env.final_obs_dropped):
+        with pytest.raises(RuntimeError, match="collect_final_obs"):
+            read()
+    env.close()

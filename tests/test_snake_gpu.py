@@ -64,12 +64,18 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode, grid, n):
     obs_d, _ = env.reset(seed=900)
     assert np.array_equal(_np(obs_d), o.reset())
     rng = np.random.default_rng(1)
+    same = mode == "SameStep"
     for t in range(300):
         a = rng.integers(0, 4, n).astype(np.int32)
-        od, rd, ted, trd, _ = env.step(a)
-        oo, ro, teo, tro = o.step(a)
+        od, rd, ted, trd, info = env.step(a)
+        res = o.step(a, want_final=same)
+        oo, ro, teo, tro = res[:4]
         assert np.array_equal(_np(od), oo), t
         assert np.array_equal(_np(rd), ro) and np.array_equal(_np(ted), teo.astype(bool)) and not _np(trd).any()
+        if same:                                   # the terminal rows step() returns (odd grids: the byte path of write_final_obs)
+            done = teo.astype(bool)
+            assert np.array_equal(_np(info["_final_obs"]), done), t
+            assert np.array_equal(_np(info["final_obs"])[done], res[4][done]), t
     for f, k in [("score", 0), ("snake_length", 1), ("steps", 2), ("direction", 3), ("food_r", 4), ("food_c", 5),
                  ("episodes", 7), ("head_r", 8), ("head_c", 9), ("needs_reset", 10)]:
         assert np.array_equal(_np(env.info(f)), o.info(k)), f
@@ -262,7 +268,8 @@ def test_million_env_config_properties_and_sampled_parity(cge, oracle):
 
 
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
-@pytest.mark.parametrize("grid,n", [(6, 200), (8, 333), (12, 257), (16, 130), (20, 191)])
+@pytest.mark.parametrize("grid,n", [(6, 200), (8, 333), (12, 257), (16, 130), (20, 191),
+                                    (4, 70), (5, 129), (7, 100), (15, 65), (17, 66), (18, 130), (23, 65), (30, 70)])
 def test_rollout_trajectory_equals_stepping_the_oracle(cge, oracle, mode, grid, n):
     """The fused rollout (writer wave, incremental LDS obs rows, cooperative food placement) for every supported grid:
     each step's obs / reward / terminated of a [K, N, G, G] trajectory equals the oracle stepped with the same actions."""
