@@ -58,6 +58,16 @@ class ManufacturingConfig(C.Structure):
     _fields_ = [("max_steps", C.c_int32), ("autoreset_mode", C.c_int32)]
 
 
+class Pcg64State(C.Structure):
+    """cge_pcg64_state: NumPy's PCG64 bit_generator.state as 40 bytes."""
+    _fields_ = [("state_lo", C.c_uint64), ("state_hi", C.c_uint64), ("inc_lo", C.c_uint64), ("inc_hi", C.c_uint64),
+                ("has_uint32", C.c_uint32), ("uinteger", C.c_uint32)]
+
+
+SAMPLE_INDEX, SAMPLE_UNIFORM, SAMPLE_BITS = 0, 1, 2
+DTYPE_INT8, DTYPE_INT32, DTYPE_INT64, DTYPE_FLOAT32 = 0, 1, 2, 3
+SAMPLER_MAX_K, SAMPLER_MAX_STEPS = 4096, 65535
+
 # name -> (restype, argtypes); also the list tests check against include/cge_amd.h
 _vp, _i32, _i64, _u32, _u64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 SIGNATURES = {
@@ -200,6 +210,15 @@ SIGNATURES = {
     "cge_hospital_done_mask": (C.c_int, [_vp, _vp]),
     "cge_hospital_last_error": (C.c_char_p, [_vp]),
     "cge_hospital_last_kernel": (C.c_char_p, [_vp]),
+    "cge_pcg64_advance": (C.c_int, [C.POINTER(Pcg64State), _u64, _u64]),
+    "cge_sampler_create": (C.c_int, [_i32, _i64, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, C.POINTER(_vp)]),
+    "cge_sampler_destroy": (C.c_int, [_vp]),
+    "cge_sampler_set_state": (C.c_int, [_vp, C.POINTER(Pcg64State), _vp]),
+    "cge_sampler_get_state": (C.c_int, [_vp, C.POINTER(Pcg64State), _vp]),
+    "cge_sampler_sample": (C.c_int, [_vp, _i64, _vp, _i32, _vp]),
+    "cge_sampler_device_bytes": (_sz, [_vp]),
+    "cge_sampler_last_error": (C.c_char_p, [_vp]),
+    "cge_sampler_last_kernel": (C.c_char_p, [_vp]),
 }
 
 _lib = None

@@ -1,5 +1,7 @@
 """Spaces for the vector façade: gymnasium's when it is importable, else attribute-compatible minimal
 stand-ins (the build and GPU boxes have no gymnasium and no network)."""
+from collections.abc import Mapping
+
 import numpy as np
 
 try:  # pragma: no cover - gymnasium is absent in the build image
@@ -7,7 +9,7 @@ try:  # pragma: no cover - gymnasium is absent in the build image
     from gymnasium import spaces as _sp
     from gymnasium.vector.utils import batch_space as _batch_space
     HAVE_GYMNASIUM = True
-    Box, Discrete, MultiDiscrete = _sp.Box, _sp.Discrete, _sp.MultiDiscrete
+    Box, Discrete, MultiDiscrete, MultiBinary, Dict = _sp.Box, _sp.Discrete, _sp.MultiDiscrete, _sp.MultiBinary, _sp.Dict
     VectorEnvBase = _gym.vector.VectorEnv
 
     def batch_space(space, n):
@@ -72,6 +74,67 @@ except Exception:  # ModuleNotFoundError in this image
         def sample(self):
             return (self._rng.random(self.nvec.shape) * self.nvec).astype(self.dtype)
 
+    class MultiBinary(_Space):
+        """gymnasium.spaces.MultiBinary: int8 0 / 1 of shape n; sample() = integers(0, 2, shape, dtype=int8)."""
+
+        def __init__(self, n, seed=None):
+            self.n = tuple(int(v) for v in np.atleast_1d(n)) if not isinstance(n, (int, np.integer)) else int(n)
+            super().__init__(tuple(int(v) for v in np.atleast_1d(n)), np.int8, seed)
+
+        def contains(self, x):
+            x = np.asarray(x)
+            return x.shape == self.shape and np.issubdtype(x.dtype, np.integer) and bool(np.all((x == 0) | (x == 1)))
+
+        def sample(self):
+            return self._rng.integers(0, 2, self.shape, dtype=np.int8)
+
+    class Dict(_Space, Mapping):
+        """gymnasium.spaces.Dict: an ordered mapping of subspaces (keys sorted, as gymnasium sorts a dict argument); each subspace
+        keeps its own generator.  seed(int s) seeds subspace j with default_rng(s).integers(2**31 - 1, size=len(keys))[j] in key
+        order, seed({key: int}) seeds the named subspaces, seed(None) every subspace from OS entropy."""
+
+        def __init__(self, spaces=None, seed=None, **kwargs):
+            spaces = dict(spaces or {}, **kwargs)
+            try:
+                spaces = dict(sorted(spaces.items()))
+            except TypeError:
+                pass
+            self.spaces = spaces
+            self.shape, self.dtype = None, None
+            self.seed(seed)
+
+        def seed(self, seed=None):
+            if isinstance(seed, Mapping):
+                if set(seed) - set(self.spaces):
+                    raise ValueError(f"seed keys {sorted(set(seed) - set(self.spaces))} are not subspaces")
+                for k, s in seed.items():
+                    self.spaces[k].seed(s)
+            elif seed is None:
+                for sp in self.spaces.values():
+                    sp.seed(None)
+            else:
+                self._rng = np.random.default_rng(int(seed))
+                for sp, sub in zip(self.spaces.values(), self._rng.integers(np.iinfo(np.int32).max, size=len(self.spaces))):
+                    sp.seed(int(sub))
+
+        def sample(self):
+            return {k: sp.sample() for k, sp in self.spaces.items()}
+
+        def contains(self, x):
+            return isinstance(x, Mapping) and set(x) == set(self.spaces) and all(sp.contains(x[k]) for k, sp in self.spaces.items())
+
+        def __getitem__(self, key):
+            return self.spaces[key]
+
+        def __iter__(self):
+            return iter(self.spaces)
+
+        def __len__(self):
+            return len(self.spaces)
+
+        def __repr__(self):
+            return "Dict(" + ", ".join(f"{k!r}: {v}" for k, v in self.spaces.items()) + ")"
+
     class VectorEnvBase:
         """Attribute surface of gymnasium.vector.VectorEnv (gymnasium 1.x)."""
         metadata = {}
@@ -105,4 +168,8 @@ except Exception:  # ModuleNotFoundError in this image
             return MultiDiscrete(np.full((n,), space.n, dtype=np.int64))
         if isinstance(space, MultiDiscrete):
             return MultiDiscrete(np.broadcast_to(space.nvec, (n,) + space.nvec.shape).copy())
+        if isinstance(space, MultiBinary):
+            return MultiBinary((n,) + space.shape)
+        if isinstance(space, Dict):
+            return Dict({k: batch_space(v, n) for k, v in space.spaces.items()})
         raise TypeError(space)

@@ -63,7 +63,24 @@ struct Pcg64 {
         has_uint32 = 0;
         uinteger = 0;
     }
-    __device__ __forceinline__ uint64_t next64() {
+    // bit_generator.advance(delta): the LCG moves `delta` (mod 2^128) steps, square-and-multiply as NumPy's pcg64_advance does;
+    // like NumPy it clears the buffered 32-bit half (has_uint32 = uinteger = 0)
+    __host__ __device__ __forceinline__ void advance(u128 delta) {
+        u128 acc_mult = 1, acc_plus = 0, cur_mult = mult(), cur_plus = inc;
+        while (delta) {
+            if (delta & 1) { acc_mult *= cur_mult; acc_plus = acc_plus * cur_mult + cur_plus; }
+            cur_plus = (cur_mult + 1) * cur_plus;
+            cur_mult *= cur_mult;
+            delta >>= 1;
+        }
+        state = acc_mult * state + acc_plus;
+        has_uint32 = 0;
+        uinteger = 0;
+    }
+    // the same LCG jump for a 64-bit delta through the seed-independent table below (one multiply-add pair per set bit); the
+    // 32-bit buffer is left alone: the samplers track it themselves
+    __host__ __device__ __forceinline__ void jump(uint64_t delta);
+    __host__ __device__ __forceinline__ uint64_t next64() {
         state = state * mult() + inc;
         const uint64_t hi = (uint64_t)(state >> 64), lo = (uint64_t)state, x = hi ^ lo;
         const unsigned rot = (unsigned)(state >> 122);
@@ -76,7 +93,7 @@ struct Pcg64 {
         uinteger = (uint32_t)(n >> 32);
         return (uint32_t)n;
     }
-    __device__ __forceinline__ double random() { return (double)(next64() >> 11) * (1.0 / 9007199254740992.0); }
+    __host__ __device__ __forceinline__ double random() { return (double)(next64() >> 11) * (1.0 / 9007199254740992.0); }
     __device__ __forceinline__ double uniform(double lo, double hi) { return lo + (hi - lo) * random(); }
     __device__ __forceinline__ int64_t integers(int64_t low, int64_t high) {      // Generator.integers(low, high), range < 2**32-1
         const uint32_t rng = (uint32_t)(high - low - 1);
@@ -119,5 +136,35 @@ struct Pcg64 {
         return (c0 <= u) + (c1 <= u) + (c2 <= u) + (c3 <= u);
     }
 };
+
+// A jump of d steps is state' = A_d * state + S_d * inc with A_d = mult^d and S_d = sum_{i<d} mult^i: neither depends on the
+// seed, so (A, S) for d = 2^j, j < 64, is one constant table (2 KiB); A_{2d} = A_d^2, S_{2d} = S_d * (A_d + 1).
+struct Pcg64JumpTable { u128 a[64], s[64]; };
+constexpr Pcg64JumpTable make_pcg64_jump_table() {
+    Pcg64JumpTable t{};
+    u128 a = ((u128)0x2360ED051FC65DA4ull << 64) | 0x4385DF649FCCF645ull, s = 1;
+    for (int j = 0; j < 64; ++j) {
+        t.a[j] = a;
+        t.s[j] = s;
+        s = s * (a + 1);
+        a = a * a;
+    }
+    return t;
+}
+__constant__ constexpr Pcg64JumpTable pcg64_jump_table = make_pcg64_jump_table();
+constexpr Pcg64JumpTable pcg64_jump_table_host = make_pcg64_jump_table();
+
+__host__ __device__ __forceinline__ void Pcg64::jump(uint64_t delta) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const Pcg64JumpTable &t = pcg64_jump_table;
+#else
+    const Pcg64JumpTable &t = pcg64_jump_table_host;
+#endif
+    while (delta) {
+        const int j = __builtin_ctzll(delta);
+        state = t.a[j] * state + t.s[j] * inc;
+        delta &= delta - 1;
+    }
+}
 
 }  // namespace cge

@@ -124,6 +124,18 @@ class DeviceVectorEnv(VectorEnvBase):
     def device_bytes(self):
         return int(self._fn("device_bytes")(self._h))
 
+    def action_sampler(self, seed=None, dtype=None):
+        """A DeviceSpaceSampler over this batch's `action_space` (sampling.py): `env.step(env.action_sampler(0).sample())` is
+        `env.step(env.action_space.sample())` for an action_space seeded with 0, as one sampling launch plus the step launch.  Its
+        output is what step() takes with no conversion (int32 for the discrete kinds).  A shard of `make_sharded` samples its
+        slice of the whole batch's stream."""
+        from .sampling import DeviceSpaceSampler
+        space = self.action_space
+        if dtype is None and hasattr(space, "nvec"):
+            dtype = torch.int32
+        return DeviceSpaceSampler(space, self.device, seed=seed, env_index0=self.env_index0,
+                                  global_num_envs=getattr(self, "global_num_envs", None), dtype=dtype)
+
     def last_kernel(self):
         """Name(s) of the kernel(s) the last step() / rollout() launched, as rocprofv3 prints them ("" before the first call)."""
         raw = self._fn("last_kernel")(self._h)

@@ -566,6 +566,60 @@ int cge_hospital_done_mask(cge_hospital *h, uint8_t *done_out);
 const char *cge_hospital_last_error(const cge_hospital *h);
 const char *cge_hospital_last_kernel(const cge_hospital *h);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Action-space sampler: `action_space.sample()` of a batched space on the device               */
+/*   Every reference script drives its env with env.action_space.sample() (snake_env_classic/    */
+/*   example.py:23, smart_parking_env/examples/test_env.py:52, traffic_management_env/demo.py:49, */
+/*   crypto_trading_env/test_crypto_trading.py:151, smartclimate_rl-main/examples/demo.py:9);     */
+/*   the vector form is envs.step(envs.action_space.sample()).  A sampler handle owns one NumPy   */
+/*   PCG64 stream (np.random.default_rng(seed), seeded on the host) and writes, bit for bit,      */
+/*   what successive sample() calls of the batched space draw from it (gymnasium 1.x):            */
+/*     CGE_SAMPLE_INDEX    MultiDiscrete / batched Discrete: one random() per element, C order,   */
+/*                         int(trunc(u * nvec[col])); out int32 or int64                           */
+/*     CGE_SAMPLE_UNIFORM  bounded Box: one random() per element; out float32 =                    */
+/*                         float32(low + (high - low) * u) (Generator.uniform), out int8 / int32 = */
+/*                         floor(low + ((high + 1) - low) * u) (gymnasium's integer-Box path)      */
+/*     CGE_SAMPLE_BITS     MultiBinary: Generator.integers(0, 2, dtype=int8): 32-bit words of the   */
+/*                         buffered next32 path (carry kept across calls), 4 bytes per word low    */
+/*                         byte first, byte b -> (b * 2) >> 8; out int8                            */
+/*   params (host, copied at create): INDEX nvec[k] (integers >= 1, as doubles); UNIFORM low[k]    */
+/*   then high[k] (finite, low <= high); BITS none.  Column c of every row uses params[c].         */
+/*   Rows [row0, row0 + n_rows) of a world batch of world_rows rows: a shard draws its slice of    */
+/*   the world's stream and every call advances the stream by the world's draw count, so shards   */
+/*   of a sharding.make_sharded batch sample exactly what the unsplit batch does.                 */
+/*   cge_sampler_sample writes steps successive calls, [steps, n_rows, k], advances the stream on */
+/*   the device inside the same launch (no host sync; safe under graph capture and replay) and    */
+/*   takes the calls in stream order: one handle is not used on two streams at once.             */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_sampler cge_sampler;
+
+/* NumPy's bit_generator.state of a PCG64: {"state": {"state", "inc"}, "has_uint32", "uinteger"} (40 bytes) */
+typedef struct {
+    uint64_t state_lo, state_hi, inc_lo, inc_hi;
+    uint32_t has_uint32, uinteger;
+} cge_pcg64_state;
+
+enum { CGE_SAMPLE_INDEX = 0, CGE_SAMPLE_UNIFORM = 1, CGE_SAMPLE_BITS = 2 };
+enum { CGE_DTYPE_INT8 = 0, CGE_DTYPE_INT32 = 1, CGE_DTYPE_INT64 = 2, CGE_DTYPE_FLOAT32 = 3 };
+enum { CGE_SAMPLER_MAX_K = 4096, CGE_SAMPLER_MAX_STEPS = 65535 };
+
+/* host only (no device needed): bit_generator.advance(delta_hi * 2^64 + delta_lo); clears has_uint32 and uinteger as NumPy does */
+int cge_pcg64_advance(cge_pcg64_state *state, uint64_t delta_lo, uint64_t delta_hi);
+/* k columns per row, 1 <= k <= CGE_SAMPLER_MAX_K; 0 <= row0, n_rows >= 1, row0 + n_rows <= world_rows.  The stream starts as
+ * default_rng(0) until set_state */
+int cge_sampler_create(int32_t kind, int64_t k, const double *params, int64_t n_rows, int64_t row0, int64_t world_rows, int device,
+                       cge_sampler **out);
+int cge_sampler_destroy(cge_sampler *h);
+/* host state in / out; both synchronise `stream` */
+int cge_sampler_set_state(cge_sampler *h, const cge_pcg64_state *state, void *stream);
+int cge_sampler_get_state(cge_sampler *h, cge_pcg64_state *state, void *stream);
+/* out: DEVICE [steps, n_rows, k] of out_dtype (CGE_DTYPE_*; INDEX: int32 / int64, UNIFORM: float32 / int8 / int32, BITS: int8);
+ * 1 <= steps <= CGE_SAMPLER_MAX_STEPS */
+int cge_sampler_sample(cge_sampler *h, int64_t steps, void *out, int32_t out_dtype, void *stream);
+size_t cge_sampler_device_bytes(const cge_sampler *h);
+const char *cge_sampler_last_error(const cge_sampler *h);
+const char *cge_sampler_last_kernel(const cge_sampler *h);
+
 #ifdef __cplusplus
 }
 #endif
