@@ -124,13 +124,18 @@ int snapshot_set(H *h, const void *host, hipStream_t s) {
 // | (cur[k+1] & 0x7fffffff), and g(y) = (y >> 1) ^ (y & 1 ? 0x9908b0df : 0) gives y back (bit 31 of g(y) is y's bit 0).  What cannot
 // be recovered, the low 31 bits of cur[0], no future output depends on.
 // old0: the saved word 0 of the current generation (its dead low bits), or nullptr: then they read as zero.
-inline void mt_export_cpython(const uint32_t *w, uint32_t pos, uint32_t pretw, uint32_t *omt, int32_t *idx, const uint32_t *old0 = nullptr) {
+// The un-twist of word k reads word k + 397 of the current generation, so it can take back at most MT_EXPORT_MAX_AHEAD words
+// of the next generation (224 in whole 32-word chunks).  The kernels stay far below it (crypto: at most 64 words, traffic: at most
+// 96; tests/test_mt_export_cpu.py derives both); a longer run is refused (returns false, *idx = -1) instead of read past the record.
+constexpr uint32_t MT_EXPORT_MAX_AHEAD = 624u - 397u;
+inline bool mt_export_cpython(const uint32_t *w, uint32_t pos, uint32_t pretw, uint32_t *omt, int32_t *idx, const uint32_t *old0 = nullptr) {
     memcpy(omt, w, 624 * 4);
     // a cursor that has just wrapped (pos 0) with chunks of the new generation already twisted: CPython regenerates lazily, its
     // state at this point is index 624 over the OLD generation — the same un-twist, seen from the end of that generation
     if (pos == 0u && pretw > 0u && pretw < 624u) { pos = 624u; pretw += 624u; }
     if (pretw > 624u) {
         const uint32_t ahead = pretw - 624u;         // words [0, ahead) belong to the next generation
+        if (ahead > MT_EXPORT_MAX_AHEAD) { *idx = -1; return false; }
         std::vector<uint32_t> y(ahead);
         for (uint32_t k = 0; k < ahead; ++k) {
             const uint32_t g = omt[k] ^ omt[k + 397];          // k + 397 < 624: a word of the current generation
@@ -144,14 +149,15 @@ inline void mt_export_cpython(const uint32_t *w, uint32_t pos, uint32_t pretw, u
         omt[ahead] = (omt[ahead] & 0x80000000u) | (y[ahead - 1] & 0x7fffffffu);   // (its low bits were never changed: a consistency no-op)
         pretw = 624;
     }
-    if (pretw >= 624u) { *idx = (int32_t)pos; return; }
-    if (pos == 0 && pretw == 0) { *idx = 624; return; }
+    if (pretw >= 624u) { *idx = (int32_t)pos; return true; }
+    if (pos == 0 && pretw == 0) { *idx = 624; return true; }
     for (uint32_t k = pretw > pos ? pretw : pos; k < 624u; ++k) {
         const uint32_t k1 = k + 1 == 624u ? 0 : k + 1, km = k + 397 >= 624u ? k + 397 - 624 : k + 397;
         const uint32_t t = (omt[k] & 0x80000000u) | (omt[k1] & 0x7fffffffu);
         omt[k] = omt[km] ^ (t >> 1) ^ ((t & 1u) ? 0x9908b0dfu : 0u);
     }
     *idx = (int32_t)pos;
+    return true;
 }
 
 

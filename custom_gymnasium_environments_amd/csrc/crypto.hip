@@ -1283,8 +1283,9 @@ int cge_crypto_get_state(cge_crypto *h, void *host_buf, void *stream) {
         int32_t hd[12] = {(int32_t)e.regime, (int32_t)e.step, (int32_t)e.needs_reset, (int32_t)e.cash_kind,
                           0, 0, (int32_t)e.has_gauss, (int32_t)e.episodes, 0, 0, 0, 0};
         double scv[6] = {e.cash, e.holdings, e.psych, e.trend, e.gauss, e.ep_return};   // [5]: episode return so far
-        mt_export_cpython(&mp[(size_t)i * MT_STRIDE], e.ppos, e.ppretw, (uint32_t *)(p + 96), &hd[4]);
-        mt_export_cpython(&ml[(size_t)i * MT_STRIDE], e.lpos, e.lpretw, (uint32_t *)(p + 96 + MT_N * 4), &hd[5]);
+        if (!mt_export_cpython(&mp[(size_t)i * MT_STRIDE], e.ppos, e.ppretw, (uint32_t *)(p + 96), &hd[4]) ||
+            !mt_export_cpython(&ml[(size_t)i * MT_STRIDE], e.lpos, e.lpretw, (uint32_t *)(p + 96 + MT_N * 4), &hd[5]))
+            return h->fail(CGE_ERR_UNSUPPORTED, "cge_crypto_get_state: a generator stream is twisted further ahead than the export can take back");
         memcpy(p, hd, 48);
         memcpy(p + 48, scv, 48);
         double *hh = (double *)(p + 96 + 2 * MT_N * 4);

@@ -1142,7 +1142,8 @@ int cge_traffic_get_state(cge_traffic *h, void *host_buf, void *stream) {
         double total_reward;
         uint32_t mt_pos, mt_pretw, mt_old0;
         to_record(&st[(size_t)i * recw], ni, hd, &total_reward, w, &mt_pos, &mt_pretw, &mt_old0);
-        mt_export_cpython(&mt[(size_t)i * MT_STRIDE], mt_pos, mt_pretw, (uint32_t *)(w + 16 * ni), &hd[3], &mt_old0);
+        if (!mt_export_cpython(&mt[(size_t)i * MT_STRIDE], mt_pos, mt_pretw, (uint32_t *)(w + 16 * ni), &hd[3], &mt_old0))
+            return h->fail(CGE_ERR_UNSUPPORTED, "cge_traffic_get_state: the generator stream is twisted further ahead than the export can take back");
         memcpy(p, hd, 24);
         memcpy(p + 24, &total_reward, 8);
     }

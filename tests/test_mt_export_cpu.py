@@ -1,0 +1,193 @@
+"""mt_export_cpython (csrc/cge_host.hpp), the host half of every canonical get_state record, against CPython's own generator.
+
+The device keeps an MT19937 stream as a 640-word block (624 words + 16 mirror words) and a cursor (pos, pretw) in the env's
+record: the words the cursor has reached or made ready are twisted in place, the rest of the generation still holds the previous
+one, and a ready mark beyond 624 means words [0, pretw - 624) already hold the NEXT generation (cge_device.hpp).  The export turns
+that back into CPython's (624 words, index).  This test builds, from a true stream, the block the device would hold at every
+cursor and checks the export: the state it returns continues the stream, and with the saved word 0 (old0) it is CPython's own
+getstate() byte for byte.  No GPU: the shim is compiled for the host from the same header."""
+import ctypes as C
+import os
+import random
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "custom_gymnasium_environments_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+N, M, STRIDE, CHUNK = 624, 397, 640, 32
+DRAWS = 2000
+
+# The export's bound.  Un-twisting word k of the next generation reads word k + 397 of the current one, so at most 624 - 397 = 227
+# next-generation words (224 in whole chunks) can be taken back; from 256 words on the export refuses (get_state then fails with
+# CGE_ERR_UNSUPPORTED) instead of reading past the record.
+EXPORT_MAX_AHEAD = N - M
+
+
+def _src_int(fname, pattern):
+    with open(os.path.join(CSRC, fname)) as f:
+        return int(re.search(pattern, f.read()).group(1))
+
+
+def _next_gen_run(pos, run):
+    """ready mark - 624 after mt_make_ready-style twisting: the last chunk twisted starts below pos + run (unwrapped), and the mark
+    ends at that chunk's end"""
+    lo = pos + run - 1
+    return 0 if lo < N else ((lo - N) & ~(CHUNK - 1)) + CHUNK
+
+
+def test_kernels_stay_inside_the_export_bound():
+    """The longest next-generation run each kernel can leave in a block, derived from its code.
+    crypto (crypto.hip): mt_make_ready(blk, pos, pretw, need = WP or WL = 16, ..., slack = MT_CHUNK): a lane twists a chunk while
+      pretw < pos + need + slack, so the last chunk starts below pos + 16 + 32.
+    traffic (traffic.hip: Draws::park_unit): a group twists while its ready mark is below gend + UNIT, gend = pos + parked + UNIT with
+      at most RING (64, rollout ring) words parked, so the last chunk starts below pos + 64 + 2 * 16.
+    With the cursor at its last word (623) and the chunk rounding: crypto 64 words, traffic 96 — both below the bound.  After the
+    cursor wraps, the same run is the ready mark at pos 0, which the export also un-twists."""
+    wp = _src_int("crypto.hip", r"constexpr int WP = (\d+);")
+    wl = _src_int("crypto.hip", r"constexpr int WL = (\d+);")
+    ring = _src_int("traffic.hip", r"RingLay \{ static constexpr int RING = ROLLOUT \? (\d+) :")
+    unit = _src_int("traffic.hip", r"constexpr int UNIT = (\d+);")
+    crypto_run = max(_next_gen_run(p, max(wp, wl) + CHUNK) for p in range(N))
+    traffic_run = max(_next_gen_run(p, ring + 2 * unit) for p in range(N))
+    assert (crypto_run, traffic_run) == (64, 96), (crypto_run, traffic_run)
+    assert max(crypto_run, traffic_run) <= EXPORT_MAX_AHEAD
+
+
+# ------------------------------------------------------------------ a NumPy MT19937
+def _twist(prev):
+    """the next generation, as CPython's in-place regeneration computes it (words >= 227 read words of the new generation)"""
+    old = prev.astype(np.uint64)
+    new = np.zeros(N, np.uint64)
+
+    def f(hi, lo):
+        y = (hi & 0x80000000) | (lo & 0x7FFFFFFF)
+        return (y >> 1) ^ np.where(y & 1, 0x9908B0DF, 0).astype(np.uint64)
+
+    new[:N - M] = old[M:] ^ f(old[:N - M], old[1:N - M + 1])
+    for a in range(N - M, N - 1, N - M):                 # segments of 227 words: each reads the one before it
+        b = min(a + N - M, N - 1)
+        new[a:b] = new[a - (N - M):b - (N - M)] ^ f(old[a:b], old[a + 1:b + 1])
+    new[N - 1] = new[M - 1] ^ f(old[N - 1:N], new[0:1])[0]
+    return new.astype(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def stream():
+    """generations G0..G4 of a seeded CPython generator (NumPy twist, checked against CPython) and its output words"""
+    r = random.Random(20261016)
+    st = r.getstate()
+    assert st[1][N] == N
+    gens = [np.array(st[1][:N], np.uint32)]
+    for _ in range(4):
+        gens.append(_twist(gens[-1]))
+    out = [r.getrandbits(32) for _ in range(2 * N + DRAWS)]
+    r2 = random.Random()
+    for g in range(1, 5):                                 # the NumPy twist IS CPython's: state after generation g was produced
+        r2.setstate((3, tuple(int(x) for x in gens[g]) + (N,), None))
+        assert tuple(r2.getstate()[1][:N]) == tuple(int(x) for x in gens[g])
+    probe = random.Random()
+    probe.setstate((3, tuple(int(x) for x in gens[1]) + (0,), None))
+    assert [probe.getrandbits(32) for _ in range(3 * N)] == out[:3 * N]
+    return gens, out
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("needs hipcc to compile the export shim")
+    d = tmp_path_factory.mktemp("mt_export")
+    so = str(d / "mt_export_shim.so")
+    subprocess.run([HIPCC, "-O2", "-fPIC", "-shared", "--offload-arch=gfx950", os.path.join(ROOT, "tests", "native", "mt_export_shim.cpp"),
+                    "-o", so], check=True, capture_output=True)
+    L = C.CDLL(so)
+    L.mt_export_shim.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mt_export_shim.restype = C.c_int
+    L.mt_export_shim_max_ahead.restype = C.c_uint32
+    L.mt_ready_decode_shim.argtypes = [C.c_uint32]
+    L.mt_ready_decode_shim.restype = C.c_uint32
+    return L
+
+
+def _block(prev, cur, nxt, pos, pretw):
+    """the block the device holds with its cursor at (pos, pretw) in generation `cur` (cge_device.hpp): the words the cursor has
+    consumed or made ready are twisted, the rest still hold `prev`; a mark beyond 624 put words [0, pretw - 624) of `nxt` in"""
+    blk = np.zeros(STRIDE, np.uint32)
+    twisted = max(pos, min(pretw, N))
+    blk[:twisted] = cur[:twisted]
+    blk[twisted:N] = prev[twisted:N]
+    if pretw > N:
+        blk[:pretw - N] = nxt[:pretw - N]
+    blk[N:] = blk[:STRIDE - N]                            # mirror words
+    return blk
+
+
+def _legal(pos, pretw):
+    """A ready mark beyond 624 means the next generation's first words have been twisted over words of this one; the device does
+    that only to words the cursor has consumed (mt_make_ready twists from max(pretw, pos) on, and wraps the cursor before it
+    reaches them), so pretw - 624 <= pos.  Every other pair is a state the device can hold: marks at or below the cursor are stale
+    marks (words the cursor consumed by twisting them one at a time), pos 0 with 0 < pretw < 624 is a cursor that has just wrapped
+    (or a freshly seeded block made ready), pos 0 with pretw 624 a state imported at index 0."""
+    return pretw <= N or pretw - N <= pos
+
+
+def _export(shim, blk, pos, pretw, old0):
+    omt = np.zeros(N, np.uint32)
+    idx = np.zeros(1, np.int32)
+    o0 = None if old0 is None else np.array([old0], np.uint32)
+    st = shim.mt_export_shim(blk.ctypes.data, pos, pretw, omt.ctypes.data, idx.ctypes.data, None if o0 is None else o0.ctypes.data)
+    return st, omt, int(idx[0])
+
+
+def test_ready_marks_are_the_decoded_codes(shim):
+    marks = [shim.mt_ready_decode_shim(q) for q in range(32)]
+    assert marks == [32 * q for q in range(20)] + [N + 32 * q for q in range(12)]
+    assert shim.mt_export_shim_max_ahead() == EXPORT_MAX_AHEAD
+
+
+@pytest.mark.parametrize("with_old0", [True, False], ids=["old0", "no_old0"])
+def test_export_matches_cpython_at_every_cursor(shim, stream, with_old0):
+    gens, out = stream
+    prev, cur, nxt = gens[1], gens[2], gens[3]          # the cursor reads generation 2 = output words [624, 1248)
+    marks = [shim.mt_ready_decode_shim(q) for q in range(32)]
+    r = random.Random()
+    checked = refused = unreachable = 0
+    for pos in range(N):
+        for pretw in marks:
+            if not _legal(pos, pretw):
+                unreachable += 1
+                continue
+            blk = _block(prev, cur, nxt, pos, pretw)
+            # what CPython's getstate() says at this point: its regeneration is lazy, so a cursor at word 0 of `cur` (nothing of it
+            # consumed) is index 624 over `prev` unless the state was imported at index 0 (ready mark 624)
+            if pos == 0 and pretw != N:
+                want_words, want_idx, first = prev, N, N
+            else:
+                want_words, want_idx, first = cur, pos, N + pos
+            ahead = pretw - N if pretw > N else (pretw if pos == 0 and pretw < N else 0)
+            st, omt, idx = _export(shim, blk, pos, pretw, int(want_words[0]) if with_old0 else None)
+            if ahead > EXPORT_MAX_AHEAD:
+                assert st != 0 and idx == -1, (pos, pretw)
+                refused += 1
+                continue
+            assert st == 0, (pos, pretw)
+            assert idx == want_idx, (pos, pretw, idx)
+            if with_old0:
+                assert np.array_equal(omt, want_words), (pos, pretw, np.flatnonzero(omt != want_words)[:5])
+            else:                                          # only the dead low bits of word 0 may differ: they read as zero
+                diff = np.flatnonzero(omt != want_words)
+                assert set(diff.tolist()) <= {0}, (pos, pretw, diff[:5])
+                if ahead:
+                    assert omt[0] == want_words[0] & 0x80000000, (pos, pretw)
+            r.setstate((3, tuple(int(x) for x in omt) + (idx,), None))
+            assert [r.getrandbits(32) for _ in range(DRAWS)] == out[first:first + DRAWS], (pos, pretw)
+            checked += 1
+    # 624 * 32 pairs: the ones with a next-generation run longer than the cursor's position are not device states; of the rest,
+    # the runs beyond the bound (at pos 0, marks 256..608; elsewhere, marks 624 + 256 and up) must be refused
+    assert unreachable == sum(1 for p in range(N) for m in marks if m > N and m - N > p)
+    assert refused == sum(1 for p in range(N) for m in marks if _legal(p, m) and
+                          ((m > N and m - N > EXPORT_MAX_AHEAD) or (p == 0 and EXPORT_MAX_AHEAD < m < N)))
+    assert checked + refused + unreachable == N * 32 and checked > 16000
