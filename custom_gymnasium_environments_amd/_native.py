@@ -58,6 +58,10 @@ class ManufacturingConfig(C.Structure):
     _fields_ = [("max_steps", C.c_int32), ("autoreset_mode", C.c_int32)]
 
 
+class BusConfig(C.Structure):
+    _fields_ = [("max_timesteps", C.c_int32), ("autoreset_mode", C.c_int32)]
+
+
 class Pcg64State(C.Structure):
     """cge_pcg64_state: NumPy's PCG64 bit_generator.state as 40 bytes."""
     _fields_ = [("state_lo", C.c_uint64), ("state_hi", C.c_uint64), ("inc_lo", C.c_uint64), ("inc_hi", C.c_uint64),
@@ -210,6 +214,21 @@ SIGNATURES = {
     "cge_hospital_done_mask": (C.c_int, [_vp, _vp]),
     "cge_hospital_last_error": (C.c_char_p, [_vp]),
     "cge_hospital_last_kernel": (C.c_char_p, [_vp]),
+    "cge_bus_create": (C.c_int, [C.POINTER(BusConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
+    "cge_bus_destroy": (C.c_int, [_vp]),
+    "cge_bus_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
+    "cge_bus_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "cge_bus_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cge_bus_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "cge_bus_info": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "cge_bus_error_count": (_i64, [_vp, _vp]),
+    "cge_bus_snapshot_bytes": (_sz, [_vp]),
+    "cge_bus_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
+    "cge_bus_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
+    "cge_bus_device_bytes": (_sz, [_vp]),
+    "cge_bus_episode_stats": (C.c_int, [_vp, _vp, _vp]),
+    "cge_bus_last_error": (C.c_char_p, [_vp]),
+    "cge_bus_last_kernel": (C.c_char_p, [_vp]),
     "cge_pcg64_advance": (C.c_int, [C.POINTER(Pcg64State), _u64, _u64]),
     "cge_sampler_create": (C.c_int, [_i32, _i64, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, C.POINTER(_vp)]),
     "cge_sampler_destroy": (C.c_int, [_vp]),

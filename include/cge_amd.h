@@ -567,6 +567,78 @@ const char *cge_hospital_last_error(const cge_hospital *h);
 const char *cge_hospital_last_kernel(const cge_hospital *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Bus system  (bus_system_env/environment.py: BusSystemEnv, utils.py, config.py)                */
+/*   4 buses on a 4-stop ring, 50..150 passengers per episode, 500 steps; truncated only (:176).  */
+/*   action int32 [4] in 0..10: the dwell time of each bus (MultiDiscrete([11]*4), :82).          */
+/*   obs: the Dict of :94-123 as KEY-MAJOR PLANES of int32 — gymnasium's batched-Dict layout.     */
+/*   One observation of the whole batch is a slab of CGE_BUS_OBS_INTS * n_envs ints (16-byte      */
+/*   aligned) holding, in this order, one contiguous [n_envs, ...] array per key:                 */
+/*     bus_stops [n,4]  bus_states [n,4] (1 stopped)  bus_remaining_times [n,4]  bus_capacities   */
+/*     [n,4]  bus_passenger_destinations [n,4,4]  stop_waiting_counts [n,4]                       */
+/*     stop_destination_distributions [n,4,4]  timestep [n]  total_delivered [n]                  */
+/*     total_waiting [n]  total_onboard [n]                                                       */
+/*   (the reference's int8 bus_states and Python-int scalars are int32 here).                     */
+/*   Bit-exact: integer state; the reward is a sum of multiples of 0.5.                           */
+/*   Generator: the process-global CPython `random`, drawn only by reset() (utils.py:22-46); the  */
+/*   env never seeds it (reset(seed) reaches np_random only, :127), so cge_bus_seed is the        */
+/*   caller's random.seed(s_i) for env i.  A fresh handle holds empty stops until its first reset.*/
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_bus cge_bus;
+
+typedef struct {
+    int32_t max_timesteps;    /* MAX_TIMESTEPS = 500 (config.py:10, __init__ :57); 0 -> 500; <= 60000 */
+    int32_t autoreset_mode;   /* CGE_AUTORESET_* */
+} cge_bus_config;
+
+enum { CGE_BUS_OBS_INTS = 56 };
+
+enum { /* cge_bus_info int32 fields (`index` = bus or stop 0..3 where noted) — the values behind _get_info (:339-350) */
+    CGE_BUS_INFO_TIMESTEP = 0,
+    CGE_BUS_INFO_TOTAL_DELIVERED = 1,
+    CGE_BUS_INFO_TOTAL_WAITING = 2,
+    CGE_BUS_INFO_TOTAL_ONBOARD = 3,
+    CGE_BUS_INFO_BUS_POSITION = 4,    /* index = bus */
+    CGE_BUS_INFO_BUS_STOPPED = 5,     /* index = bus; 1 = "stopped", 0 = "traveling" */
+    CGE_BUS_INFO_BUS_CAPACITY = 6,    /* index = bus; free seats */
+    CGE_BUS_INFO_STOP_WAITING = 7,    /* index = stop */
+    CGE_BUS_INFO_NEEDS_RESET = 8
+};
+
+/* BusSystemEnv.__init__ :57-92 */
+int cge_bus_create(const cge_bus_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_bus **out);
+int cge_bus_destroy(cge_bus *h);
+/* random.seed(s_i) for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Does not reset the envs. */
+int cge_bus_seed(cge_bus *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :125-151 with generate_passengers (utils.py:22-46) on env i's stream, for envs with mask[i] != 0 (all if NULL);
+ * writes the whole slab if obs_out != NULL */
+int cge_bus_reset(cge_bus *h, const uint8_t *mask, int32_t *obs_out, void *stream);
+/* step :153-186.  actions int32 [n_envs, 4].  An action outside 0..10 raises ValueError in the reference (:160-161); here the env is
+ * left untouched, its row reports (current obs, 0, 0, 0) and a device-side counter is bumped (cge_bus_error_count).
+ * terminated_out is always 0; truncated_out is REQUIRED.  final_obs_out (nullable; a slab): SAME_STEP writes the pieces of the envs
+ * that were truncated in this step, the others are left as they were. */
+int cge_bus_step(cge_bus *h, const int32_t *actions, int32_t *obs_out, float *reward_out, uint8_t *terminated_out,
+                 uint8_t *truncated_out, int32_t *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs, 4], or NULL: bus j of env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 11, j).
+ * obs_out: k slabs obs_step_stride ints apart (a multiple of 4, >= CGE_BUS_OBS_INTS * n_envs), or with stride 0 the last step's slab.
+ * truncated_traj_out [k, n_envs]; done_count counts truncated steps. */
+int cge_bus_rollout(cge_bus *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
+                    int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
+                    int32_t *done_count_out, void *stream);
+/* _get_info :339-350 */
+int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void *stream);
+/* env-steps refused for an invalid action since the last call; synchronises */
+int64_t cge_bus_error_count(cge_bus *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_bus_snapshot_bytes(const cge_bus *h);
+int cge_bus_snapshot_get(cge_bus *h, void *host_buf, void *stream);
+int cge_bus_snapshot_set(cge_bus *h, const void *host_buf, void *stream);
+size_t cge_bus_device_bytes(const cge_bus *h);
+int cge_bus_episode_stats(cge_bus *h, double *return_out, int32_t *length_out);
+const char *cge_bus_last_error(const cge_bus *h);
+const char *cge_bus_last_kernel(const cge_bus *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Action-space sampler: `action_space.sample()` of a batched space on the device               */
 /*   Every reference script drives its env with env.action_space.sample() (snake_env_classic/    */
 /*   example.py:23, smart_parking_env/examples/test_env.py:52, traffic_management_env/demo.py:49, */
