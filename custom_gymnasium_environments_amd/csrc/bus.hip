@@ -361,9 +361,6 @@ struct cge_bus : HandleBase {
     uint32_t *mt = nullptr;
     unsigned long long *err = nullptr;
     static constexpr uint32_t snap_tag = 6u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)bus::COLS * n * sizeof(uint4)}, {mt, (size_t)n * MT_STRIDE * 4}}; }
-    uint32_t snap_extra() const { return 0u; }
-    void set_snap_extra(uint32_t v) { (void)v; }
     bus::Params params() const {
         bus::Params p{};
         p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.max_t = cfg.max_timesteps; p.err_count = err;
@@ -371,7 +368,18 @@ struct cge_bus : HandleBase {
         return p;
     }
     unsigned blocks() const { return (unsigned)((n + bus::BLOCK - 1) / bus::BLOCK); }
-    void release() { (void)hipFree(state); (void)hipFree(mt); (void)hipFree(err); }
+    static int check(const cge_bus_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 0 || c.max_timesteps > 60000 ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_timesteps == 0) cfg.max_timesteps = 500;      // config.py:10
+        CGE_HIP(alloc(state, (size_t)bus::COLS * n * sizeof(uint4), true, true));
+        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
+        CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
+        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        hipLaunchKernelGGL(bus::reset_kernel, dim3(blocks()), dim3(bus::BLOCK), 0, nullptr, params(), 1, 0);
+        return hipGetLastError();
+    }
 };
 
 template <int MODE>
@@ -389,59 +397,14 @@ static void launch_bus(cge_bus *h, const bus::Params &p, int kind, hipStream_t s
 
 extern "C" {
 
-int cge_bus_create(const cge_bus_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_bus **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_timesteps < 0 || cfg->max_timesteps > 60000) return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_bus *h = new cge_bus();
-    h->cfg = *cfg;
-    if (h->cfg.max_timesteps == 0) h->cfg.max_timesteps = 500;      // config.py:10
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t sb = (size_t)bus::COLS * n_envs * sizeof(uint4), mb = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->mt, mb)) != hipSuccess || (e = hipMalloc(&h->err, sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(h->state, 0, sb)) != hipSuccess || (e = hipMemset(h->err, 0, sizeof(unsigned long long))) != hipSuccess) {
-        h->release();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + mb + sizeof(unsigned long long);
-    e = launch_mt_seed(h->mt, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) {
-        bus::Params p = h->params();
-        hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, nullptr, p, 1, 0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        h->release();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_bus_destroy(cge_bus *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    h->release();
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(bus)
 
 int cge_bus_seed(cge_bus *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    bus::Params p = h->params();
-    hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, as_stream(stream), p, 0, 1);   // rewind cursors
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, as_stream(stream), h->params(), 0, 1);   // rewind cursors
+    return launched(h);
 }
 
 int cge_bus_reset(cge_bus *h, const uint8_t *mask, int32_t *obs_out, void *stream) {
@@ -450,40 +413,35 @@ int cge_bus_reset(cge_bus *h, const uint8_t *mask, int32_t *obs_out, void *strea
     bus::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, as_stream(stream), p, 0, 0);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_bus_step(cge_bus *h, const int32_t *actions, int32_t *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
                  int32_t *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out || !truncated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_bus_step: null actions/obs/reward/terminated/truncated pointer");
+    bus::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
+                             "cge_bus_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out, truncated_out,
+                             final_obs_out)) return st;
     DeviceGuard g(h->device);
-    bus::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     launch_bus(h, p, 0, as_stream(stream));
     h->last_kernel = "cge::bus::step_kernel<" + std::to_string(h->cfg.autoreset_mode) + ">";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_bus_rollout(cge_bus *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
                     int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
                     int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && (obs_step_stride < h->n * bus::OBS || obs_step_stride % 4 != 0)))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_bus_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    bus::Params p;
+    const int st = rollout_params_nofin(h, p, obs_step_stride % 4 == 0, h->n * bus::OBS, "cge_bus_rollout: bad k_steps / obs_step_stride", k_steps,
+                                        action_seed, t0, obs_out, obs_step_stride, reward_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    bus::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.truncated = truncated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
+    p.actions = actions; p.truncated = truncated_traj_out;
     launch_bus(h, p, actions ? 1 : 2, as_stream(stream));
     h->last_kernel = "cge::bus::rollout_kernel<" + std::to_string(h->cfg.autoreset_mode) + (actions ? ", true>" : ", false>");
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void *stream) {
@@ -491,33 +449,11 @@ int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void
     if (!out || field_id < 0 || field_id > CGE_BUS_INFO_NEEDS_RESET || index < 0 || index > 3)
         return h->fail(CGE_ERR_INVALID_ARG, "cge_bus_info: bad field / index / null out");
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(bus::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, index, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(bus::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, index, out);
+    return launched(h);
 }
 
-int64_t cge_bus_error_count(cge_bus *h, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    unsigned long long v = 0;
-    if (hipStreamSynchronize(as_stream(stream)) != hipSuccess) return CGE_ERR_HIP;
-    if (hipMemcpy(&v, h->err, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return CGE_ERR_HIP;
-    if (v && hipMemset(h->err, 0, sizeof v) != hipSuccess) return CGE_ERR_HIP;
-    return (int64_t)v;
-}
-
-size_t cge_bus_snapshot_bytes(const cge_bus *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_bus_snapshot_get(cge_bus *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_bus_snapshot_set(cge_bus *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_bus_device_bytes(const cge_bus *h) { return h ? h->device_bytes : 0; }
-int cge_bus_episode_stats(cge_bus *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_bus_last_error(const cge_bus *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_bus_last_kernel(const cge_bus *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_ERROR_COUNT(bus)
+CGE_DEFINE_SNAPSHOT(bus)
 
 }  // extern "C"

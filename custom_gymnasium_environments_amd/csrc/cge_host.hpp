@@ -29,6 +29,31 @@ struct HandleBase {
     int64_t fin_cap = 0;           // rows per segment
     int32_t *fin_count = nullptr;  // [n_segments]: rows the last rollout delivered for the segment (may exceed fin_cap: the surplus was dropped)
 
+    // The handle's device arrays.  alloc() is the only place one is created; free_all(), device_bytes and the snapshot's blobs()
+    // all follow from what it recorded, in registration order.  snap: the array is part of a whole-handle snapshot.
+    struct Array { void *ptr; size_t bytes; bool snap; };
+    std::vector<Array> arrays;
+    template <class T>
+    hipError_t alloc(T *&slot, size_t bytes, bool zero, bool snap) {
+        hipError_t e = hipMalloc(&slot, bytes);
+        if (e != hipSuccess) return e;
+        arrays.push_back({slot, bytes, snap});
+        device_bytes += bytes;
+        return zero ? hipMemset(slot, 0, bytes) : hipSuccess;
+    }
+    void free_all() {
+        for (const Array &a : arrays) (void)hipFree(a.ptr);
+        arrays.clear();
+    }
+    std::vector<std::pair<void *, size_t>> blobs() const {
+        std::vector<std::pair<void *, size_t>> b;
+        for (const Array &a : arrays)
+            if (a.snap) b.emplace_back(a.ptr, a.bytes);
+        return b;
+    }
+    uint32_t snap_extra() const { return 0u; }       // host-side state a snapshot carries in its header (fleet has its own pair)
+    void set_snap_extra(uint32_t v) { (void)v; }
+
     int fail(int status, const char *what, hipError_t e = hipSuccess) {
         char buf[512];
         if (e != hipSuccess)
@@ -77,11 +102,131 @@ int register_final_obs(H *h, void *rows, int64_t *index, int64_t seg_capacity, i
         if (_e != hipSuccess) return (h)->fail(CGE_ERR_HIP, #expr, _e);    \
     } while (0)
 
+// inside a function that returns hipError_t (a handle's init()): pass the first failure on
+#define CGE_HIP(expr)                          \
+    do {                                       \
+        hipError_t _e = (expr);                \
+        if (_e != hipSuccess) return _e;       \
+    } while (0)
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }   // blocks of 256 threads, one thread per env
+
+// the tail of every entry point that launched kernels
+template <class H>
+int launched(H *h) {
+    CGE_TRY(h, hipGetLastError());
+    return CGE_OK;
+}
+
+// cge_<env>_create / _destroy.  An env type's handle H supplies what is its own:
+//   static int check(const config &)   the status of a config it cannot run (CGE_OK: fine); runs before the device is looked at
+//   hipError_t init()                  defaults, derived fields, alloc() of every device array, initial seed and reset launches
+// The order of the checks decides the status code: arguments, config, device.  *out is null on every failure.
+template <class H, class C>
+int create_handle(const C *cfg, int64_t n_envs, int device, int64_t env_index0, H **out) {
+    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (int st = H::check(*cfg)) return st;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
+    H *h = new H();
+    h->cfg = *cfg; h->n = n_envs; h->env0 = env_index0; h->device = device;
+    DeviceGuard g(device);
+    hipError_t e = h->init();
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        h->free_all();
+        delete h;
+        return CGE_ERR_HIP;
+    }
+    *out = h;
+    return CGE_OK;
+}
+template <class H>
+int destroy_handle(H *h) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    (void)hipDeviceSynchronize();
+    h->free_all();
+    delete h;
+    return CGE_OK;
+}
+inline bool bad_autoreset_mode(int mode) { return mode < 0 || mode > 2; }
+
+// Head of cge_<env>_step: null checks (`have`: every pointer this env type requires is there; `what`: the error text if not), then
+// p = h->params() with one step's outputs filled in.  The action pointers stay with the caller.
+template <class H, class P, class O>
+int step_params(H *h, P &p, bool have, const char *what, O *obs, float *reward, uint8_t *terminated, uint8_t *truncated, O *final_obs) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    if (!have) return h->fail(CGE_ERR_INVALID_ARG, what);
+    p = h->params();
+    p.obs = obs; p.reward = reward; p.terminated = terminated; p.truncated = truncated; p.final_obs = final_obs; p.k_steps = 1;
+    return CGE_OK;
+}
+
+// Head of cge_<env>_rollout, h not null: k_steps and obs_step_stride (0, or at least one step's `step_elems` = n * obs row) are
+// checked together with what the env type adds (`env_ok`), then p = h->params() with the rollout's arguments filled in.
+// Returns CGE_OK for k_steps == 0 too: the caller returns then, there is nothing to launch.
+template <class H, class P, class O, class S>
+int rollout_params_nofin(H *h, P &p, bool env_ok, int64_t step_elems, const char *what, int32_t k_steps, uint64_t a_seed, int64_t t0, O *obs,
+                         int64_t obs_step_stride, float *reward, S *reward_sum, int32_t *done_count) {
+    if (!env_ok || k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < step_elems))
+        return h->fail(CGE_ERR_INVALID_ARG, what);
+    p = h->params();
+    p.k_steps = k_steps; p.a_seed = a_seed; p.t0 = t0; p.obs = obs; p.obs_step_stride = obs_step_stride;
+    p.reward = reward; p.reward_sum = reward_sum; p.done_count = done_count;
+    return CGE_OK;
+}
+// ... and, for the env types whose rollout reports terminated and compacts terminal observations (all but the bus system), those two
+template <class H, class P, class O, class S>
+int rollout_params(H *h, P &p, bool env_ok, int64_t step_elems, const char *what, int32_t k_steps, uint64_t a_seed, int64_t t0, O *obs,
+                   int64_t obs_step_stride, float *reward, uint8_t *terminated, S *reward_sum, int32_t *done_count) {
+    const int st = rollout_params_nofin(h, p, env_ok, step_elems, what, k_steps, a_seed, t0, obs, obs_step_stride, reward, reward_sum, done_count);
+    if (st != CGE_OK) return st;
+    p.terminated = terminated;
+    p.fin = decltype(p.fin){h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    return CGE_OK;
+}
+
+// The entry points that read the same in every env type (inside extern "C")
+#define CGE_DEFINE_LIFECYCLE(ENV)                                                                                                        \
+    int cge_##ENV##_create(const cge_##ENV##_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_##ENV **out) {             \
+        return cge::create_handle(cfg, n_envs, device, env_index0, out);                                                                 \
+    }                                                                                                                                    \
+    int cge_##ENV##_destroy(cge_##ENV *h) { return cge::destroy_handle(h); }                                                             \
+    size_t cge_##ENV##_device_bytes(const cge_##ENV *h) { return h ? h->device_bytes : 0; }                                              \
+    int cge_##ENV##_episode_stats(cge_##ENV *h, double *return_out, int32_t *length_out) {                                               \
+        if (!h) return CGE_ERR_INVALID_ARG;                                                                                              \
+        h->ep_ret = return_out; h->ep_len = length_out;                                                                                  \
+        return CGE_OK;                                                                                                                   \
+    }                                                                                                                                    \
+    const char *cge_##ENV##_last_error(const cge_##ENV *h) { return h ? h->last_error.c_str() : "null handle"; }                         \
+    const char *cge_##ENV##_last_kernel(const cge_##ENV *h) { return h ? h->last_kernel.c_str() : ""; }
+
+#define CGE_DEFINE_DONE_MASK(ENV)                                    \
+    int cge_##ENV##_done_mask(cge_##ENV *h, uint8_t *done_out) {     \
+        if (!h) return CGE_ERR_INVALID_ARG;                          \
+        h->done_out = done_out;                                      \
+        return CGE_OK;                                               \
+    }
+
+// the handle's `err`: one counter of the conditions a kernel reports instead of acting on; reading it clears it
+#define CGE_DEFINE_ERROR_COUNT(ENV)                                                                              \
+    int64_t cge_##ENV##_error_count(cge_##ENV *h, void *stream) {                                                \
+        if (!h) return CGE_ERR_INVALID_ARG;                                                                      \
+        cge::DeviceGuard g(h->device);                                                                           \
+        unsigned long long v = 0;                                                                                \
+        if (hipStreamSynchronize(cge::as_stream(stream)) != hipSuccess) return CGE_ERR_HIP;                      \
+        if (hipMemcpy(&v, h->err, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return CGE_ERR_HIP;            \
+        if (v && hipMemset(h->err, 0, sizeof v) != hipSuccess) return CGE_ERR_HIP;                               \
+        return (int64_t)v;                                                                                       \
+    }
 
 // Whole-handle snapshots (checkpoint / resume) for the env types without a canonical per-env record: a 32-byte header
 // {magic, n_envs, env tag, extra} followed by the handle's device arrays in their device layout.  Only valid for a handle
-// created with the same n_envs and config.  H provides blobs() -> vector<pair<void*, size_t>>, snap_tag, snap_extra().
+// created with the same n_envs and config.  The blobs are the arrays H registered with alloc(..., snap = true); H adds snap_tag.
 struct SnapHeader { uint64_t magic; int64_t n; uint32_t tag, extra; uint64_t reserved; };
 // "CGESNAP3": 1 = round 1; 2 = round 2 (MT blocks grew mirror words 624..639, ep_return fields in the records) — blobs of an older
 // layout are refused instead of being read with the wrong meaning
@@ -116,6 +261,10 @@ int snapshot_set(H *h, const void *host, hipStream_t s) {
     h->set_snap_extra(hd.extra);
     return CGE_OK;
 }
+#define CGE_DEFINE_SNAPSHOT(ENV)                                                                                                                            \
+    size_t cge_##ENV##_snapshot_bytes(const cge_##ENV *h) { return h ? cge::snapshot_bytes(h) : 0; }                                                       \
+    int cge_##ENV##_snapshot_get(cge_##ENV *h, void *host_buf, void *stream) { return cge::snapshot_get(h, host_buf, cge::as_stream(stream)); }            \
+    int cge_##ENV##_snapshot_set(cge_##ENV *h, const void *host_buf, void *stream) { return cge::snapshot_set(h, host_buf, cge::as_stream(stream)); }
 
 // device stream (block, cursor, ready mark) -> CPython layout (624 words of ONE generation + index of the next unconsumed word).
 // Words [pos, pretw) are twisted already; the rest of the generation is twisted here.  A ready mark beyond 624 means the first

@@ -275,9 +275,6 @@ struct cge_climate : HandleBase {
     cge_climate_config cfg{};
     uint4 *state = nullptr;
     static constexpr uint32_t snap_tag = 2u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)climate::COLS * n * sizeof(uint4)}}; }
-    uint32_t snap_extra() const { return 0u; }
-    void set_snap_extra(uint32_t v) { (void)v; }
     climate::Params params() const {
         climate::Params p{};
         p.state = state; p.n = n; p.env0 = env0; p.mode = cfg.autoreset_mode; p.max_occ = cfg.max_occupancy; p.max_steps = cfg.episode_minutes;
@@ -285,53 +282,23 @@ struct cge_climate : HandleBase {
         return p;
     }
     unsigned blocks() const { return (unsigned)((n + climate::BLOCK - 1) / climate::BLOCK); }
+    static int check(const cge_climate_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_occupancy < 0 || c.max_occupancy > 15 || c.episode_minutes < 0 || c.episode_minutes > 65535
+                   ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_occupancy == 0) cfg.max_occupancy = 8;
+        if (cfg.episode_minutes == 0) cfg.episode_minutes = 1440;
+        CGE_HIP(alloc(state, (size_t)climate::COLS * n * sizeof(uint4), true, true));
+        // default generators: default_rng(env_index0 + i); no reset (fresh env)
+        hipLaunchKernelGGL(climate::reset_kernel, dim3(blocks()), dim3(climate::BLOCK), 0, nullptr, params(), 1);
+        return hipGetLastError();
+    }
 };
 
 extern "C" {
 
-int cge_climate_create(const cge_climate_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_climate **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_occupancy < 0 || cfg->max_occupancy > 15 || cfg->episode_minutes < 0 ||
-        cfg->episode_minutes > 65535)
-        return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_climate *h = new cge_climate();
-    h->cfg = *cfg;
-    if (h->cfg.max_occupancy == 0) h->cfg.max_occupancy = 8;
-    if (h->cfg.episode_minutes == 0) h->cfg.episode_minutes = 1440;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t sb = (size_t)climate::COLS * n_envs * sizeof(uint4);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMemset(h->state, 0, sb)) != hipSuccess) {
-        (void)hipFree(h->state);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb;
-    climate::Params p = h->params();                       // default generators: default_rng(env_index0 + i); no reset (fresh env)
-    hipLaunchKernelGGL(climate::reset_kernel, dim3(h->blocks()), dim3(climate::BLOCK), 0, nullptr, p, 1);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(h->state);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_climate_destroy(cge_climate *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(h->state);
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(climate)
 
 int cge_climate_seed(cge_climate *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
@@ -339,8 +306,7 @@ int cge_climate_seed(cge_climate *h, const uint64_t *seeds, uint64_t base_seed, 
     climate::Params p = h->params();
     p.seeds = seeds; p.base_seed = base_seed;
     hipLaunchKernelGGL(climate::reset_kernel, dim3(h->blocks()), dim3(climate::BLOCK), 0, as_stream(stream), p, 1);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_climate_reset(cge_climate *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -349,41 +315,36 @@ int cge_climate_reset(cge_climate *h, const uint8_t *mask, float *obs_out, void 
     climate::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(climate::reset_kernel, dim3(h->blocks()), dim3(climate::BLOCK), 0, as_stream(stream), p, 0);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_climate_step(cge_climate *h, const float *ac_temp, const int8_t *lights, float *obs_out, float *reward_out, uint8_t *terminated_out,
                      uint8_t *truncated_out, float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!ac_temp || !lights || !obs_out || !reward_out || !terminated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_climate_step: null ac_temp/lights/obs/reward/terminated pointer");
+    climate::Params p;
+    if (int st = step_params(h, p, ac_temp && lights && obs_out && reward_out && terminated_out,
+                             "cge_climate_step: null ac_temp/lights/obs/reward/terminated pointer", obs_out, reward_out, terminated_out, truncated_out,
+                             final_obs_out)) return st;
     DeviceGuard g(h->device);
-    climate::Params p = h->params();
-    p.ac = ac_temp; p.lights = lights; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.ac = ac_temp; p.lights = lights;
     hipLaunchKernelGGL(climate::step_kernel<false>, dim3(h->blocks()), dim3(climate::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::climate::step_kernel<false>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_climate_rollout(cge_climate *h, int32_t k_steps, const float *ac_temp, const int8_t *lights, uint64_t action_seed, int64_t t0,
                         float *obs_out, int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                         int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * climate::OBS) || ((ac_temp == nullptr) != (lights == nullptr)))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_climate_rollout: bad k_steps / obs_step_stride / actions");
-    if (k_steps == 0) return CGE_OK;
+    climate::Params p;
+    const int st = rollout_params(h, p, (ac_temp == nullptr) == (lights == nullptr), h->n * climate::OBS,
+                                  "cge_climate_rollout: bad k_steps / obs_step_stride / actions", k_steps, action_seed, t0, obs_out, obs_step_stride,
+                                  reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    climate::Params p = h->params();
-    p.k_steps = k_steps; p.ac = ac_temp; p.lights = lights; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.ac = ac_temp; p.lights = lights;
     hipLaunchKernelGGL(climate::step_kernel<true>, dim3(h->blocks()), dim3(climate::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::climate::step_kernel<true>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(climate, float, 64)
@@ -391,23 +352,10 @@ CGE_DEFINE_FINAL_OBS(climate, float, 64)
 int cge_climate_info(cge_climate *h, int32_t field_id, double *out, void *stream) {
     if (!h || !out || field_id < 0 || field_id > CGE_CLIMATE_INFO_NEEDS_RESET) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(climate::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(climate::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
+    return launched(h);
 }
 
-size_t cge_climate_snapshot_bytes(const cge_climate *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_climate_snapshot_get(cge_climate *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_climate_snapshot_set(cge_climate *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_climate_device_bytes(const cge_climate *h) { return h ? h->device_bytes : 0; }
-int cge_climate_episode_stats(cge_climate *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_climate_last_error(const cge_climate *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_climate_last_kernel(const cge_climate *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_SNAPSHOT(climate)
 
 }  // extern "C"

@@ -1105,8 +1105,24 @@ struct cge_crypto : HandleBase {
         return p;
     }
     unsigned blocks() const { return (unsigned)((n + crypto::BLOCK - 1) / crypto::BLOCK); }
-    void free_all() {
-        (void)hipFree(scal); (void)hipFree(closes); (void)hipFree(ohlv); (void)hipFree(mtP); (void)hipFree(mtL);
+    static int check(const cge_crypto_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_steps <= 0 || c.max_steps > crypto::MAX_STEPS_LIMIT || c.action_type < 0 ||
+                       c.action_type > 1 || !(c.min_price > 0) || !(c.max_price >= c.min_price)
+                   ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        const size_t mb = (size_t)n * MT_STRIDE * sizeof(uint32_t);
+        CGE_HIP(alloc(scal, (size_t)4 * n * sizeof(uint4), true, false));
+        CGE_HIP(alloc(closes, (size_t)crypto::HLEN * n * sizeof(double), true, false));
+        CGE_HIP(alloc(ohlv, (size_t)crypto::HLEN * n * sizeof(float4), true, false));
+        CGE_HIP(alloc(mtP, mb, false, false));
+        CGE_HIP(alloc(mtL, mb, false, false));
+        CGE_HIP(launch_mt_seed(mtP, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        CGE_HIP(launch_mt_seed(mtL, MT_STRIDE, n, nullptr, 0, env0, 1, nullptr));
+        // no reset here: a fresh handle is a freshly constructed env (:244-278) — the MarketSimulator state a
+        // reset leaves behind would otherwise leak into the first real reset(seed=...)
+        hipLaunchKernelGGL(crypto::init_kernel, dim3(grid256(n)), dim3(256), 0, nullptr, scal, n, cfg.initial_balance, 0);
+        return hipGetLastError();
     }
 };
 
@@ -1142,56 +1158,7 @@ void cge_crypto_default_config(cge_crypto_config *c) {
     *c = cge_crypto_config{10000.0, 0.001, 0.0005, 100.0, 100000.0, 0.02, 0.1, 1000, 0, CGE_AUTORESET_NEXT_STEP, 0};
 }
 
-int cge_crypto_create(const cge_crypto_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_crypto **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_steps <= 0 || cfg->max_steps > crypto::MAX_STEPS_LIMIT ||
-        cfg->action_type < 0 || cfg->action_type > 1 || !(cfg->min_price > 0) || !(cfg->max_price >= cfg->min_price))
-        return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_crypto *h = new cge_crypto();
-    h->cfg = *cfg; h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t sb = (size_t)4 * n_envs * sizeof(uint4), cb = (size_t)crypto::HLEN * n_envs * sizeof(double),
-                 ob = (size_t)crypto::HLEN * n_envs * sizeof(float4), mb = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    hipError_t e;
-    if ((e = hipMalloc(&h->scal, sb)) != hipSuccess || (e = hipMalloc(&h->closes, cb)) != hipSuccess ||
-        (e = hipMalloc(&h->ohlv, ob)) != hipSuccess || (e = hipMalloc(&h->mtP, mb)) != hipSuccess ||
-        (e = hipMalloc(&h->mtL, mb)) != hipSuccess || (e = hipMemset(h->scal, 0, sb)) != hipSuccess ||
-        (e = hipMemset(h->closes, 0, cb)) != hipSuccess || (e = hipMemset(h->ohlv, 0, ob)) != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + cb + ob + 2 * mb;
-    e = launch_mt_seed(h->mtP, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) e = launch_mt_seed(h->mtL, MT_STRIDE, n_envs, nullptr, 0, env_index0, 1, nullptr);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(crypto::init_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, nullptr, h->scal, n_envs,
-                           cfg->initial_balance, 0);
-        // no reset here: a fresh handle is a freshly constructed env (:244-278) — the MarketSimulator state a
-        // reset leaves behind would otherwise leak into the first real reset(seed=...)
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_crypto_destroy(cge_crypto *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    h->free_all();
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(crypto)
 
 int cge_crypto_seed(cge_crypto *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
@@ -1200,10 +1167,8 @@ int cge_crypto_seed(cge_crypto *h, const uint64_t *seeds, uint64_t base_seed, vo
         return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_seed: np.random.seed needs seeds < 2**32");
     CGE_TRY(h, launch_mt_seed(h->mtP, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     CGE_TRY(h, launch_mt_seed(h->mtL, MT_STRIDE, h->n, seeds, base_seed, h->env0, 1, as_stream(stream)));
-    hipLaunchKernelGGL(crypto::init_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->scal, h->n,
-                       h->cfg.initial_balance, 1);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(crypto::init_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->scal, h->n, h->cfg.initial_balance, 1);
+    return launched(h);
 }
 
 int cge_crypto_reset(cge_crypto *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -1212,19 +1177,16 @@ int cge_crypto_reset(cge_crypto *h, const uint8_t *mask, float *obs_out, void *s
     crypto::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(crypto::reset_kernel, dim3(h->blocks()), dim3(crypto::BLOCK), 0, as_stream(stream), p);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_crypto_step(cge_crypto *h, const void *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
                     uint8_t *truncated_out, float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_step: null actions/obs/reward/terminated pointer");
+    crypto::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out, "cge_crypto_step: null actions/obs/reward/terminated pointer",
+                             obs_out, reward_out, terminated_out, truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    crypto::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     // the four-wave resident kernel also serves a single step: its waves share the row, feature and market work of the 64 envs
     CGE_TRY(h, launch_resident(h, p, as_stream(stream), true));
     h->phase = (h->phase + 1) % crypto::HLEN;
@@ -1235,14 +1197,12 @@ int cge_crypto_rollout(cge_crypto *h, int32_t k_steps, const void *actions, uint
                        int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                        int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * crypto::OBS))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    crypto::Params p;
+    const int st = rollout_params(h, p, true, h->n * crypto::OBS, "cge_crypto_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    crypto::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     CGE_TRY(h, launch_resident(h, p, as_stream(stream), false));
     h->phase = (h->phase + k_steps) % crypto::HLEN;
     return CGE_OK;
@@ -1254,9 +1214,8 @@ int cge_crypto_info(cge_crypto *h, int32_t field_id, double *out, void *stream) 
     if (!h) return CGE_ERR_INVALID_ARG;
     if (!out || field_id < 0 || field_id > CGE_CRYPTO_INFO_CASH_KIND) return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_info: bad field / null out");
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(crypto::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->scal, h->n, field_id, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(crypto::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->scal, h->n, field_id, out);
+    return launched(h);
 }
 
 size_t cge_crypto_state_bytes(const cge_crypto *h) { return h ? 12 * 4 + 6 * 8 + 2 * MT_N * 4 + crypto::HLEN * 5 * 8 : 0; }
@@ -1343,16 +1302,5 @@ int cge_crypto_set_state(cge_crypto *h, const void *host_buf, void *stream) {
     CGE_TRY(h, hipMemcpy(h->mtL, ml.data(), ml.size() * 4, hipMemcpyHostToDevice));
     return CGE_OK;
 }
-
-size_t cge_crypto_device_bytes(const cge_crypto *h) { return h ? h->device_bytes : 0; }
-int cge_crypto_episode_stats(cge_crypto *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_crypto_last_error(const cge_crypto *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_crypto_last_kernel(const cge_crypto *h) { return h ? h->last_kernel.c_str() : ""; }
 
 }  // extern "C"

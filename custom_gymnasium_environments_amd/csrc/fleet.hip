@@ -723,7 +723,6 @@ struct cge_fleet : HandleBase {
     hipStream_t side = nullptr;          // pipelined rollouts: the dense launches' stream
     hipEvent_t ev_step = nullptr, ev_dense = nullptr;
     static constexpr uint32_t snap_tag = 3u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)fleet::COLS * n * sizeof(uint4)}, {mtP, (size_t)n * MT_STRIDE * 4}, {mtL, (size_t)n * MT_STRIDE * 4}, {work_count, count_bytes()}}; }
     static size_t count_bytes() { return (size_t)3 * fleet::NSUB * fleet::CNT_STRIDE * sizeof(uint32_t); }
     unsigned blocks() const { return (unsigned)((n + fleet::BLOCK - 1) / fleet::BLOCK); }
     int64_t sub_cap() const { return ((int64_t)blocks() + fleet::NSUB - 1) / fleet::NSUB * fleet::BLOCK; }
@@ -737,8 +736,28 @@ struct cge_fleet : HandleBase {
         p.ep_ret = ep_ret; p.ep_len = ep_len; p.done = done_out;
         return p;
     }
-    void free_all() { if (side) (void)hipStreamDestroy(side); if (ev_step) (void)hipEventDestroy(ev_step); if (ev_dense) (void)hipEventDestroy(ev_dense);
-                      (void)hipFree(state); (void)hipFree(mtP); (void)hipFree(mtL); (void)hipFree(work_count); (void)hipFree(work_list); }
+    // the side stream and its events are not arrays: they go with the handle itself (create's failure path and destroy delete it
+    // right after free_all(), with its device still current)
+    ~cge_fleet() { if (side) (void)hipStreamDestroy(side); if (ev_step) (void)hipEventDestroy(ev_step); if (ev_dense) (void)hipEventDestroy(ev_dense); }
+    static int check(const cge_fleet_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 0 || c.max_timesteps > 1023 ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_timesteps == 0) cfg.max_timesteps = 800;
+        const size_t mb = (size_t)n * MT_STRIDE * sizeof(uint32_t);
+        CGE_HIP(alloc(state, (size_t)fleet::COLS * n * sizeof(uint4), true, true));
+        CGE_HIP(alloc(mtP, mb, false, true));
+        CGE_HIP(alloc(mtL, mb, false, true));
+        CGE_HIP(alloc(work_count, count_bytes(), true, true));
+        CGE_HIP(alloc(work_list, list_entries() * sizeof(uint64_t), false, false));     // (not part of a snapshot)
+        CGE_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        CGE_HIP(hipEventCreateWithFlags(&ev_step, hipEventDisableTiming));
+        CGE_HIP(hipEventCreateWithFlags(&ev_dense, hipEventDisableTiming));
+        CGE_HIP(launch_mt_seed(mtP, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        CGE_HIP(launch_mt_seed(mtL, MT_STRIDE, n, nullptr, 0, env0, 1, nullptr));
+        fleet::Params p = params();
+        return launch_all(p, 3, nullptr);
+    }
     // k env steps.  step() (the rows must be final when the call returns): the RNG-free step kernel, then the dense kernel over the
     // envs it listed, on the caller's stream.
     hipError_t launch_steps(fleet::Params &p, int k, hipStream_t s) {
@@ -813,54 +832,7 @@ int cge_fleet_debug_timing(unsigned long long *out, int clear) {
 }
 #endif
 
-int cge_fleet_create(const cge_fleet_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_fleet **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_timesteps < 0 || cfg->max_timesteps > 1023) return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_fleet *h = new cge_fleet();
-    h->cfg = *cfg;
-    if (h->cfg.max_timesteps == 0) h->cfg.max_timesteps = 800;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t sb = (size_t)fleet::COLS * n_envs * sizeof(uint4), mb = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->mtP, mb)) != hipSuccess || (e = hipMalloc(&h->mtL, mb)) != hipSuccess ||
-        (e = hipMalloc(&h->work_count, cge_fleet::count_bytes())) != hipSuccess ||
-        (e = hipMalloc(&h->work_list, h->list_entries() * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMemset(h->work_count, 0, cge_fleet::count_bytes())) != hipSuccess || (e = hipMemset(h->state, 0, sb)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&h->ev_step, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&h->ev_dense, hipEventDisableTiming)) != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + 2 * mb + h->list_entries() * sizeof(uint64_t) + cge_fleet::count_bytes();
-    e = launch_mt_seed(h->mtP, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) e = launch_mt_seed(h->mtL, MT_STRIDE, n_envs, nullptr, 0, env_index0, 1, nullptr);
-    if (e == hipSuccess) {
-        fleet::Params p = h->params();
-        e = h->launch_all(p, 3, nullptr);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_fleet_destroy(cge_fleet *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    h->free_all();
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(fleet)
 
 int cge_fleet_seed(cge_fleet *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
@@ -885,13 +857,12 @@ int cge_fleet_reset(cge_fleet *h, const uint8_t *mask, float *obs_out, void *str
 
 int cge_fleet_step(cge_fleet *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
                    float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out || !truncated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_fleet_step: null actions/obs/reward/terminated/truncated pointer");
+    fleet::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
+                             "cge_fleet_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out, truncated_out,
+                             final_obs_out)) return st;
     DeviceGuard g(h->device);
-    fleet::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     CGE_TRY(h, h->launch_steps(p, 1, as_stream(stream)));
     return CGE_OK;
 }
@@ -900,15 +871,12 @@ int cge_fleet_rollout(cge_fleet *h, int32_t k_steps, const int32_t *actions, uin
                       int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                       int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * fleet::OBS))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_fleet_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    fleet::Params p;
+    const int st = rollout_params(h, p, true, h->n * fleet::OBS, "cge_fleet_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    fleet::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.accumulate = 1;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions; p.accumulate = 1;
     if (h->fin_count) CGE_TRY(h, hipMemsetAsync(h->fin_count, 0, (size_t)((h->n + 63) / 64) * sizeof(int32_t), as_stream(stream)));
     if (reward_sum_out) CGE_TRY(h, hipMemsetAsync(reward_sum_out, 0, (size_t)h->n * sizeof(double), as_stream(stream)));
     if (done_count_out) CGE_TRY(h, hipMemsetAsync(done_count_out, 0, (size_t)h->n * sizeof(int32_t), as_stream(stream)));
@@ -921,29 +889,11 @@ CGE_DEFINE_FINAL_OBS(fleet, float, 64)
 int cge_fleet_info(cge_fleet *h, int32_t field_id, double *out, void *stream) {
     if (!h || !out || field_id < 0 || field_id > CGE_FLEET_INFO_FUEL2) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(fleet::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(fleet::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
+    return launched(h);
 }
 
-size_t cge_fleet_snapshot_bytes(const cge_fleet *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_fleet_snapshot_get(cge_fleet *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_fleet_snapshot_set(cge_fleet *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_fleet_device_bytes(const cge_fleet *h) { return h ? h->device_bytes : 0; }
-int cge_fleet_episode_stats(cge_fleet *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-int cge_fleet_done_mask(cge_fleet *h, uint8_t *done_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->done_out = done_out;
-    return CGE_OK;
-}
-
-const char *cge_fleet_last_error(const cge_fleet *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_fleet_last_kernel(const cge_fleet *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_SNAPSHOT(fleet)
+CGE_DEFINE_DONE_MASK(fleet)
 
 }  // extern "C"

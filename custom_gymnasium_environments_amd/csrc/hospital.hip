@@ -1027,9 +1027,6 @@ struct cge_hospital : HandleBase {
     uint32_t *state = nullptr;
     uint32_t *mt = nullptr, *ring = nullptr;
     static constexpr uint32_t snap_tag = 5u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)hosp::REC_W * 4 * n}, {mt, (size_t)n * MT_STRIDE * 4}, {ring, (size_t)n * hosp::RING * 8}}; }
-    uint32_t snap_extra() const { return 0u; }
-    void set_snap_extra(uint32_t v) { (void)v; }
     hosp::Params params() const {
         hosp::Params p{};
         p.state = state; p.mt = mt; p.ring = ring; p.n = n; p.env0 = env0; p.mode = cfg.autoreset_mode; p.max_steps = cfg.max_episode_length;
@@ -1040,7 +1037,19 @@ struct cge_hospital : HandleBase {
     }
     unsigned blocks() const { return (unsigned)((n + hosp::EPW - 1) / hosp::EPW); }          // reset / seed kernels: one wave per 16 envs, in order
     unsigned step_blocks() const { return (unsigned)(((n + hosp::EPW - 1) / hosp::EPW + 7) / 8 * 8); }
-    void free_all() { (void)hipFree(state); (void)hipFree(mt); (void)hipFree(ring); }
+    static int check(const cge_hospital_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_episode_length < 0 || c.max_episode_length > 2000 ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_episode_length == 0) cfg.max_episode_length = 1440;
+        const size_t N = (size_t)n;
+        CGE_HIP(alloc(state, (size_t)hosp::REC_W * 4 * N, true, true));
+        CGE_HIP(alloc(mt, N * MT_STRIDE * sizeof(uint32_t), false, true));
+        CGE_HIP(alloc(ring, N * hosp::RING * 8, false, true));
+        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        hipLaunchKernelGGL(hosp::reset_kernel, dim3(blocks()), dim3(hosp::BLOCK), 0, nullptr, params(), 2);
+        return hipGetLastError();
+    }
 };
 
 extern "C" {
@@ -1063,60 +1072,14 @@ int cge_hospital_debug_timing(unsigned long long *out, int clear) {
 }
 #endif
 
-int cge_hospital_create(const cge_hospital_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_hospital **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_episode_length < 0 || cfg->max_episode_length > 2000) return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_hospital *h = new cge_hospital();
-    h->cfg = *cfg;
-    if (h->cfg.max_episode_length == 0) h->cfg.max_episode_length = 1440;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t N = (size_t)n_envs;
-    const size_t sb = (size_t)hosp::REC_W * 4 * N, mb = N * MT_STRIDE * sizeof(uint32_t), rb = N * hosp::RING * 8;
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->mt, mb)) != hipSuccess || (e = hipMalloc(&h->ring, rb)) != hipSuccess ||
-        (e = hipMemset(h->state, 0, sb)) != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + mb + rb;
-    e = launch_mt_seed(h->mt, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) {
-        hosp::Params p = h->params();
-        hipLaunchKernelGGL(hosp::reset_kernel, dim3(h->blocks()), dim3(hosp::BLOCK), 0, nullptr, p, 2);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_hospital_destroy(cge_hospital *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    h->free_all();
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(hospital)
 
 int cge_hospital_seed(cge_hospital *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    hosp::Params p = h->params();
-    hipLaunchKernelGGL(hosp::reset_kernel, dim3(h->blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), p, 1);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(hosp::reset_kernel, dim3(h->blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), h->params(), 1);
+    return launched(h);
 }
 
 int cge_hospital_reset(cge_hospital *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -1125,41 +1088,35 @@ int cge_hospital_reset(cge_hospital *h, const uint8_t *mask, float *obs_out, voi
     hosp::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(hosp::reset_kernel, dim3(h->blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), p, 0);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_hospital_step(cge_hospital *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
                       float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out || !truncated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_hospital_step: null actions/obs/reward/terminated/truncated pointer");
+    hosp::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
+                             "cge_hospital_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out,
+                             truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    hosp::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     hipLaunchKernelGGL(hosp::step_kernel<false>, dim3(h->step_blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::hosp::step_kernel<false>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_hospital_rollout(cge_hospital *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                          int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                          int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * hosp::OBS))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_hospital_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    hosp::Params p;
+    const int st = rollout_params(h, p, true, h->n * hosp::OBS, "cge_hospital_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    hosp::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     hipLaunchKernelGGL(hosp::step_kernel<true>, dim3(h->step_blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::hosp::step_kernel<true>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(hospital, float, hosp::EPW)
@@ -1167,29 +1124,11 @@ CGE_DEFINE_FINAL_OBS(hospital, float, hosp::EPW)
 int cge_hospital_info(cge_hospital *h, int32_t field_id, double *out, void *stream) {
     if (!h || !out || field_id < 0 || field_id > CGE_HOSPITAL_INFO_OVERFLOW) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(hosp::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(hosp::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
+    return launched(h);
 }
 
-size_t cge_hospital_snapshot_bytes(const cge_hospital *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_hospital_snapshot_get(cge_hospital *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_hospital_snapshot_set(cge_hospital *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_hospital_device_bytes(const cge_hospital *h) { return h ? h->device_bytes : 0; }
-int cge_hospital_episode_stats(cge_hospital *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-int cge_hospital_done_mask(cge_hospital *h, uint8_t *done_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->done_out = done_out;
-    return CGE_OK;
-}
-
-const char *cge_hospital_last_error(const cge_hospital *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_hospital_last_kernel(const cge_hospital *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_SNAPSHOT(hospital)
+CGE_DEFINE_DONE_MASK(hospital)
 
 }  // extern "C"

@@ -858,9 +858,6 @@ struct cge_manufacturing : HandleBase {
     uint16_t *pm = nullptr, *pnext = nullptr, *pts = nullptr, *tid = nullptr;
     double *tq = nullptr;
     static constexpr uint32_t snap_tag = 4u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)mfg::COLS * n * sizeof(uint4)}, {pq, (size_t)mfg::CAP * n * 8}, {pm, (size_t)mfg::CAP * n * 2}, {pnext, (size_t)mfg::CAP * n * 2}, {pts, (size_t)mfg::CAP * n * 2}, {tq, (size_t)mfg::TROW * n * 8}, {tid, (size_t)mfg::TROW * n * 2}, {comp, (size_t)20 * n * 8}, {hist, (size_t)100 * n * 8}}; }
-    uint32_t snap_extra() const { return 0u; }
-    void set_snap_extra(uint32_t v) { (void)v; }
     mfg::Params params() const {
         mfg::Params p{};
         p.state = state; p.pq = pq; p.pm = pm; p.pnext = pnext; p.pts = pts; p.tq = tq; p.tid = tid; p.comp = comp; p.hist = hist;
@@ -869,7 +866,25 @@ struct cge_manufacturing : HandleBase {
         return p;
     }
     unsigned blocks() const { return (unsigned)((n + mfg::BLOCK - 1) / mfg::BLOCK); }
-    void free_all() { (void)hipFree(state); (void)hipFree(pq); (void)hipFree(pm); (void)hipFree(pnext); (void)hipFree(pts); (void)hipFree(tq); (void)hipFree(tid); (void)hipFree(comp); (void)hipFree(hist); }
+    static int check(const cge_manufacturing_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 0 || c.max_steps > 1500 ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_steps == 0) cfg.max_steps = 1500;
+        const size_t N = (size_t)n;
+        CGE_HIP(alloc(state, (size_t)mfg::COLS * N * sizeof(uint4), true, true));
+        CGE_HIP(alloc(pq, (size_t)mfg::CAP * N * 8, false, true));
+        CGE_HIP(alloc(pm, (size_t)mfg::CAP * N * 2, false, true));
+        CGE_HIP(alloc(pnext, (size_t)mfg::CAP * N * 2, false, true));
+        CGE_HIP(alloc(pts, (size_t)mfg::CAP * N * 2, false, true));
+        CGE_HIP(alloc(tq, (size_t)mfg::TROW * N * 8, false, true));
+        CGE_HIP(alloc(tid, (size_t)mfg::TROW * N * 2, false, true));
+        CGE_HIP(alloc(comp, 20 * N * 8, false, true));
+        CGE_HIP(alloc(hist, 100 * N * 8, false, true));
+        // default generators: PCG64(SeedSequence(env_index0 + i)); no reset
+        hipLaunchKernelGGL(mfg::reset_kernel, dim3(blocks()), dim3(mfg::BLOCK), 0, nullptr, params(), 2);
+        return hipGetLastError();
+    }
 };
 
 extern "C" {
@@ -892,52 +907,7 @@ int cge_manufacturing_debug_timing(unsigned long long *out, int clear) {
 }
 #endif
 
-int cge_manufacturing_create(const cge_manufacturing_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_manufacturing **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_steps < 0 || cfg->max_steps > 1500) return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_manufacturing *h = new cge_manufacturing();
-    h->cfg = *cfg;
-    if (h->cfg.max_steps == 0) h->cfg.max_steps = 1500;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t N = (size_t)n_envs;
-    const size_t sb = (size_t)mfg::COLS * N * sizeof(uint4), qb = (size_t)mfg::CAP * N * 8, mb = (size_t)mfg::CAP * N * 2, cb = 20 * N * 8, hb = 100 * N * 8;
-    const size_t tqb = (size_t)mfg::TROW * N * 8;
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->pq, qb)) != hipSuccess || (e = hipMalloc(&h->pm, mb)) != hipSuccess ||
-        (e = hipMalloc(&h->pnext, mb)) != hipSuccess || (e = hipMalloc(&h->pts, mb)) != hipSuccess ||
-        (e = hipMalloc(&h->tq, tqb)) != hipSuccess || (e = hipMalloc(&h->tid, (size_t)mfg::TROW * N * 2)) != hipSuccess ||
-        (e = hipMalloc(&h->comp, cb)) != hipSuccess || (e = hipMalloc(&h->hist, hb)) != hipSuccess ||
-        (e = hipMemset(h->state, 0, sb)) != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + qb + 3 * mb + tqb + (size_t)mfg::TROW * N * 2 + cb + hb;
-    mfg::Params p = h->params();                               // default generators: PCG64(SeedSequence(env_index0 + i)); no reset
-    hipLaunchKernelGGL(mfg::reset_kernel, dim3(h->blocks()), dim3(mfg::BLOCK), 0, nullptr, p, 2);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        h->free_all();
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_manufacturing_destroy(cge_manufacturing *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    h->free_all();
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(manufacturing)
 
 int cge_manufacturing_seed(cge_manufacturing *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
@@ -945,8 +915,7 @@ int cge_manufacturing_seed(cge_manufacturing *h, const uint64_t *seeds, uint64_t
     mfg::Params p = h->params();
     p.seeds = seeds; p.base_seed = base_seed;
     hipLaunchKernelGGL(mfg::reset_kernel, dim3(h->blocks()), dim3(mfg::BLOCK), 0, as_stream(stream), p, 1);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_manufacturing_reset(cge_manufacturing *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -955,41 +924,35 @@ int cge_manufacturing_reset(cge_manufacturing *h, const uint8_t *mask, float *ob
     mfg::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(mfg::reset_kernel, dim3(h->blocks()), dim3(mfg::BLOCK), 0, as_stream(stream), p, 0);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_manufacturing_step(cge_manufacturing *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
                            uint8_t *truncated_out, float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out || !truncated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_manufacturing_step: null actions/obs/reward/terminated/truncated pointer");
+    mfg::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
+                             "cge_manufacturing_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out,
+                             truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    mfg::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     hipLaunchKernelGGL(mfg::step_kernel<false>, dim3(h->blocks()), dim3(mfg::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::mfg::step_kernel<false>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_manufacturing_rollout(cge_manufacturing *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                               int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                               int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * mfg::OBS))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_manufacturing_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    mfg::Params p;
+    const int st = rollout_params(h, p, true, h->n * mfg::OBS, "cge_manufacturing_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    mfg::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     hipLaunchKernelGGL(mfg::step_kernel<true>, dim3(h->blocks()), dim3(mfg::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::mfg::step_kernel<true>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(manufacturing, float, 64)
@@ -997,29 +960,11 @@ CGE_DEFINE_FINAL_OBS(manufacturing, float, 64)
 int cge_manufacturing_info(cge_manufacturing *h, int32_t field_id, double *out, void *stream) {
     if (!h || !out || field_id < 0 || field_id > CGE_MANUFACTURING_INFO_COMPLETED_TYPE0 + 5) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(mfg::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(mfg::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, out);
+    return launched(h);
 }
 
-size_t cge_manufacturing_snapshot_bytes(const cge_manufacturing *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_manufacturing_snapshot_get(cge_manufacturing *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_manufacturing_snapshot_set(cge_manufacturing *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_manufacturing_device_bytes(const cge_manufacturing *h) { return h ? h->device_bytes : 0; }
-int cge_manufacturing_episode_stats(cge_manufacturing *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-int cge_manufacturing_done_mask(cge_manufacturing *h, uint8_t *done_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->done_out = done_out;
-    return CGE_OK;
-}
-
-const char *cge_manufacturing_last_error(const cge_manufacturing *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_manufacturing_last_kernel(const cge_manufacturing *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_SNAPSHOT(manufacturing)
+CGE_DEFINE_DONE_MASK(manufacturing)
 
 }  // extern "C"

@@ -450,9 +450,6 @@ struct cge_parking : HandleBase {
     uint4 *state = nullptr;
     uint32_t *mt = nullptr;
     static constexpr uint32_t snap_tag = 1u;
-    std::vector<std::pair<void *, size_t>> blobs() const { return {{state, (size_t)parking::COLS * n * sizeof(uint4)}, {mt, (size_t)n * MT_STRIDE * 4}}; }
-    uint32_t snap_extra() const { return 0u; }
-    void set_snap_extra(uint32_t v) { (void)v; }
     parking::Params params() const {
         parking::Params p{};
         p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.mode = cfg.autoreset_mode; p.max_steps = cfg.max_steps;
@@ -460,62 +457,29 @@ struct cge_parking : HandleBase {
         return p;
     }
     unsigned blocks() const { return (unsigned)((n + parking::BLOCK - 1) / parking::BLOCK); }
+    static int check(const cge_parking_config &c) {
+        return bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 0 || c.max_steps > 60000 ? CGE_ERR_INVALID_ARG : CGE_OK;
+    }
+    hipError_t init() {
+        if (cfg.max_steps == 0) cfg.max_steps = 1440;
+        CGE_HIP(alloc(state, (size_t)parking::COLS * n * sizeof(uint4), true, true));
+        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
+        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        hipLaunchKernelGGL(parking::reset_kernel, dim3(blocks()), dim3(parking::BLOCK), 0, nullptr, params(), 1, 0);
+        return hipGetLastError();
+    }
 };
 
 extern "C" {
 
-int cge_parking_create(const cge_parking_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_parking **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_steps < 0 || cfg->max_steps > 60000) return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_parking *h = new cge_parking();
-    h->cfg = *cfg;
-    if (h->cfg.max_steps == 0) h->cfg.max_steps = 1440;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t sb = (size_t)parking::COLS * n_envs * sizeof(uint4), mb = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->mt, mb)) != hipSuccess || (e = hipMemset(h->state, 0, sb)) != hipSuccess) {
-        (void)hipFree(h->state); (void)hipFree(h->mt);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + mb;
-    e = launch_mt_seed(h->mt, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) {
-        parking::Params p = h->params();
-        hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, nullptr, p, 1, 0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(h->state); (void)hipFree(h->mt);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_parking_destroy(cge_parking *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(h->state); (void)hipFree(h->mt);
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(parking)
 
 int cge_parking_seed(cge_parking *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    parking::Params p = h->params();
-    hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p, 0, 1);   // rewind cursors
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), h->params(), 0, 1);   // rewind cursors
+    return launched(h);
 }
 
 int cge_parking_reset(cge_parking *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -524,41 +488,34 @@ int cge_parking_reset(cge_parking *h, const uint8_t *mask, float *obs_out, void 
     parking::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
     hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p, 0, 0);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_parking_step(cge_parking *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
                      uint8_t *truncated_out, float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_parking_step: null actions/obs/reward/terminated pointer");
+    parking::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out, "cge_parking_step: null actions/obs/reward/terminated pointer",
+                             obs_out, reward_out, terminated_out, truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    parking::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     hipLaunchKernelGGL(parking::step_kernel<false>, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::parking::step_kernel<false>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_parking_rollout(cge_parking *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                         int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                         int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * parking::OBS))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_parking_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    parking::Params p;
+    const int st = rollout_params(h, p, true, h->n * parking::OBS, "cge_parking_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    parking::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     hipLaunchKernelGGL(parking::step_kernel<true>, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::parking::step_kernel<true>";
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(parking, float, 64)
@@ -568,33 +525,17 @@ int cge_parking_info(cge_parking *h, int32_t field_id, int32_t index, int32_t *o
     if (!out || field_id < 0 || field_id > CGE_PARKING_INFO_NEEDS_RESET || index < 0 || index > 2)
         return h->fail(CGE_ERR_INVALID_ARG, "cge_parking_info: bad field / index / null out");
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(parking::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id,
-                       index, out, (double *)nullptr);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(parking::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, index, out, (double *)nullptr);
+    return launched(h);
 }
 
 int cge_parking_info64(cge_parking *h, int32_t field_id, double *out, void *stream) {
     if (!h || !out || field_id < 0 || field_id > 1) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(parking::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, 0,
-                       (int32_t *)nullptr, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(parking::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, field_id, 0, (int32_t *)nullptr, out);
+    return launched(h);
 }
 
-size_t cge_parking_snapshot_bytes(const cge_parking *h) { return h ? snapshot_bytes(h) : 0; }
-int cge_parking_snapshot_get(cge_parking *h, void *host_buf, void *stream) { return snapshot_get(h, host_buf, as_stream(stream)); }
-int cge_parking_snapshot_set(cge_parking *h, const void *host_buf, void *stream) { return snapshot_set(h, host_buf, as_stream(stream)); }
-size_t cge_parking_device_bytes(const cge_parking *h) { return h ? h->device_bytes : 0; }
-int cge_parking_episode_stats(cge_parking *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_parking_last_error(const cge_parking *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_parking_last_kernel(const cge_parking *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_SNAPSHOT(parking)
 
 }  // extern "C"

@@ -1130,6 +1130,24 @@ struct cge_snake : HandleBase {
         p.ep_ret = ep_ret; p.ep_len = ep_len;
         return p;
     }
+    // cfg.max_steps == 0: the reference's default (snake_env.py:47)
+    static int check(const cge_snake_config &c) {
+        if (bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 0 || c.max_steps > 65535) return CGE_ERR_INVALID_ARG;
+        snake::Ops o;
+        return snake::ops_for(c.grid_size, o) && (c.max_steps ? c.max_steps : 1000) <= o.max_steps_limit ? CGE_OK : CGE_ERR_UNSUPPORTED;
+    }
+    hipError_t init() {
+        if (cfg.max_steps == 0) cfg.max_steps = 1000;
+        snake::ops_for(cfg.grid_size, ops);
+        CGE_HIP(alloc(state, (size_t)ops.cols * n * sizeof(uint4), true, false));
+        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, false));
+        CGE_HIP(alloc(dq, (size_t)ops.dq_cols * n * sizeof(uint4), true, false));
+        CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
+        // default streams: random.seed(env_index0 + i); default state: reset() so a handle is always steppable
+        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
+        ops.reset(params(), nullptr);
+        return hipGetLastError();
+    }
 };
 
 extern "C" {
@@ -1140,74 +1158,14 @@ uint32_t cge_hash_action(uint64_t a_seed, uint64_t env, uint64_t t, uint32_t n, 
     return hash_action_from_key(hash_env_key(a_seed, env), t, n, j);
 }
 
-int cge_snake_create(const cge_snake_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_snake **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_steps < 0 || cfg->max_steps > 65535)
-        return CGE_ERR_INVALID_ARG;
-    snake::Ops ops;
-    if (!snake::ops_for(cfg->grid_size, ops)) return CGE_ERR_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_snake *h = new cge_snake();
-    h->cfg = *cfg;
-    if (h->cfg.max_steps == 0) h->cfg.max_steps = 1000;   // snake_env.py:47
-    if (h->cfg.max_steps > ops.max_steps_limit) { delete h; return CGE_ERR_UNSUPPORTED; }
-    h->ops = ops;
-    h->n = n_envs; h->env0 = env_index0; h->device = device;
-    DeviceGuard g(device);
-    const size_t state_bytes = (size_t)ops.cols * n_envs * sizeof(uint4);
-    const size_t mt_bytes = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    const size_t dq_bytes = (size_t)ops.dq_cols * n_envs * sizeof(uint4);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, state_bytes)) != hipSuccess || (e = hipMalloc(&h->mt, mt_bytes)) != hipSuccess ||
-        (e = hipMalloc(&h->dq, dq_bytes)) != hipSuccess || (e = hipMalloc(&h->err, sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(h->state, 0, state_bytes)) != hipSuccess || (e = hipMemset(h->dq, 0, dq_bytes)) != hipSuccess ||
-        (e = hipMemset(h->err, 0, sizeof(unsigned long long))) != hipSuccess) {
-        if (h->state) (void)hipFree(h->state);
-        if (h->mt) (void)hipFree(h->mt);
-        if (h->dq) (void)hipFree(h->dq);
-        if (h->err) (void)hipFree(h->err);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = state_bytes + mt_bytes + dq_bytes + sizeof(unsigned long long);
-    // default streams: random.seed(env_index0 + i); default state: reset() so a handle is always steppable
-    e = launch_mt_seed(h->mt, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) {
-        snake::Params p = h->params();
-        h->ops.reset(p, nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(h->state); (void)hipFree(h->mt); (void)hipFree(h->dq); (void)hipFree(h->err);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_snake_destroy(cge_snake *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(h->state);
-    (void)hipFree(h->mt);
-    (void)hipFree(h->dq);
-    (void)hipFree(h->err);
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(snake)
 
 int cge_snake_seed(cge_snake *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     h->ops.rewind(h->state, h->n, as_stream(stream));   // stream cursors back to word 0
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_snake_reset(cge_snake *h, const uint8_t *mask, int8_t *obs_out, void *stream) {
@@ -1217,39 +1175,31 @@ int cge_snake_reset(cge_snake *h, const uint8_t *mask, int8_t *obs_out, void *st
     p.mask = mask;
     p.obs = obs_out;
     h->ops.reset(p, as_stream(stream));
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_snake_step(cge_snake *h, const int32_t *actions, int8_t *obs_out, float *reward_out, uint8_t *terminated_out,
                    uint8_t *truncated_out, int8_t *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_step: null actions/obs/reward/terminated pointer");
+    snake::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out, "cge_snake_step: null actions/obs/reward/terminated pointer",
+                             obs_out, reward_out, terminated_out, truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    snake::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out;
-    p.terminated = terminated_out; p.truncated = truncated_out; p.final_obs = final_obs_out;
+    p.actions = actions;
     h->ops.step(p, as_stream(stream), &h->last_kernel);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_snake_rollout(cge_snake *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0,
                       int8_t *obs_out, int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out,
                       float *reward_sum_out, int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * h->ops.cells) ||
-        ((obs_step_stride & 3) && h->ops.cells % 4 == 0))          // (odd grids: a step's N*G*G bytes need not be a multiple of 4)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    snake::Params p;
+    const bool aligned = !((obs_step_stride & 3) && h->ops.cells % 4 == 0);   // (odd grids: a step's N*G*G bytes need not be a multiple of 4)
+    const int st = rollout_params(h, p, aligned, h->n * h->ops.cells, "cge_snake_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    snake::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0;
-    p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out;
-    p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     // Rings that hold less than one placement round are topped up before the launch's first step; everything else is left to
     // the in-loop refill (wave-convergent, ~0.25 / 64 per env-step).  Measured on 1M envs, us per step at k = 20 / 40 / 100 / 200
     // (gpurun_out/r3_ab_topup.txt, one box): threshold 8-16: 26.5-27.8 / 25.2-26.3 / 24.7-25.4 / 23.4-24.8; 32: 28.5-29.3 / 26.9-27.7 /
@@ -1260,8 +1210,7 @@ int cge_snake_rollout(cge_snake *h, int32_t k_steps, const int32_t *actions, uin
     if (const char *ev = getenv("CGE_SNAKE_TOPUP")) p.dq_topup = (uint32_t)atoi(ev);
 #endif
     h->ops.rollout(p, as_stream(stream), &h->last_kernel);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(snake, int8_t, 64)
@@ -1272,8 +1221,7 @@ int cge_snake_info(cge_snake *h, int32_t field_id, int32_t *out, void *stream) {
         return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_info: bad field id / null out");
     DeviceGuard g(h->device);
     h->ops.info(h->state, h->n, field_id, out, as_stream(stream));
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_snake_render_rgb(cge_snake *h, uint8_t *rgb_out, void *stream) {
@@ -1281,8 +1229,7 @@ int cge_snake_render_rgb(cge_snake *h, uint8_t *rgb_out, void *stream) {
     if (!rgb_out || (reinterpret_cast<uintptr_t>(rgb_out) & 3u)) return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_render_rgb: null or unaligned rgb_out");
     DeviceGuard g(h->device);
     h->ops.render(h->state, h->n, reinterpret_cast<uint32_t *>(rgb_out), as_stream(stream));
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 size_t cge_snake_state_bytes(const cge_snake *h) {
@@ -1371,26 +1318,6 @@ int cge_snake_set_state(cge_snake *h, const void *host_buf, void *stream) {
     return CGE_OK;
 }
 
-int64_t cge_snake_error_count(cge_snake *h, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    unsigned long long v = 0;
-    if (hipStreamSynchronize(as_stream(stream)) != hipSuccess) return CGE_ERR_HIP;
-    if (hipMemcpy(&v, h->err, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return CGE_ERR_HIP;
-    if (v && hipMemset(h->err, 0, sizeof v) != hipSuccess) return CGE_ERR_HIP;
-    return (int64_t)v;
-}
-
-size_t cge_snake_device_bytes(const cge_snake *h) { return h ? h->device_bytes : 0; }
-
-int cge_snake_episode_stats(cge_snake *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_snake_last_error(const cge_snake *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_snake_last_kernel(const cge_snake *h) { return h ? h->last_kernel.c_str() : ""; }
+CGE_DEFINE_ERROR_COUNT(snake)
 
 }  // extern "C"

@@ -928,6 +928,29 @@ struct cge_traffic : HandleBase {
         p.ep_ret = ep_ret; p.ep_len = ep_len;
         return p;
     }
+    // environment.py:79: num_intersections = min(num_intersections, rows * cols)
+    static int clamp_ni(const cge_traffic_config &c) { return c.num_intersections < c.grid_rows * c.grid_cols ? c.num_intersections : c.grid_rows * c.grid_cols; }
+    static int check(const cge_traffic_config &c) {
+        if (c.grid_rows < 1 || c.grid_cols < 1 || c.grid_rows > 64 || c.grid_cols > 64 || c.num_intersections < 1) return CGE_ERR_INVALID_ARG;
+        // 2..16: route_length = randint(2, min(5, NI)) raises for a single intersection (utils.py:181), and an env is spread over
+        // 16 (slot, lane) places
+        if (clamp_ni(c) < 2 || clamp_ni(c) > traffic::MAXNI) return CGE_ERR_UNSUPPORTED;
+        // queue word: len:7 dest:7 wait:18; timestep 16 bits; passed 24 bits
+        if (bad_autoreset_mode(c.autoreset_mode) || c.max_vehicles < 0 || c.max_vehicles > 127 || c.max_steps <= 0 || c.max_steps > 65535 ||
+            (int64_t)c.max_vehicles * c.max_steps > 262143 || !(c.spawn_rate >= 0.0))
+            return CGE_ERR_INVALID_ARG;
+        return CGE_OK;
+    }
+    hipError_t init() {
+        cfg.num_intersections = ni = clamp_ni(cfg);
+        recw = traffic::rec_words(ni); obsw = 14 * ni + 4; ipl = (ni + traffic::L - 1) / traffic::L;
+        const bool own = ni == 4 || ni == 9 || ni == 16;
+        snprintf(step_name, sizeof step_name, "cge::traffic::step_kernel<%d, %d, false>", own ? ni : 0, ipl);
+        snprintf(rollout_name, sizeof rollout_name, "cge::traffic::step_kernel<%d, %d, true>", own ? ni : 0, ipl);
+        CGE_HIP(alloc(state, (size_t)recw * 4 * n, true, false));      // all-zero state == a freshly reset env
+        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, false));
+        return launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr);
+    }
     void launch(const traffic::Params &p, bool rollout, hipStream_t s) const {
         switch (ni) {                                      // the layouts the reference's scripts build get their own instance
             case 4: traffic::launch_step<4, 1>(p, rollout, s); return;       // simple_test.py:71-76
@@ -995,65 +1018,14 @@ void cge_traffic_default_config(cge_traffic_config *c) {
     if (c) *c = cge_traffic_config{5, 5, 9, 50, 0.3, 1000, CGE_AUTORESET_NEXT_STEP};
 }
 
-int cge_traffic_create(const cge_traffic_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_traffic **out) {
-    if (!cfg || !out || n_envs <= 0 || env_index0 < 0) return CGE_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (cfg->grid_rows < 1 || cfg->grid_cols < 1 || cfg->grid_rows > 64 || cfg->grid_cols > 64 || cfg->num_intersections < 1)
-        return CGE_ERR_INVALID_ARG;
-    // environment.py:79: num_intersections = min(num_intersections, rows * cols).  2..16: route_length = randint(2, min(5, NI)) raises
-    // for a single intersection (utils.py:181), and an env is spread over 16 (slot, lane) places
-    const int cells = cfg->grid_rows * cfg->grid_cols;
-    const int ni = cfg->num_intersections < cells ? cfg->num_intersections : cells;
-    if (ni < 2 || ni > traffic::MAXNI) return CGE_ERR_UNSUPPORTED;
-    // queue word: len:7 dest:7 wait:18; timestep 16 bits; passed 24 bits
-    if (cfg->autoreset_mode < 0 || cfg->autoreset_mode > 2 || cfg->max_vehicles < 0 || cfg->max_vehicles > 127 || cfg->max_steps <= 0 ||
-        cfg->max_steps > 65535 || (int64_t)cfg->max_vehicles * cfg->max_steps > 262143 || !(cfg->spawn_rate >= 0.0))
-        return CGE_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return CGE_ERR_NO_DEVICE;
-    cge_traffic *h = new cge_traffic();
-    h->cfg = *cfg; h->cfg.num_intersections = ni; h->n = n_envs; h->env0 = env_index0; h->device = device;
-    h->ni = ni; h->recw = traffic::rec_words(ni); h->obsw = 14 * ni + 4; h->ipl = (ni + traffic::L - 1) / traffic::L;
-    const bool own = ni == 4 || ni == 9 || ni == 16;
-    snprintf(h->step_name, sizeof h->step_name, "cge::traffic::step_kernel<%d, %d, false>", own ? ni : 0, h->ipl);
-    snprintf(h->rollout_name, sizeof h->rollout_name, "cge::traffic::step_kernel<%d, %d, true>", own ? ni : 0, h->ipl);
-    DeviceGuard g(device);
-    const size_t sb = (size_t)h->recw * 4 * n_envs, mb = (size_t)n_envs * MT_STRIDE * sizeof(uint32_t);
-    hipError_t e;
-    if ((e = hipMalloc(&h->state, sb)) != hipSuccess || (e = hipMalloc(&h->mt, mb)) != hipSuccess ||
-        (e = hipMemset(h->state, 0, sb)) != hipSuccess) {     // all-zero state == a freshly reset env
-        (void)hipFree(h->state); (void)hipFree(h->mt);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    h->device_bytes = sb + mb;
-    e = launch_mt_seed(h->mt, MT_STRIDE, n_envs, nullptr, 0, env_index0, 0, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(h->state); (void)hipFree(h->mt);
-        delete h;
-        return CGE_ERR_HIP;
-    }
-    *out = h;
-    return CGE_OK;
-}
-
-int cge_traffic_destroy(cge_traffic *h) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(h->state); (void)hipFree(h->mt);
-    delete h;
-    return CGE_OK;
-}
+CGE_DEFINE_LIFECYCLE(traffic)
 
 int cge_traffic_seed(cge_traffic *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    hipLaunchKernelGGL(traffic::rewind_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(traffic::rewind_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw);
+    return launched(h);
 }
 
 int cge_traffic_reset(cge_traffic *h, const uint8_t *mask, float *obs_out, void *stream) {
@@ -1061,42 +1033,35 @@ int cge_traffic_reset(cge_traffic *h, const uint8_t *mask, float *obs_out, void 
     DeviceGuard g(h->device);
     traffic::Params p = h->params();
     p.mask = mask; p.obs = obs_out;
-    hipLaunchKernelGGL(traffic::reset_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), p);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(traffic::reset_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), p);
+    return launched(h);
 }
 
 int cge_traffic_step(cge_traffic *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
                      uint8_t *truncated_out, float *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!actions || !obs_out || !reward_out || !terminated_out)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_traffic_step: null actions/obs/reward/terminated pointer");
+    traffic::Params p;
+    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out, "cge_traffic_step: null actions/obs/reward/terminated pointer",
+                             obs_out, reward_out, terminated_out, truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
-    traffic::Params p = h->params();
-    p.actions = actions; p.obs = obs_out; p.reward = reward_out; p.terminated = terminated_out; p.truncated = truncated_out;
-    p.final_obs = final_obs_out; p.k_steps = 1;
+    p.actions = actions;
     h->launch(p, false, as_stream(stream));
     h->last_kernel = h->step_name;
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 int cge_traffic_rollout(cge_traffic *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                         int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                         int32_t *done_count_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
-    if (k_steps < 0 || obs_step_stride < 0 || (obs_step_stride != 0 && obs_step_stride < h->n * h->obsw))
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_traffic_rollout: bad k_steps / obs_step_stride");
-    if (k_steps == 0) return CGE_OK;
+    traffic::Params p;
+    const int st = rollout_params(h, p, true, h->n * h->obsw, "cge_traffic_rollout: bad k_steps / obs_step_stride", k_steps, action_seed, t0,
+                                  obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out);
+    if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
-    traffic::Params p = h->params();
-    p.k_steps = k_steps; p.actions = actions; p.a_seed = action_seed; p.t0 = t0; p.obs = obs_out; p.obs_step_stride = obs_step_stride;
-    p.reward = reward_traj_out; p.terminated = terminated_traj_out; p.reward_sum = reward_sum_out; p.done_count = done_count_out;
-    p.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+    p.actions = actions;
     h->launch(p, true, as_stream(stream));
     h->last_kernel = h->rollout_name;
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    return launched(h);
 }
 
 CGE_DEFINE_FINAL_OBS(traffic, float, traffic::EPW)
@@ -1107,19 +1072,17 @@ int cge_traffic_info(cge_traffic *h, int32_t field_id, int32_t index, int32_t *o
     if (!out || field_id < 0 || field_id > CGE_TRAFFIC_INFO_NEEDS_RESET || index < 0 || index >= (per_queue ? 4 : 1) * h->ni)
         return h->fail(CGE_ERR_INVALID_ARG, "cge_traffic_info: bad field / index / null out");
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(traffic::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw, h->ni,
-                       field_id, index, out, (double *)nullptr);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(traffic::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw, h->ni, field_id, index,
+                       out, (double *)nullptr);
+    return launched(h);
 }
 
 int cge_traffic_total_reward(cge_traffic *h, double *out, void *stream) {
     if (!h || !out) return CGE_ERR_INVALID_ARG;
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(traffic::info_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw, h->ni,
-                       0, 0, (int32_t *)nullptr, out);
-    CGE_TRY(h, hipGetLastError());
-    return CGE_OK;
+    hipLaunchKernelGGL(traffic::info_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw, h->ni, 0, 0,
+                       (int32_t *)nullptr, out);
+    return launched(h);
 }
 
 size_t cge_traffic_state_bytes(const cge_traffic *h) { return h ? 6 * 4 + 8 + (size_t)16 * h->ni * 4 + MT_N * 4 : 0; }
@@ -1178,16 +1141,5 @@ int cge_traffic_set_state(cge_traffic *h, const void *host_buf, void *stream) {
     CGE_TRY(h, hipMemcpy(h->mt, mt.data(), mt.size() * 4, hipMemcpyHostToDevice));
     return CGE_OK;
 }
-
-size_t cge_traffic_device_bytes(const cge_traffic *h) { return h ? h->device_bytes : 0; }
-int cge_traffic_episode_stats(cge_traffic *h, double *return_out, int32_t *length_out) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    h->ep_ret = return_out; h->ep_len = length_out;
-    return CGE_OK;
-}
-
-const char *cge_traffic_last_error(const cge_traffic *h) { return h ? h->last_error.c_str() : "null handle"; }
-
-const char *cge_traffic_last_kernel(const cge_traffic *h) { return h ? h->last_kernel.c_str() : ""; }
 
 }  // extern "C"

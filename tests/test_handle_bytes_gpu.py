@@ -1,0 +1,64 @@
+"""Every handle's device footprint and snapshot size, as constants: device_bytes(), snapshot_bytes() and the frees all derive from the
+one list of arrays a handle registers when it is created (cge_host.hpp: HandleBase::alloc), so an array that is dropped from it,
+registered twice or given the wrong size shows up here.  n = 200 is no multiple of a wave (64), of a 256-thread block or of fleet's
+sub-list rounding."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+MT = 640 * 4          # one MT19937 stream block: 624 words + 16 mirror words (cge_device.hpp: MT_STRIDE)
+SNAP_HEADER = 32      # cge_host.hpp: SnapHeader
+
+# name -> (ctor kwargs, device bytes per env, device bytes per handle, of those: bytes outside the snapshot; None = no snapshot)
+ENVS = {
+    # state 3 uint4 columns (grid 10: 12 words) + stream block + digit ring 2 uint4 columns; one 8-byte error counter
+    "Snake": (dict(grid_size=10), 3 * 16 + MT + 2 * 16, 8, None),
+    # scalars 4 uint4 + closes 50 doubles + ohlv 50 float4 + two stream blocks
+    "Crypto": (dict(action_type="discrete"), 4 * 16 + 50 * 8 + 50 * 16 + 2 * MT, 0, None),
+    # 9 intersections: record of (8 + 6 * 9 + 3) & ~3 = 64 words + stream block
+    "Traffic": ({}, 64 * 4 + MT, 0, None),
+    # state 18 uint4 columns + stream block
+    "Parking": ({}, 18 * 16 + MT, 0, 0),
+    # state 5 uint4 columns (the PCG64 generator lives in them)
+    "Climate": ({}, 5 * 16, 0, 0),
+    # state 10 uint4 columns + two stream blocks; per handle: 3 lists x 64 sub-lists x 16-dword counter stride, and the work lists
+    # 3 x 64 x sub_cap entries of 8 bytes, sub_cap = ceil(ceil(n / 64) / 64) * 64 = 64 for both n — only the lists stay out of a snapshot
+    "Fleet": ({}, 10 * 16 + 2 * MT, 3 * 64 * 16 * 4 + 3 * 64 * 64 * 8, 3 * 64 * 64 * 8),
+    # state 23 uint4 columns + product table 320 x (double + 3 uint16) + transport table 1920 x (double + uint16) + 20 + 100 doubles
+    "Manufacturing": ({}, 23 * 16 + 320 * (8 + 3 * 2) + 1920 * (8 + 2) + 20 * 8 + 100 * 8, 0, 0),
+    # record of 212 words + stream block + draw ring of 3008 8-byte entries
+    "Hospital": ({}, 212 * 4 + MT + 3008 * 8, 0, 0),
+    # state 3 uint4 columns + stream block; one 8-byte error counter, which a snapshot leaves out
+    "Bus": ({}, 3 * 16 + MT, 8, 8),
+}
+# ... which is, written out (n = 1, n = 200):
+DEVICE_BYTES = {"Snake": (2648, 528008), "Crypto": (6384, 1276800), "Traffic": (2816, 563200), "Parking": (2848, 569600),
+                "Climate": (80, 16000), "Fleet": (115872, 1166592), "Manufacturing": (25008, 5001600), "Hospital": (27472, 5494400),
+                "Bus": (2616, 521608)}
+SNAPSHOT_BYTES = {"Parking": (2880, 569632), "Climate": (112, 16032), "Fleet": (17600, 1068320), "Manufacturing": (25040, 5001632),
+                  "Hospital": (27504, 5494432), "Bus": (2640, 521632)}
+
+
+@pytest.mark.parametrize("n", [1, 200])
+@pytest.mark.parametrize("name", list(ENVS))
+def test_device_and_snapshot_bytes(name, n):
+    import custom_gymnasium_environments_amd as cge
+    kw, per_env, per_handle, not_in_snapshot = ENVS[name]
+    want = DEVICE_BYTES[name][n == 200]
+    assert want == per_env * n + per_handle          # the table above agrees with its own derivation
+    Env = getattr(cge, name + "VectorEnv")
+    env = Env(n, **kw)
+    assert env.device_bytes() == want
+    if not_in_snapshot is None:
+        assert name not in SNAPSHOT_BYTES
+        env.close()
+        return
+    assert SNAPSHOT_BYTES[name][n == 200] == SNAP_HEADER + want - not_in_snapshot
+    env.reset(seed=3)
+    snap = env.snapshot()
+    assert len(snap) == SNAPSHOT_BYTES[name][n == 200]
+    other = Env(n, **kw)                                   # a second handle, never reset or seeded
+    other.restore(snap)
+    assert np.array_equal(other.snapshot(), snap)
+    env.close(); other.close()
