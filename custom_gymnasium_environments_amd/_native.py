@@ -74,161 +74,61 @@ SAMPLER_MAX_K, SAMPLER_MAX_STEPS = 4096, 65535
 
 # name -> (restype, argtypes); also the list tests check against include/cge_amd.h
 _vp, _i32, _i64, _u32, _u64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
+_host_buf = (C.c_int, [_vp, _vp, _vp])                       # (handle, host or device buffer, stream)
+
+# cge_<env>_<name> for every env type; `create` takes the type's own config struct and is added per type below
+_SHARED = {
+    "destroy": (C.c_int, [_vp]),
+    "seed": (C.c_int, [_vp, _vp, _u64, _vp]),
+    "reset": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "device_bytes": (_sz, [_vp]),
+    "episode_stats": (C.c_int, [_vp, _vp, _vp]),
+    "last_error": (C.c_char_p, [_vp]),
+    "last_kernel": (C.c_char_p, [_vp]),
+}
+# what only some types have, by group; a group may replace a shared prototype (climate's two action pointers)
+_EXTRAS = {
+    "final_obs": {"rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]), "final_obs_segment": (_i64, [_vp])},
+    "state": {"state_bytes": (_sz, [_vp]), "get_state": _host_buf, "set_state": _host_buf},
+    "snapshot": {"snapshot_bytes": (_sz, [_vp]), "snapshot_get": _host_buf, "snapshot_set": _host_buf},
+    "done_mask": {"done_mask": (C.c_int, [_vp, _vp])},
+    "info": {"info": (C.c_int, [_vp, _i32, _vp, _vp])},
+    "info_indexed": {"info": (C.c_int, [_vp, _i32, _i32, _vp, _vp])},
+    "info64": {"info64": (C.c_int, [_vp, _i32, _vp, _vp])},
+    "total_reward": {"total_reward": _host_buf},
+    "render_rgb": {"render_rgb": _host_buf},
+    "error_count": {"error_count": (_i64, [_vp, _vp])},
+    "two_actions": {"step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+                    "rollout": (C.c_int, [_vp, _i32, _vp, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp])},
+}
+_ENV_TYPES = {
+    "snake": (SnakeConfig, "final_obs info render_rgb state error_count"),
+    "crypto": (CryptoConfig, "final_obs info state"),
+    "traffic": (TrafficConfig, "final_obs info_indexed total_reward state"),
+    "parking": (ParkingConfig, "final_obs info_indexed info64 snapshot"),
+    "climate": (ClimateConfig, "two_actions final_obs info snapshot"),
+    "fleet": (FleetConfig, "final_obs info snapshot done_mask"),
+    "manufacturing": (ManufacturingConfig, "final_obs info snapshot done_mask"),
+    "hospital": (HospitalConfig, "final_obs info snapshot done_mask"),
+    "bus": (BusConfig, "info_indexed error_count snapshot"),
+}
+_HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
+
+
+def _env_signatures(env, config, extras):
+    sig = dict(_SHARED, create=(C.c_int, [C.POINTER(config), _i64, C.c_int, _i64, C.POINTER(_vp)]))
+    if env in _HAVE_DEFAULT_CONFIG:
+        sig["default_config"] = (None, [C.POINTER(config)])
+    for group in extras.split():
+        sig.update(_EXTRAS[group])
+    return {f"cge_{env}_{name}": proto for name, proto in sig.items()}
+
+
 SIGNATURES = {
     "cge_version": (C.c_char_p, []),
     "cge_hash_action": (_u32, [_u64, _u64, _u64, _u32, _u32]),
-    "cge_snake_create": (C.c_int, [C.POINTER(SnakeConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_snake_destroy": (C.c_int, [_vp]),
-    "cge_snake_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_snake_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_snake_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_snake_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_snake_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_snake_final_obs_segment": (_i64, [_vp]),
-    "cge_snake_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_snake_render_rgb": (C.c_int, [_vp, _vp, _vp]),
-    "cge_snake_state_bytes": (_sz, [_vp]),
-    "cge_snake_get_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_snake_set_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_snake_error_count": (_i64, [_vp, _vp]),
-    "cge_snake_device_bytes": (_sz, [_vp]),
-    "cge_snake_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_snake_last_error": (C.c_char_p, [_vp]),
-    "cge_snake_last_kernel": (C.c_char_p, [_vp]),
-    "cge_crypto_default_config": (None, [C.POINTER(CryptoConfig)]),
-    "cge_crypto_create": (C.c_int, [C.POINTER(CryptoConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_crypto_destroy": (C.c_int, [_vp]),
-    "cge_crypto_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_crypto_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_crypto_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_crypto_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_crypto_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_crypto_final_obs_segment": (_i64, [_vp]),
-    "cge_crypto_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_crypto_state_bytes": (_sz, [_vp]),
-    "cge_crypto_get_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_crypto_set_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_crypto_device_bytes": (_sz, [_vp]),
-    "cge_crypto_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_crypto_last_error": (C.c_char_p, [_vp]),
-    "cge_crypto_last_kernel": (C.c_char_p, [_vp]),
-    "cge_traffic_default_config": (None, [C.POINTER(TrafficConfig)]),
-    "cge_traffic_create": (C.c_int, [C.POINTER(TrafficConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_traffic_destroy": (C.c_int, [_vp]),
-    "cge_traffic_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_traffic_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_traffic_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_traffic_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_traffic_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_traffic_final_obs_segment": (_i64, [_vp]),
-    "cge_traffic_info": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
-    "cge_traffic_total_reward": (C.c_int, [_vp, _vp, _vp]),
-    "cge_traffic_state_bytes": (_sz, [_vp]),
-    "cge_traffic_get_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_traffic_set_state": (C.c_int, [_vp, _vp, _vp]),
-    "cge_traffic_device_bytes": (_sz, [_vp]),
-    "cge_traffic_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_traffic_last_error": (C.c_char_p, [_vp]),
-    "cge_traffic_last_kernel": (C.c_char_p, [_vp]),
-    "cge_parking_create": (C.c_int, [C.POINTER(ParkingConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_parking_destroy": (C.c_int, [_vp]),
-    "cge_parking_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_parking_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_parking_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_parking_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_parking_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_parking_final_obs_segment": (_i64, [_vp]),
-    "cge_parking_info": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
-    "cge_parking_info64": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_parking_snapshot_bytes": (_sz, [_vp]),
-    "cge_parking_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_parking_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_parking_device_bytes": (_sz, [_vp]),
-    "cge_parking_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_parking_last_error": (C.c_char_p, [_vp]),
-    "cge_parking_last_kernel": (C.c_char_p, [_vp]),
-    "cge_climate_create": (C.c_int, [C.POINTER(ClimateConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_climate_destroy": (C.c_int, [_vp]),
-    "cge_climate_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_climate_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_climate_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_climate_rollout": (C.c_int, [_vp, _i32, _vp, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_climate_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_climate_final_obs_segment": (_i64, [_vp]),
-    "cge_climate_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_climate_snapshot_bytes": (_sz, [_vp]),
-    "cge_climate_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_climate_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_climate_device_bytes": (_sz, [_vp]),
-    "cge_climate_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_climate_last_error": (C.c_char_p, [_vp]),
-    "cge_climate_last_kernel": (C.c_char_p, [_vp]),
-    "cge_fleet_create": (C.c_int, [C.POINTER(FleetConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_fleet_destroy": (C.c_int, [_vp]),
-    "cge_fleet_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_fleet_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_fleet_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_fleet_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_fleet_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_fleet_final_obs_segment": (_i64, [_vp]),
-    "cge_fleet_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_fleet_snapshot_bytes": (_sz, [_vp]),
-    "cge_fleet_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_fleet_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_fleet_device_bytes": (_sz, [_vp]),
-    "cge_fleet_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_fleet_done_mask": (C.c_int, [_vp, _vp]),
-    "cge_fleet_last_error": (C.c_char_p, [_vp]),
-    "cge_fleet_last_kernel": (C.c_char_p, [_vp]),
-    "cge_manufacturing_create": (C.c_int, [C.POINTER(ManufacturingConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_manufacturing_destroy": (C.c_int, [_vp]),
-    "cge_manufacturing_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_manufacturing_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_manufacturing_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_manufacturing_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_manufacturing_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_manufacturing_final_obs_segment": (_i64, [_vp]),
-    "cge_manufacturing_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_manufacturing_snapshot_bytes": (_sz, [_vp]),
-    "cge_manufacturing_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_manufacturing_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_manufacturing_device_bytes": (_sz, [_vp]),
-    "cge_manufacturing_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_manufacturing_done_mask": (C.c_int, [_vp, _vp]),
-    "cge_manufacturing_last_error": (C.c_char_p, [_vp]),
-    "cge_manufacturing_last_kernel": (C.c_char_p, [_vp]),
-    "cge_hospital_create": (C.c_int, [C.POINTER(HospitalConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_hospital_destroy": (C.c_int, [_vp]),
-    "cge_hospital_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_hospital_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_hospital_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_hospital_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_hospital_rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
-    "cge_hospital_final_obs_segment": (_i64, [_vp]),
-    "cge_hospital_info": (C.c_int, [_vp, _i32, _vp, _vp]),
-    "cge_hospital_snapshot_bytes": (_sz, [_vp]),
-    "cge_hospital_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_hospital_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_hospital_device_bytes": (_sz, [_vp]),
-    "cge_hospital_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_hospital_done_mask": (C.c_int, [_vp, _vp]),
-    "cge_hospital_last_error": (C.c_char_p, [_vp]),
-    "cge_hospital_last_kernel": (C.c_char_p, [_vp]),
-    "cge_bus_create": (C.c_int, [C.POINTER(BusConfig), _i64, C.c_int, _i64, C.POINTER(_vp)]),
-    "cge_bus_destroy": (C.c_int, [_vp]),
-    "cge_bus_seed": (C.c_int, [_vp, _vp, _u64, _vp]),
-    "cge_bus_reset": (C.c_int, [_vp, _vp, _vp, _vp]),
-    "cge_bus_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cge_bus_rollout": (C.c_int, [_vp, _i32, _vp, _u64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "cge_bus_info": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
-    "cge_bus_error_count": (_i64, [_vp, _vp]),
-    "cge_bus_snapshot_bytes": (_sz, [_vp]),
-    "cge_bus_snapshot_get": (C.c_int, [_vp, _vp, _vp]),
-    "cge_bus_snapshot_set": (C.c_int, [_vp, _vp, _vp]),
-    "cge_bus_device_bytes": (_sz, [_vp]),
-    "cge_bus_episode_stats": (C.c_int, [_vp, _vp, _vp]),
-    "cge_bus_last_error": (C.c_char_p, [_vp]),
-    "cge_bus_last_kernel": (C.c_char_p, [_vp]),
     "cge_pcg64_advance": (C.c_int, [C.POINTER(Pcg64State), _u64, _u64]),
     "cge_sampler_create": (C.c_int, [_i32, _i64, C.POINTER(C.c_double), _i64, _i64, _i64, C.c_int, C.POINTER(_vp)]),
     "cge_sampler_destroy": (C.c_int, [_vp]),
@@ -239,6 +139,8 @@ SIGNATURES = {
     "cge_sampler_last_error": (C.c_char_p, [_vp]),
     "cge_sampler_last_kernel": (C.c_char_p, [_vp]),
 }
+for _env, (_config, _extras) in _ENV_TYPES.items():
+    SIGNATURES.update(_env_signatures(_env, _config, _extras))
 
 _lib = None
 

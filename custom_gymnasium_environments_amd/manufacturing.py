@@ -1,11 +1,9 @@
 """ManufacturingVectorEnv — batched drop-in for SmartManufacturingEnv (smart_manufacturing_env/manufacturing_env.py:69-606)."""
-import ctypes as C
-
 import numpy as np
 
 from . import _native
-from ._spaces import Box, Discrete, MultiDiscrete, batch_space  # noqa: F401
-from .vector_env import FlagsVectorEnv
+from ._spaces import Box, Discrete, MultiDiscrete  # noqa: F401
+from .vector_env import BOTH, DeviceVectorEnv
 
 INFO_FIELDS = {"raw_material": 0, "energy_consumption": 1, "total_reward": 2, "in_system": 3, "completed": 4, "scrapped": 5,
                "product_ids": 6, "history_len": 7, "oee_availability": 8, "oee_performance": 9, "oee_quality": 10,
@@ -14,7 +12,7 @@ INFO_FIELDS = {"raw_material": 0, "energy_consumption": 1, "total_reward": 2, "i
 OBS_DIM = 73
 
 
-class ManufacturingVectorEnv(FlagsVectorEnv):
+class ManufacturingVectorEnv(DeviceVectorEnv):
     """N independent SmartManufacturingEnv instances (5 stations, 6 product types, quality checkpoints, machine breakdowns,
     supply disruptions) stepped by one HIP kernel launch.  Actions `Discrete(25)` (:303-359), obs float32 (73,).  Both
     `terminated` (:555-578) and `truncated` (timestep >= 1500) are reported; auto-reset triggers on either.  `reset(seed=s)`
@@ -22,25 +20,17 @@ class ManufacturingVectorEnv(FlagsVectorEnv):
     continues the stream.  Bit-exact with the reference, including the NumPy pairwise-summed per-type quality means."""
 
     _abi = "cge_manufacturing"
-    _obs_dim = OBS_DIM
-    _action_shape = ()
     INFO_FIELDS = INFO_FIELDS
+    _flags = BOTH
     metadata = {"render_modes": []}
 
     def __init__(self, num_envs, device="cuda:0", autoreset_mode="NextStep", env_index0=0, max_steps=1500, reuse_buffers=False,
                  info_fields=(), record_episode_statistics=False, reference_info=False):
         self._init_common(num_envs, device, autoreset_mode, env_index0, reuse_buffers)
-        self._reference_info = bool(reference_info)
         self.single_action_space = Discrete(25)
         self.single_observation_space = Box(0.0, 500.0, (OBS_DIM,), np.float32)
-        self.action_space = batch_space(self.single_action_space, self.num_envs)
-        self.observation_space = batch_space(self.single_observation_space, self.num_envs)
-        cfg = _native.ManufacturingConfig(int(max_steps), self._mode_code)
-        h = C.c_void_p()
-        _native.check(self._fn("create")(C.byref(cfg), self.num_envs, self._dev_index, self.env_index0, C.byref(h)), what="cge_manufacturing_create")
-        self._h = h
-        self._finish_init(info_fields)
-        self.record_episode_statistics(record_episode_statistics)
+        self._obs_shape = (self.num_envs, OBS_DIM)
+        self._create(_native.ManufacturingConfig(int(max_steps), self._mode_code), info_fields, record_episode_statistics, reference_info)
 
     def reference_info(self):
         """The reference's `info` under ITS keys (manufacturing_env.py:293-299, reset: :184-190): timestep, total_reward,

@@ -6,13 +6,14 @@ built on this module occupy that SyncVectorEnv slot: same attribute surface, sam
 reset()/step() return tuples, but the batch lives in HBM and one step() is one kernel launch.
 Observations/rewards/flags are torch tensors on the env's device (no host sync per step).
 """
+import ctypes as C
 import enum
 
 import numpy as np
 import torch
 
 from . import _native
-from ._spaces import VectorEnvBase
+from ._spaces import VectorEnvBase, batch_space
 
 try:  # pragma: no cover
     from gymnasium.vector import AutoresetMode
@@ -39,10 +40,31 @@ def parse_autoreset_mode(mode):
     raise ValueError(f"unknown autoreset_mode {mode!r}")
 
 
+def _batch(space, n):
+    """batch_space, key by key for a plain dict of spaces (climate's Dict action)."""
+    return {k: batch_space(v, n) for k, v in space.items()} if isinstance(space, dict) else batch_space(space, n)
+
+
+TERMINATED, TRUNCATED, BOTH = "terminated", "truncated", "both"
+
+
 class DeviceVectorEnv(VectorEnvBase):
-    """Base of every batched env: owns the native handle, the device and the output buffers."""
+    """Base of every batched env: owns the native handle, the device and the output buffers, and holds the ONLY reset() / step() /
+    rollout() / info() / get_state() / set_state().  An env type declares what differs through the class attributes below and
+    `_obs_shape` (the shape of one observation buffer, set in __init__), and writes none of them; DESIGN.md §1 "One façade" has the
+    table of variants.  `_flags` names the flag the type raises and with it the tensor that means "done": TERMINATED (`truncated` is
+    NULL for the kernel and one shared all-False tensor for the caller; done = terminated), TRUNCATED (bus: both written,
+    done = truncated) or BOTH (done = the `done_mask` buffer the step kernel fills; a rollout's per-step flags are uint8
+    terminated | truncated << 1 instead of bool)."""
 
     _abi = None  # e.g. "cge_snake"
+    INFO_FIELDS = {}
+    INFO64_FIELDS = {}
+    _obs_dtype = torch.float32
+    _action_shape, _action_dtype, _action_ptrs = (), torch.int32, 1
+    _flags = TERMINATED
+    _reward_sum_dtype = torch.float64
+    _info_dtype, _info_indexed = torch.float64, False
 
     def _init_common(self, num_envs, device, autoreset_mode, env_index0, reuse_buffers):
         if int(num_envs) <= 0:
@@ -66,7 +88,39 @@ class DeviceVectorEnv(VectorEnvBase):
         self._h = None
         self._bufs = {}
         self._ep_ret = self._ep_len = None
+        self._done_ptr = 0
+        self._last_obs = None
         self.closed = False
+
+    def _create(self, cfg, info_fields, record_episode_statistics, reference_info):
+        """The tail of every constructor, after the type has set its spaces and `_obs_shape`: create the native handle, bind the
+        entry points the hot path calls, batch the spaces; `info_fields` is validated first."""
+        known = {**self.INFO_FIELDS, **self.INFO64_FIELDS}
+        for f in info_fields:                                      # before create: a misspelt field allocates nothing
+            if f not in known:
+                raise ValueError(f"unknown info field {f!r}; choose from {sorted(known)}")
+        h = C.c_void_p()
+        status = self._fn("create")(C.byref(cfg), self.num_envs, self._dev_index, self.env_index0, C.byref(h))
+        if status:
+            error = self._create_error(status)
+            if error is not None:
+                raise error
+        _native.check(status, what=f"{self._abi}_create")
+        self._h = h
+        # bound once: step() / reset() / rollout() / info() do no string formatting and no getattr by name
+        self._c_reset, self._c_step, self._c_rollout, self._c_info, self._c_done_mask, self._c_last_error, self._c_seed = (
+            getattr(self._lib, f"{self._abi}_{name}", None) for name in ("reset", "step", "rollout", "info", "done_mask", "last_error", "seed"))
+        self._obs_stride = int(np.prod(self._obs_shape))
+        self._actions_shape = (self.num_envs,) + tuple(self._action_shape)
+        self._reference_info = bool(reference_info)
+        self.action_space = _batch(self.single_action_space, self.num_envs)
+        self.observation_space = _batch(self.single_observation_space, self.num_envs)
+        self.info_fields = tuple(info_fields)
+        self.record_episode_statistics(record_episode_statistics)
+
+    def _create_error(self, status):
+        """The exception a failing create raises instead of the generic NativeLibraryError, or None."""
+        return None
 
     # ------------------------------------------------------------------ native helpers
     def _fn(self, name):
@@ -74,7 +128,7 @@ class DeviceVectorEnv(VectorEnvBase):
 
     def _check(self, status, what):
         if status:                                             # hot path: no lookups or string formatting on success
-            _native.check(status, self._h, self._fn("last_error"), f"{self._abi}_{what}")
+            _native.check(status, self._h, self._c_last_error, f"{self._abi}_{what}")
 
     def _stream(self):
         # the raw handle of torch's current stream on this device (the private getter skips building a Stream object: ~2 us per call
@@ -112,13 +166,13 @@ class DeviceVectorEnv(VectorEnvBase):
         if isinstance(seed, (int, np.integer)):
             if seed < 0:
                 raise ValueError("seed must be non-negative")
-            self._check(self._fn("seed")(self._h, None, int(seed), self._stream()), "seed")
+            self._check(self._c_seed(self._h, None, int(seed), self._stream()), "seed")
             return
         arr = np.asarray(seed)
         if arr.shape != (self.num_envs,) or np.any(arr < 0):
             raise ValueError(f"seed sequence must hold {self.num_envs} non-negative ints")
         t = torch.from_numpy(arr.astype(np.uint64).view(np.int64)).to(self.device)
-        self._check(self._fn("seed")(self._h, t.data_ptr(), 0, self._stream()), "seed")
+        self._check(self._c_seed(self._h, t.data_ptr(), 0, self._stream()), "seed")
         self._keepalive = t
 
     def device_bytes(self):
@@ -140,6 +194,130 @@ class DeviceVectorEnv(VectorEnvBase):
         """Name(s) of the kernel(s) the last step() / rollout() launched, as rocprofv3 prints them ("" before the first call)."""
         raw = self._fn("last_kernel")(self._h)
         return raw.decode() if raw else ""
+
+    # ------------------------------------------------------------------ gymnasium API
+    # hooks; None = the plain case, which the hot path then handles without a call
+    _device_actions = None    # (actions, k=None) -> the tuple of device tensors whose pointers the C call takes (climate: ac_temp, lights)
+    _wrap_obs = None          # an observation buffer -> what the caller sees (bus: its dict of views)
+
+    def reset(self, *, seed=None, options=None):
+        """Reset every env (or those in options['reset_mask']).  Returns (obs, infos)."""
+        self._seed_native(seed)
+        mask = None
+        if options and options.get("reset_mask") is not None:
+            mask = self._as_device(options["reset_mask"], torch.uint8, (self.num_envs,), "reset_mask")
+        obs = self._last_obs = self._out("obs", self._obs_shape, self._obs_dtype)
+        self._check(self._c_reset(self._h, mask.data_ptr() if mask is not None else None, obs.data_ptr(), self._stream()), "reset")
+        return (obs if self._wrap_obs is None else self._wrap_obs(obs)), self._infos()
+
+    def step(self, actions):
+        split = self._device_actions
+        a = self._as_device(actions, self._action_dtype, self._actions_shape, "actions") if split is None else split(actions)
+        obs = self._last_obs = self._out("obs", self._obs_shape, self._obs_dtype)
+        rew = self._out("reward", (self.num_envs,), torch.float32)
+        term = self._out("terminated", (self.num_envs,), torch.bool)
+        same = self._mode_code == _native.AUTORESET_SAME_STEP
+        fin = self._out("final_obs", self._obs_shape, self._obs_dtype) if same else None
+        if self._flags == TERMINATED:
+            # the reference never truncates: one shared all-False tensor, never rewritten (also without reuse_buffers)
+            trunc = self._bufs.get("_truncated")
+            if trunc is None:
+                trunc = self._bufs["_truncated"] = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+            trunc_ptr, done = None, term
+        else:
+            trunc = done = self._out("truncated", (self.num_envs,), torch.bool)
+            trunc_ptr = trunc.data_ptr()
+            if self._flags == BOTH:
+                done = None
+                if same or self._ep_ret is not None:               # terminated | truncated, written by the step kernel itself
+                    done = self._out("done", (self.num_envs,), torch.bool)
+                    if done.data_ptr() != self._done_ptr:
+                        self._done_ptr = done.data_ptr()
+                        self._check(self._c_done_mask(self._h, self._done_ptr), "done_mask")
+                elif self._done_ptr:
+                    self._done_ptr = 0
+                    self._check(self._c_done_mask(self._h, None), "done_mask")
+        fin_ptr = fin.data_ptr() if same else None
+        if split is None:                                          # spelled out, not splatted: ~0.5 us per call on a 10 us step
+            status = self._c_step(self._h, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc_ptr, fin_ptr, self._stream())
+        else:
+            status = self._c_step(self._h, a[0].data_ptr(), a[1].data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc_ptr,
+                                  fin_ptr, self._stream())
+        self._check(status, "step")
+        infos = self._infos()
+        wrap = self._wrap_obs
+        if same:
+            # rows of final_obs are valid where _final_obs is True (gymnasium's SAME_STEP convention)
+            infos["final_obs"] = fin if wrap is None else wrap(fin)
+            infos["_final_obs"] = done
+        return (obs if wrap is None else wrap(obs)), rew, term, trunc, self._episode_infos(infos, done)
+
+    def rollout(self, k_steps, actions=None, action_seed=0, t0=0, trajectory=False, want_obs=True, per_step=False):
+        """k fused step()s queued by one C-ABI call (state stays in registers between steps).  actions: None -> counter-hash
+        random actions (cge_hash_action) or what step() takes with a leading [k].  Returns (obs, reward_sum, done_count) with obs
+        [k, N, ...] if trajectory else the last step's [N, ...] (None with want_obs=False); with per_step=True
+        (obs, reward[k, N], flags[k, N], reward_sum, done_count) — the outputs of k step() calls, where flags is the bool flag the
+        type raises (terminated; bus: truncated) or, for the types that raise both, uint8 terminated | truncated << 1.
+        reward_sum is float64 (snake: float32).  A SAME_STEP trajectory holds the reset observation at a step that ends an episode,
+        as step()'s `obs` does."""
+        k = int(k_steps)
+        a = ()                                                     # the tensors are held until the launch is queued
+        if actions is not None and self._device_actions is None:
+            a = (self._as_device(actions, self._action_dtype, (k,) + self._actions_shape, "actions"),)
+        elif actions is not None:
+            a = self._device_actions(actions, k)
+        a_ptrs = [t.data_ptr() for t in a] or [None] * self._action_ptrs
+        obs, stride = None, 0
+        if want_obs:
+            if trajectory:
+                obs = self._out("traj", (k,) + self._obs_shape, self._obs_dtype)
+                stride = self._obs_stride
+            else:
+                obs = self._out("obs", self._obs_shape, self._obs_dtype)
+        rs = self._out("reward_sum", (self.num_envs,), self._reward_sum_dtype)
+        dc = self._out("done_count", (self.num_envs,), torch.int32)
+        rt = ft = None
+        if per_step:
+            rt = self._out("reward_traj", (k, self.num_envs), torch.float32)
+            ft = self._out("flags_traj", (k, self.num_envs), torch.uint8 if self._flags == BOTH else torch.bool)
+        self._check(self._c_rollout(self._h, k, *a_ptrs, int(action_seed), int(t0), obs.data_ptr() if obs is not None else None, stride,
+                                    rt.data_ptr() if per_step else None, ft.data_ptr() if per_step else None,
+                                    rs.data_ptr(), dc.data_ptr(), self._stream()), "rollout")
+        if obs is not None and self._wrap_obs is not None:
+            obs = self._wrap_obs(obs)
+        return (obs, rt, ft, rs, dc) if per_step else (obs, rs, dc)
+
+    def info(self, field, index=0):
+        """One field of INFO_FIELDS for every env; `index` selects the item of a per-item field where the type has those."""
+        if index and not self._info_indexed:
+            raise TypeError(f"{type(self).__name__}.info() takes no index")
+        out = torch.empty(self.num_envs, dtype=self._info_dtype, device=self.device)
+        at = (int(index),) if self._info_indexed else ()
+        self._check(self._c_info(self._h, self.INFO_FIELDS[field], *at, out.data_ptr(), self._stream()), "info")
+        return out
+
+    def _infos(self):
+        d = {f: self.info(f) for f in self.info_fields}
+        if self._reference_info:
+            d.update(self.reference_info())
+        return d
+
+    def reference_info(self):
+        """The reference's own `info` dict (its keys, its derived expressions) as tensors; subclasses define it."""
+        raise NotImplementedError
+
+    def get_state(self):
+        """Canonical per-env state records, uint8 [N, state_bytes] on the host (snake, crypto, traffic; the others: `snapshot()`)."""
+        buf = np.zeros((self.num_envs, int(self._fn("state_bytes")(self._h))), np.uint8)
+        self._check(self._fn("get_state")(self._h, buf.ctypes.data, self._stream()), "get_state")
+        return buf
+
+    def set_state(self, buf):
+        rec = int(self._fn("state_bytes")(self._h))
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        if buf.shape != (self.num_envs, rec):
+            raise ValueError(f"state buffer must be uint8 {(self.num_envs, rec)}")
+        self._check(self._fn("set_state")(self._h, buf.ctypes.data, self._stream()), "set_state")
 
     # ------------------------------------------------------------------ episode statistics
     def record_episode_statistics(self, enable=True):
@@ -171,8 +349,6 @@ class DeviceVectorEnv(VectorEnvBase):
         return infos
 
     # ------------------------------------------------------------------ terminal observations of fused SAME_STEP rollouts
-    _obs_dtype = torch.float32
-
     def collect_final_obs(self, rows_per_env=4):
         """A SAME_STEP `rollout()` writes the RESET observation of an env that finishes at step t to slot t of its trajectory —
         what `step()` returns as `obs`; the terminal observation, which `step()` hands over as `infos["final_obs"]` (and the
@@ -192,9 +368,6 @@ class DeviceVectorEnv(VectorEnvBase):
         count = torch.zeros(nseg, dtype=torch.int32, device=self.device)
         self._check(self._fn("rollout_final_obs")(self._h, rows.data_ptr(), index.data_ptr(), cap, count.data_ptr()), "rollout_final_obs")
         self._fin = (rows, index, count, cap)
-
-    def _final_obs_begin(self):
-        pass                                     # every rollout call writes the segments' counts itself
 
     def _fin_buffers(self):
         fin = getattr(self, "_fin", None)
@@ -240,94 +413,3 @@ class DeviceVectorEnv(VectorEnvBase):
         if getattr(self, "_h", None):
             self._fn("destroy")(self._h)
             self._h = None
-
-
-class FlagsVectorEnv(DeviceVectorEnv):
-    """Shared façade of the env types whose C ABI has the same shape: int32 actions of a fixed per-env shape, float32
-    observations, both `terminated` and `truncated` reported, float64 info fields (fleet, manufacturing, hospital).
-    A subclass sets `_abi`, `_obs_dim`, `_action_shape`, `INFO_FIELDS`, builds the spaces and creates the native handle."""
-
-    _obs_dim = None
-    _action_shape = ()
-    INFO_FIELDS = {}
-
-    def _finish_init(self, info_fields):
-        self.info_fields = tuple(info_fields)
-        self._done_ptr = 0
-        self._obs_shape = (self.num_envs, self._obs_dim)
-
-    def reset(self, *, seed=None, options=None):
-        self._seed_native(seed)
-        mask = None
-        if options and options.get("reset_mask") is not None:
-            mask = self._as_device(options["reset_mask"], torch.uint8, (self.num_envs,), "reset_mask")
-        obs = self._out("obs", self._obs_shape, torch.float32)
-        self._check(self._fn("reset")(self._h, mask.data_ptr() if mask is not None else None, obs.data_ptr(), self._stream()), "reset")
-        return obs, self._infos()
-
-    def step(self, actions):
-        a = self._as_device(actions, torch.int32, (self.num_envs,) + self._action_shape, "actions")
-        obs = self._out("obs", self._obs_shape, torch.float32)
-        rew = self._out("reward", (self.num_envs,), torch.float32)
-        term = self._out("terminated", (self.num_envs,), torch.bool)
-        trunc = self._out("truncated", (self.num_envs,), torch.bool)
-        same = self._mode_code == _native.AUTORESET_SAME_STEP
-        fin = self._out("final_obs", self._obs_shape, torch.float32) if same else None
-        done = None
-        if same or self._ep_ret is not None:                   # terminated | truncated, written by the step kernel itself
-            done = self._out("done", (self.num_envs,), torch.bool)
-            if done.data_ptr() != self._done_ptr:
-                self._done_ptr = done.data_ptr()
-                self._check(self._fn("done_mask")(self._h, self._done_ptr), "done_mask")
-        elif self._done_ptr:
-            self._done_ptr = 0
-            self._check(self._fn("done_mask")(self._h, None), "done_mask")
-        self._check(self._fn("step")(self._h, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc.data_ptr(),
-                                     fin.data_ptr() if same else None, self._stream()), "step")
-        infos = self._infos()
-        if same:
-            infos["final_obs"] = fin
-            infos["_final_obs"] = done
-        if self._ep_ret is not None:
-            self._episode_infos(infos, done)
-        return obs, rew, term, trunc, infos
-
-    def rollout(self, k_steps, actions=None, action_seed=0, t0=0, trajectory=False, want_obs=True, per_step=False):
-        """k env steps queued by one C-ABI call (actions: None -> counter-hash actions, or int32 [k, N, ...]).  Returns
-        (obs, reward_sum, done_count); with per_step=True (obs, reward[k, N], flags[k, N], reward_sum, done_count) where
-        flags = terminated | truncated << 1 (uint8).  obs is [k, N, obs_dim] if trajectory else the last step's."""
-        k = int(k_steps)
-        a = None if actions is None else self._as_device(actions, torch.int32, (k, self.num_envs) + self._action_shape, "actions")
-        obs, stride = None, 0
-        if want_obs:
-            if trajectory:
-                obs = self._out("traj", (k,) + self._obs_shape, torch.float32)
-                stride = self.num_envs * self._obs_dim
-            else:
-                obs = self._out("obs", self._obs_shape, torch.float32)
-        rs = self._out("reward_sum", (self.num_envs,), torch.float64)
-        dc = self._out("done_count", (self.num_envs,), torch.int32)
-        rt = tt = None
-        if per_step:
-            rt = self._out("reward_traj", (k, self.num_envs), torch.float32)
-            tt = self._out("flags_traj", (k, self.num_envs), torch.uint8)
-        self._check(self._fn("rollout")(self._h, k, a.data_ptr() if a is not None else None, int(action_seed), int(t0),
-                                        obs.data_ptr() if obs is not None else None, stride,
-                                        rt.data_ptr() if per_step else None, tt.data_ptr() if per_step else None,
-                                        rs.data_ptr(), dc.data_ptr(), self._stream()), "rollout")
-        return (obs, rt, tt, rs, dc) if per_step else (obs, rs, dc)
-
-    def info(self, field):
-        out = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
-        self._check(self._fn("info")(self._h, self.INFO_FIELDS[field], out.data_ptr(), self._stream()), "info")
-        return out
-
-    def _infos(self):
-        d = {f: self.info(f) for f in self.info_fields}
-        if getattr(self, "_reference_info", False):
-            d.update(self.reference_info())
-        return d
-
-    def reference_info(self):
-        """The reference's own `info` dict (its keys, its derived expressions) as tensors; subclasses define it."""
-        raise NotImplementedError

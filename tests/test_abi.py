@@ -42,6 +42,33 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_native.SIGNATURES) == _declared()
 
 
+_RESTYPE = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p, "int64_t": ctypes.c_int64,
+            "uint32_t": ctypes.c_uint32, "void": None}
+_SCALAR = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+           "uint64_t": ctypes.c_uint64}
+
+
+def test_binding_table_matches_the_header_prototypes():
+    """Every prototype of include/cge_amd.h against _native.SIGNATURES: the return type, the number of parameters and each
+    parameter's kind (a pointer is c_void_p or a ctypes POINTER, a scalar is the ctypes integer of its width).  A wrong arity
+    in the table is otherwise invisible until a GPU call misbehaves."""
+    from custom_gymnasium_environments_amd import _native
+    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = re.findall(r"^\s*(const char \*|int64_t|uint32_t|size_t|void|int)\s*(cge_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M)
+    assert sorted(name for _, name, _ in protos) == _declared() == sorted(_native.SIGNATURES)
+    for ret, name, args in protos:
+        restype, argtypes = _native.SIGNATURES[name]
+        assert restype is _RESTYPE[ret], (name, ret, restype)
+        params = [] if args.strip() in ("", "void") else [" ".join(p.split()) for p in args.split(",")]
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for p, t in zip(params, argtypes):
+            if "*" in p:
+                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), (name, p, t)
+            else:
+                assert t is _SCALAR[p.rsplit(" ", 1)[0]], (name, p, t)
+
+
 def test_host_only_entry_points_work_without_a_gpu(oracle):
     from custom_gymnasium_environments_amd import _native
     L = _native.lib()
