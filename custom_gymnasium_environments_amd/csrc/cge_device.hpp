@@ -69,8 +69,8 @@ __device__ __forceinline__ void mt_load_run(const uint32_t *__restrict__ src, ui
 //          generation), or — streams advanced by mt_make_ready() below — a multiple of 32 up to 624 + 32, where the part beyond 624
 //          means words [0, pretw - 624) of the NEXT generation
 // Words are twisted in place (incremental form of the reference generator's 624-word batch regeneration; identical output
-// sequence): one at a time exactly when they are consumed (MtStream, MtWindow, the LDS queues), or a 32-word chunk at a time
-// AHEAD of the cursor (mt_make_ready) so that the draws themselves are plain loads and nothing is written back per draw.
+// sequence): one at a time exactly when they are consumed (MtStream, the LdsDraws / LdsBulkDraws fills), or a 32-word chunk at a
+// time AHEAD of the cursor (mt_make_ready, QuadRing) so that the draws themselves are plain loads and nothing is written back per draw.
 __host__ __device__ __forceinline__ uint32_t mt_wrap_ready(uint32_t pretw) { return pretw > (uint32_t)MT_N ? pretw - (uint32_t)MT_N : 0u; }   // the cursor wrapped into the next generation
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
@@ -236,44 +236,9 @@ struct MtWindow {
         const uint32_t y = mt_twist(a[j], a[j + 1], c[j]);
         return (pos + j < pretw) ? a[j] : y;
     }
-    __device__ __forceinline__ uint32_t draw(int j, uint32_t pos, uint32_t pretw) const { return mt_temper(twisted(j, pos, pretw)); }
-    // persist the first `used` words and advance the cursor
-    __device__ __forceinline__ void commit(uint32_t *__restrict__ blk, uint32_t &pos, uint32_t &pretw, uint32_t used) const {
-        if constexpr (RUN) {
-            // the window goes back as one run: consumed words twisted, the others as they were (this lane owns the block)
-            uint32_t v[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) v[j] = ((uint32_t)j < used && pos + j >= pretw) ? mt_twist(a[j], a[j + 1], c[j]) : a[j];
-#pragma unroll
-            for (int q = 0; q + 4 <= W; q += 4) *reinterpret_cast<MtQuad *>(blk + pos + q) = MtQuad{v[q], v[q + 1], v[q + 2], v[q + 3]};
-#pragma unroll
-            for (int q = W - W % 4; q < W; ++q) blk[pos + q] = v[q];
-            if (pos + W > (uint32_t)MT_N || pos < (uint32_t)MT_PAD) {     // the run touched the mirror or the mirrored words: fix the twin
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    const uint32_t k = pos + j;
-                    if (k >= (uint32_t)MT_N) blk[k - MT_N] = v[j];
-                    else if (k < (uint32_t)MT_PAD) blk[MT_N + k] = v[j];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                uint32_t k = pos + j;
-                if ((uint32_t)j < used && k >= pretw) {
-                    const uint32_t y = mt_twist(a[j], a[j + 1], c[j]);
-                    k -= k >= (uint32_t)MT_N ? MT_N : 0;
-                    mt_store(blk, k, y);
-                }
-            }
-        }
-        uint32_t p = pos + used;
-        if (p >= (uint32_t)MT_N) { p -= MT_N; pretw = mt_wrap_ready(pretw); }
-        pos = p;
-    }
 };
 
-// Draw queue for envs whose draw COUNT per step is data dependent (traffic: lights, spawn, routes): the
+// Draw queue for envs whose draw COUNT per step is data dependent (parking: arrivals, customer types; crypto's episode reset): the
 // window's twisted words are parked in the lane's own LDS row, where a per-lane cursor can index them
 // natively (a runtime-indexed register array would go to scratch).  `row` must hold W dwords; give rows an
 // odd stride so the 64 lanes' rows start in different banks.  flush() writes back only consumed words.
@@ -441,7 +406,7 @@ struct LdsDrawsCall {
     uint32_t *row;
     uint32_t *blk;
     uint32_t pos, pretw, cur;
-    uint32_t old0 = 0;                                          // twist-ahead streams: see mt_twist_chunk (kept in the env's record)
+    uint32_t old0 = 0;                                          // unused; dropping it moves crypto's code (profiles/draw_queues_ab.txt)
     bool filled;
 
     __device__ __forceinline__ LdsDrawsCall(uint32_t *lds_row, uint32_t *block, uint32_t pos_, uint32_t pretw_)
@@ -459,15 +424,6 @@ struct LdsDrawsCall {
         d.flush();
         pos = d.pos; pretw = d.pretw; cur = 0; filled = false;
     }
-    __device__ __forceinline__ void fill() {                   // unconditional (re)fill through the same call
-        const uint2 r = refill(row, blk, pos, pretw, cur, filled);
-        pos = r.x; pretw = r.y; cur = 0; filled = true;
-    }
-    // Look-ahead for draw sequences whose word OFFSETS can be computed up front: has(n) says the next n words are parked,
-    // peek(j) is the tempered word j places ahead of the cursor (any order, as often as needed), skip(n) consumes n words.
-    __device__ __forceinline__ bool has(uint32_t n) const { return filled && cur + n <= (uint32_t)W; }
-    __device__ __forceinline__ uint32_t peek(uint32_t j) const { return mt_temper(row[cur + j]); }
-    __device__ __forceinline__ void skip(uint32_t n) { cur += n; }
     __device__ __forceinline__ uint32_t next() {
         if (!filled || cur == (uint32_t)W) {
             const uint2 r = refill(row, blk, pos, pretw, cur, filled);
@@ -484,40 +440,6 @@ struct LdsDrawsCall {
         if (__ballot(shortfall) != 0ull) {
             const uint2 r = refill(row, blk, pos, pretw, cur, filled);
             pos = r.x; pretw = r.y; cur = 0; filled = true;
-        }
-    }
-    // The same two entry points for streams that twist ahead (the env's record keeps a ready mark, mt_ready_encode): the W words
-    // after the cursor are made ready first — whole 32-word chunks, wave-convergent — so the fill is plain loads and the flush
-    // writes nothing.  `active`: lanes that own a live env.  Call with all lanes of the wave.
-    __device__ __forceinline__ void fill_ahead(bool active) {
-        LdsDraws<W> d(row, blk, pos, pretw);
-        d.cur = cur; d.filled = filled;
-        d.flush();
-        mt_make_ready(blk, d.pos, d.pretw, (uint32_t)W, active, &old0);
-        d.fill_ready();
-        pos = d.pos; pretw = d.pretw; cur = 0; filled = true;
-    }
-    __device__ __forceinline__ void ensure_ahead(uint32_t need, bool active) {
-        const bool shortfall = !filled || (uint32_t)W - cur < need;
-        if (__ballot(shortfall) != 0ull) fill_ahead(active);
-    }
-    __device__ __forceinline__ void fill_inline() {            // fill() expanded in place (one site per kernel)
-        LdsDraws<W> d(row, blk, pos, pretw);
-        d.cur = cur; d.filled = filled;
-        d.flush();
-        d.fill();
-        pos = d.pos; pretw = d.pretw; cur = 0; filled = true;
-    }
-    // The same top-up with the flush and the fill expanded in place: for the ONE site per step that refills every time (the
-    // call costs the callee's register saves and the caller's spills around it, all scratch traffic).
-    __device__ __forceinline__ void ensure_inline(uint32_t need) {
-        const bool shortfall = !filled || (uint32_t)W - cur < need;
-        if (__ballot(shortfall) != 0ull) {
-            LdsDraws<W> d(row, blk, pos, pretw);
-            d.cur = cur; d.filled = filled;
-            d.flush();
-            d.fill();
-            pos = d.pos; pretw = d.pretw; cur = 0; filled = true;
         }
     }
     __device__ __forceinline__ uint32_t randbelow(uint32_t n, int kbits) {
@@ -599,179 +521,6 @@ struct LdsBulkDraws {
 #endif
         }
         return row[W + cur++];
-    }
-    __device__ __forceinline__ uint32_t randbelow(uint32_t n, int kbits) {
-        uint32_t r = next() >> (32 - kbits);
-        while (r >= n) r = next() >> (32 - kbits);
-        return r;
-    }
-    __device__ __forceinline__ double random53() {
-        const uint32_t a = next() >> 5, b = next() >> 6;
-        return (a * 67108864.0 + b) / 9007199254740992.0;
-    }
-};
-
-// Ring window for fused rollouts: W twisted words per env parked in the lane's LDS row as a circular buffer of MT_PAD-word
-// runs.  A top-up replaces only the runs that were consumed completely — the run goes back to the generator block (four
-// 16-byte stores) and the run W words ahead takes its slots — so every word of the block is fetched once and written once,
-// where LdsDraws<W> refetches the whole window (and re-reads every 128-byte line it straddles) whenever it runs low.
-// ensure() is the wave-convergent top-up for the top of a step; after it at least W - MT_PAD + 1 words are parked.
-// Same (pos, pretw) cursor contract as the other queues: pos is the stream position of the ring's base.
-// AHEAD: the stream twists ahead of its cursor in 32-word chunks (the env's record keeps a ready mark, mt_ready_encode): every run the
-// ring fetches is made ready first (mt_make_ready, wave-convergent), so a fetch is plain loads — no words 397 ahead, no twist —
-// and a consumed run is never written back.
-template <int W, bool AHEAD = false>
-struct RingDraws {
-    static_assert(W % MT_PAD == 0 && W >= 2 * MT_PAD && W + 2 * MT_PAD <= MT_N - MT_M, "whole runs; the two runs fetched ahead are independent of the parked ones");
-    static constexpr int NRUN = W / MT_PAD;
-    uint32_t *row, *blk;
-    uint32_t pos, pretw, head, cur;                            // head: slot of the base (a multiple of MT_PAD); cur: words consumed since the base
-    bool filled;
-
-    __device__ __forceinline__ RingDraws(uint32_t *lds_row, uint32_t *block, uint32_t pos_, uint32_t pretw_)
-        : row(lds_row), blk(block), pos(pos_), pretw(pretw_), head(0), cur(0), filled(false) {}
-    // twisted words [logical, logical + MT_PAD) -> slots [slot0, slot0 + MT_PAD)
-    __device__ __forceinline__ void fill_run(uint32_t slot0, uint32_t logical) {
-        MtWindow<MT_PAD> w;
-        uint32_t start = logical;
-        start -= start >= (uint32_t)MT_N ? MT_N : 0;
-        w.load(blk, start);
-#pragma unroll
-        for (int j = 0; j < MT_PAD; ++j) row[slot0 + j] = w.twisted(j, logical, pretw);
-    }
-    // words [logical, logical + count) of the run parked at slot0 go back to the block (count <= MT_PAD)
-    __device__ __forceinline__ void flush_run(uint32_t slot0, uint32_t logical, uint32_t count) {
-        uint32_t kp = logical;
-        kp -= kp >= (uint32_t)MT_N ? MT_N : 0;
-        if (logical + count <= pretw) return;                  // seeded generation: nothing was twisted
-        uint32_t v[MT_PAD];
-#pragma unroll
-        for (int q = 0; q < MT_PAD; ++q) v[q] = row[slot0 + q];
-        if (count == (uint32_t)MT_PAD && logical >= pretw && kp >= (uint32_t)MT_PAD && kp + (uint32_t)MT_PAD <= (uint32_t)MT_N) {
-#pragma unroll
-            for (int q = 0; q < MT_PAD; q += 4) *reinterpret_cast<MtQuad *>(blk + kp + q) = MtQuad{v[q], v[q + 1], v[q + 2], v[q + 3]};
-        } else {
-#pragma unroll
-            for (int q = 0; q < MT_PAD; ++q) {
-                uint32_t k = logical + (uint32_t)q;
-                if ((uint32_t)q < count && k >= pretw) {
-                    k -= k >= (uint32_t)MT_N ? MT_N : 0;
-                    mt_store(blk, k, v[q]);
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ void advance(uint32_t n) {
-        pos += n;
-        if (pos >= (uint32_t)MT_N) { pos -= MT_N; pretw = mt_wrap_ready(pretw); }
-    }
-    // NB runs per round trip: loads of all of them first, then twist and park
-    template <int NB>
-    __device__ __forceinline__ void fill_runs(uint32_t slot0, uint32_t logical, uint32_t nruns) {
-        if constexpr (AHEAD) {                                 // the runs are ready: plain loads
-            uint32_t a[NB][MT_PAD];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                uint32_t start = logical + (uint32_t)(b * MT_PAD);
-                start -= start >= (uint32_t)MT_N ? MT_N : 0;
-                if ((uint32_t)b < nruns) mt_load_run<MT_PAD>(blk + start, a[b]);
-            }
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if ((uint32_t)b < nruns) {
-                    uint32_t sl = slot0 + (uint32_t)(b * MT_PAD);
-                    sl -= sl >= (uint32_t)W ? W : 0;
-#pragma unroll
-                    for (int j = 0; j < MT_PAD; ++j) row[sl + j] = a[b][j];
-                }
-            }
-            return;
-        }
-        MtWindow<MT_PAD> w[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            uint32_t start = logical + (uint32_t)(b * MT_PAD);
-            start -= start >= (uint32_t)MT_N ? MT_N : 0;
-            if ((uint32_t)b < nruns) w[b].load(blk, start);
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            if ((uint32_t)b < nruns) {
-                uint32_t sl = slot0 + (uint32_t)(b * MT_PAD);
-                sl -= sl >= (uint32_t)W ? W : 0;
-#pragma unroll
-                for (int j = 0; j < MT_PAD; ++j) row[sl + j] = w[b].twisted(j, logical + (uint32_t)(b * MT_PAD), pretw);
-            }
-        }
-    }
-    __device__ __forceinline__ void fill_all() {
-        constexpr int NB = 3;
-        if constexpr (AHEAD) mt_make_ready(blk, pos, pretw, (uint32_t)(W + 2 * MT_PAD), true);
-#pragma unroll 1
-        for (int r = 0; r < NRUN; r += NB)
-            fill_runs<NB>((uint32_t)(r * MT_PAD), pos + (uint32_t)(r * MT_PAD), (uint32_t)(NRUN - r < NB ? NRUN - r : NB));
-        head = 0; cur = 0; filled = true;
-    }
-    // every completely consumed run is written back and replaced by the run W words ahead, two runs per round trip
-    __device__ __forceinline__ void top_up() {
-        if (!filled) { fill_all(); return; }
-        if constexpr (AHEAD) mt_make_ready(blk, pos, pretw, cur + (uint32_t)(W + 2 * MT_PAD) < 224u ? cur + (uint32_t)(W + 2 * MT_PAD) : 224u, true);
-#pragma unroll 1
-        while (cur >= (uint32_t)MT_PAD) {
-            const uint32_t n = cur >= 2u * MT_PAD ? 2u : 1u;
-            uint32_t h2 = head + (uint32_t)MT_PAD;
-            h2 -= h2 >= (uint32_t)W ? W : 0;
-            flush_run(head, pos, MT_PAD);
-            if (n == 2u) flush_run(h2, pos + (uint32_t)MT_PAD, MT_PAD);
-            fill_runs<2>(head, pos + (uint32_t)W, n);
-            head = n == 2u ? h2 + (uint32_t)MT_PAD : h2;
-            head -= head >= (uint32_t)W ? W : 0;
-            advance(n * MT_PAD);
-            cur -= n * MT_PAD;
-        }
-    }
-    __device__ __forceinline__ void ensure() {                 // wave-convergent: lanes with nothing to do idle through it
-        const bool want = !filled || cur >= (uint32_t)MT_PAD;
-        if (__ballot(want) != 0ull) { if (want) top_up(); }
-    }
-    __device__ __forceinline__ void ensure_inline(uint32_t) { ensure(); }          // the other queues' spellings (need <= W - MT_PAD + 1)
-    __device__ __forceinline__ void ensure(uint32_t) { ensure(); }
-    __device__ __forceinline__ void flush() {                  // end of the rollout: everything consumed goes back, the ring is dropped
-        if (!filled) return;
-#pragma unroll 1
-        while (cur >= (uint32_t)MT_PAD) {
-            flush_run(head, pos, MT_PAD);
-            head = head + (uint32_t)MT_PAD == (uint32_t)W ? 0u : head + (uint32_t)MT_PAD;
-            advance(MT_PAD);
-            cur -= MT_PAD;
-        }
-        if (cur) { flush_run(head, pos, cur); advance(cur); }
-        head = 0; cur = 0; filled = false;
-    }
-    // rare (more than W - MT_PAD words in one step): a real call, by value
-    static __device__ __attribute__((noinline)) uint2 restart(uint32_t *row, uint32_t *blk, uint32_t pos, uint32_t pretw, uint32_t head, uint32_t cur, bool filled) {
-        RingDraws d(row, blk, pos, pretw);
-        d.head = head; d.cur = cur; d.filled = filled;
-        d.flush();
-        d.fill_all();
-        return make_uint2(d.pos, d.pretw);
-    }
-    __device__ __forceinline__ uint32_t slot_of(uint32_t j) const {
-        uint32_t sl = head + cur + j;
-        sl -= sl >= (uint32_t)W ? W : 0;
-        return sl;
-    }
-    __device__ __forceinline__ bool has(uint32_t n) const { return filled && cur + n <= (uint32_t)W; }
-    __device__ __forceinline__ uint32_t peek(uint32_t j) const { return mt_temper(row[slot_of(j)]); }
-    __device__ __forceinline__ void skip(uint32_t n) { cur += n; }
-    __device__ __forceinline__ uint32_t next() {
-        if (!filled || cur == (uint32_t)W) {
-            const uint2 r = restart(row, blk, pos, pretw, head, cur, filled);
-            pos = r.x; pretw = r.y; head = 0; cur = 0; filled = true;
-        }
-        const uint32_t y = mt_temper(row[slot_of(0)]);
-        cur += 1;
-        return y;
     }
     __device__ __forceinline__ uint32_t randbelow(uint32_t n, int kbits) {
         uint32_t r = next() >> (32 - kbits);

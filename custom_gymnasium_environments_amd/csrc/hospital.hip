@@ -64,7 +64,6 @@ using Draws = QuadRing<RW>;
 __host__ __device__ constexpr int q_cap(int k) { return k == 0 ? 512 : k == 1 ? 256 : k == 2 ? 64 : k == 3 ? 128 : 1024; }
 __host__ __device__ constexpr int q_off(int k) { return k == 0 ? 0 : k == 1 ? 512 : k == 2 ? 768 : k == 3 ? 832 : k == 4 ? 960 : 1984; }
 __host__ __device__ constexpr int q_dept3(int k) { return k <= 2 ? 0 : k == 3 ? 1 : 2; }   // index into the 3 live departments (E, ICU, WARD)
-__host__ __device__ constexpr int q_sev(int k) { return k == 0 ? 3 : k == 1 ? 4 : k == 2 ? 5 : k == 3 ? 5 : k == 4 ? 1 : 2; }
 static_assert(q_off(5) + q_cap(5) == RING, "ring layout");
 
 struct Params {
@@ -146,7 +145,6 @@ struct Misc {
         for (int c = 0; c < 6; ++c) reinterpret_cast<uint4 *>(rec)[c] = make_uint4(r[4 * c], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
     }
     __device__ __forceinline__ uint32_t qlen(int d3) const { return d3 == 0 ? qc(0) + qc(1) + qc(2) : d3 == 1 ? qc(3) : qc(4) + qc(5); }
-    __device__ __forceinline__ uint32_t nurse_dept(int i) const { return (ndept[i / 10] >> (3 * (i % 10))) & 7u; }
 };
 
 struct Ring {
@@ -164,10 +162,6 @@ __device__ __forceinline__ void q_push(Misc &m, const Ring &rg, uint32_t arrival
     rg.rec[CGE_GX(1, p, RING)] = make_uint2(m.next_id | (arrival << 12) | (ins << 23), ttime);
     m.q[K] += 1u << 10; m.sumarr[q_dept3(K)] += arrival; m.next_id += 1;
 }
-template <int K>
-__device__ __forceinline__ void q_pop(Misc &m, uint32_t arrival) {
-    m.q_advance(K, 1u); m.sumarr[q_dept3(K)] -= arrival;
-}
 // front of a department's deque: the head with the smallest sequence number.  Returns the sub-queue (or -1).
 template <int K0, int K1>
 __device__ __forceinline__ int q_front(const Misc &m, const Ring &rg, uint32_t &rec, uint32_t &slot, uint32_t &tt) {
@@ -184,7 +178,7 @@ __device__ __forceinline__ int q_front(const Misc &m, const Ring &rg, uint32_t &
     }
     return best;
 }
-// pop with a run-time sub-queue index: arithmetic on every entry (an if-chain over q_pop<K> gets merged by the compiler
+// pop with a run-time sub-queue index: arithmetic on every entry (an if-chain over compile-time sub-queue indices gets merged by the compiler
 // into m.qh(k) with a run-time k, which would move the whole bookkeeping struct to scratch memory)
 __device__ __forceinline__ void q_pop_dyn(Misc &m, int k, uint32_t arrival) {
 #pragma unroll

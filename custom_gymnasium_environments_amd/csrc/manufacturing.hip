@@ -39,7 +39,6 @@ constexpr int COLS = 23;
 constexpr int CAP = 320;
 constexpr uint32_t NONE = 1023u;
 constexpr int TROW = 6 * CAP;        // places per env in tq / tid
-constexpr uint32_t M_ALIVE = 1u << 6;
 enum : uint32_t { OPERATIONAL = 0, BROKEN = 1, MAINTENANCE = 2 };
 enum : uint32_t { BALANCED = 0, RUSH = 1, QUALITY = 2 };
 
@@ -496,11 +495,6 @@ __device__ __forceinline__ uint32_t env_step(Env &e, const Tab &tb, int32_t max_
     return (term ? 1u : 0u) | (trunc ? 2u : 0u);
 }
 
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64); v = o < v ? o : v; }
-    return v;
-}
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64); v = o > v ? o : v; }

@@ -380,7 +380,6 @@ struct DqCtx {
     // predicated region, so a wave whose lanes need different columns still pays one memory round trip (a load per `if` would
     // be closed by its own s_waitcnt); c1 == c0 re-reads the same 16 bytes
     __device__ __forceinline__ void load_pair(bool want, uint32_t c0, uint32_t c1) {
-        using Q = DigitQ<G>;
         if (want && ((~loaded >> c0) & 1u || (~loaded >> c1) & 1u)) {
             uint32_t *row = my_row();
             const uint4 v0 = dq[(int64_t)c0 * n + i], v1 = dq[(int64_t)c1 * n + i];
@@ -556,7 +555,6 @@ template <int G, int MODE, bool FIN = false>
 __device__ __forceinline__ uint32_t transition(Env<G> &e, const Params &p, int64_t i, uint32_t action, bool valid_action,
                                                uint32_t *__restrict__ obs_row, float &reward, bool &term, bool short_wave, int64_t t = 0,
                                                uint32_t fin_base = 0, int8_t *__restrict__ fin_rowb = nullptr, uint32_t old_tail = 0) {
-    using L = Lay<G>;
     bool need_food = false, was_reset = false, deferred = false, fin_row = false;
     reward = 0.0f;
     term = false;

@@ -480,18 +480,6 @@ struct Env {
 
 struct Totals { uint32_t tp, tw, tq; };
 
-template <int IPL>
-__device__ __forceinline__ Totals totals(const Env<IPL> &e) {
-    uint32_t tp = 0, tws = 0, tq = 0;
-#pragma unroll
-    for (int s = 0; s < IPL; ++s) {
-        tp += e.lp[s] >> 8; tws += e.tw[s];
-#pragma unroll
-        for (int dd = 0; dd < 4; ++dd) tq += e.q[s][dd] & QM;
-    }
-    return Totals{gsum(tp), gsum(tws), gsum(tq)};
-}
-
 // the four global features (:352-361), one per lane: [nveh, tw / max(tp, 1), tq / NI, tp / NI] in float64 (ONE division for the quad;
 // features 1 and 2 are capped at 100 / 50 by cap_feature)
 __device__ __forceinline__ double global_feature(uint32_t ql, uint32_t nveh, const Totals &t, int ni) {
