@@ -62,6 +62,10 @@ class BusConfig(C.Structure):
     _fields_ = [("max_timesteps", C.c_int32), ("autoreset_mode", C.c_int32)]
 
 
+class WorldBuilderConfig(C.Structure):
+    _fields_ = [("grid_size", C.c_int32), ("flatten_obs", C.c_int32), ("autoreset_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Pcg64State(C.Structure):
     """cge_pcg64_state: NumPy's PCG64 bit_generator.state as 40 bytes."""
     _fields_ = [("state_lo", C.c_uint64), ("state_hi", C.c_uint64), ("inc_lo", C.c_uint64), ("inc_hi", C.c_uint64),
@@ -113,6 +117,7 @@ _ENV_TYPES = {
     "manufacturing": (ManufacturingConfig, "final_obs info snapshot done_mask"),
     "hospital": (HospitalConfig, "final_obs info snapshot done_mask"),
     "bus": (BusConfig, "info_indexed error_count snapshot"),
+    "world_builder": (WorldBuilderConfig, "info_indexed error_count state"),
 }
 _HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
 

@@ -639,6 +639,95 @@ const char *cge_bus_last_error(const cge_bus *h);
 const char *cge_bus_last_kernel(const cge_bus *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
+/*   game_logic.py: GameLogic)                                                                    */
+/*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */
+/*   0 pass, 1 farm, 2 lumberyard, 3 quarry, 4 house (Discrete(5), :57).  terminated only (:150): */
+/*   population 0 (-100) or 50 steps at population >= 20 (+100); no time limit.                    */
+/*   obs, Dict layout (flatten_obs = 0; :79-86): ONE uint8 slab per observation of the whole      */
+/*   batch, 16-byte aligned, key-major planes in the reference's key order, each plane starting   */
+/*   at a multiple of 16 bytes (a16 = round up to 16):                                             */
+/*     grid                int8    [n, G, G]  at 0                                                 */
+/*     resources           float32 [n, 4]     at a16(n * G * G)       food, wood, stone, population */
+/*     population_capacity float32 [n, 1]     at resources + 16 n                                  */
+/*     win_steps           int32   [n, 1]     at a16(population_capacity + 4 n)                    */
+/*     slab bytes = a16(win_steps + 4 n)                                                           */
+/*   obs, flat layout (flatten_obs = 1; :69-77, :205-216): float32 [n, G*G + 6], row = the grid    */
+/*   row-major, then food, wood, stone, population, population_capacity, win_steps.                */
+/*   Bit-exact: integer state (int32 resources: the reference's unbounded ints differ only after   */
+/*   millions of steps of one episode); rewards are small integers.  Box.high is not enforced by   */
+/*   the reference (:73) and not here.                                                             */
+/*   Generator: the process-global NumPy legacy np.random, drawn only by a successful build        */
+/*   (game_logic.py:130: randint(#empty cells), no word when one cell is left); the env never      */
+/*   seeds it (reset(seed) reaches np_random only, :109), so cge_world_builder_seed is the         */
+/*   caller's np.random.seed(s_i) for env i.  reset() draws nothing.                               */
+/*   State record (cge_world_builder_get_state / _set_state), little-endian, per env:              */
+/*     int32 [16]  food, wood, stone, population, population_capacity, farm, lumberyard, quarry,   */
+/*                 house, steps, win_steps, reached_win_population, needs_reset, mt_pos, 0, 0      */
+/*     int8  [G*G] the grid, row-major, zero-padded to a multiple of 4 bytes                        */
+/*     uint32[624] key                                                                             */
+/*   (key, mt_pos) is np.random.get_state()[1:3] of env i's stream: mt_pos = 624 right after       */
+/*   seeding.  The record does not hold the running episode's return (episode statistics of the    */
+/*   episode in progress restart at set_state).                                                    */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_world_builder cge_world_builder;
+
+typedef struct {
+    int32_t grid_size;        /* 2..10 (__init__ :39 default 10) */
+    int32_t flatten_obs;      /* 0: Dict slab, 1: float32 rows (:42) */
+    int32_t autoreset_mode;   /* CGE_AUTORESET_* */
+    int32_t reserved;
+} cge_world_builder_config;
+
+enum { /* cge_world_builder_info int32 fields — the values behind _get_info (:218-232) */
+    CGE_WORLD_BUILDER_INFO_STEPS = 0,
+    CGE_WORLD_BUILDER_INFO_WIN_STEPS = 1,
+    CGE_WORLD_BUILDER_INFO_REACHED_WIN_POPULATION = 2,
+    CGE_WORLD_BUILDER_INFO_FOOD = 3,
+    CGE_WORLD_BUILDER_INFO_WOOD = 4,
+    CGE_WORLD_BUILDER_INFO_STONE = 5,
+    CGE_WORLD_BUILDER_INFO_POPULATION = 6,
+    CGE_WORLD_BUILDER_INFO_POPULATION_CAPACITY = 7,
+    CGE_WORLD_BUILDER_INFO_BUILDING_COUNT = 8,   /* index = 0 farm, 1 lumberyard, 2 quarry, 3 house */
+    CGE_WORLD_BUILDER_INFO_NEEDS_RESET = 9
+};
+
+/* WorldBuilderEnv.__init__ :39-97; a grid_size outside 2..10 is CGE_ERR_INVALID_ARG */
+int cge_world_builder_create(const cge_world_builder_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_world_builder **out);
+int cge_world_builder_destroy(cge_world_builder *h);
+/* np.random.seed(s_i) for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Does not reset the envs. */
+int cge_world_builder_seed(cge_world_builder *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :99-121 (game_logic.py:31-54) for envs with mask[i] != 0 (all if NULL); writes the whole observation if obs_out != NULL */
+int cge_world_builder_reset(cge_world_builder *h, const uint8_t *mask, void *obs_out, void *stream);
+/* step :123-166.  actions int32 [n_envs].  An action outside 0..4 raises ValueError in the reference (:133-134); here the env is
+ * left untouched, its row reports (current obs, 0, 0) and a device-side counter is bumped (cge_world_builder_error_count).
+ * truncated_out (nullable) is written 0.  final_obs_out (nullable; one observation): SAME_STEP writes the terminal observations of the
+ * wavefronts (64 consecutive envs) in which an env terminated in this step; rows of envs that did not terminate are unspecified. */
+int cge_world_builder_step(cge_world_builder *h, const int32_t *actions, void *obs_out, float *reward_out, uint8_t *terminated_out,
+                           uint8_t *truncated_out, void *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs], or NULL: env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 5, 0).
+ * obs_out: k observations obs_step_stride elements apart (bytes of the Dict slab: a multiple of 16, >= the slab; floats of the flat
+ * layout: >= n_envs * (G*G + 6)), or with stride 0 the last step's observation.  terminated_traj_out [k, n_envs]; done_count counts
+ * terminated steps.  A SAME_STEP trajectory holds the reset observation at a step that ends an episode. */
+int cge_world_builder_rollout(cge_world_builder *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, void *obs_out,
+                              int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
+                              int32_t *done_count_out, void *stream);
+/* _get_info :218-232 */
+int cge_world_builder_info(cge_world_builder *h, int32_t field_id, int32_t index, int32_t *out, void *stream);
+/* env-steps refused for an invalid action since the last call; synchronises */
+int64_t cge_world_builder_error_count(cge_world_builder *h, void *stream);
+/* canonical per-env records (host memory, n_envs * state_bytes; layout above); both calls synchronise `stream`.  set_state validates:
+ * cells <= 4, counts equal to the grid's census, population_capacity = 10 + 5 * house, mt_pos <= 624, flags 0 / 1; otherwise
+ * CGE_ERR_INVALID_ARG with a message and nothing is written */
+size_t cge_world_builder_state_bytes(const cge_world_builder *h);
+int cge_world_builder_get_state(cge_world_builder *h, void *host_buf, void *stream);
+int cge_world_builder_set_state(cge_world_builder *h, const void *host_buf, void *stream);
+size_t cge_world_builder_device_bytes(const cge_world_builder *h);
+int cge_world_builder_episode_stats(cge_world_builder *h, double *return_out, int32_t *length_out);
+const char *cge_world_builder_last_error(const cge_world_builder *h);
+const char *cge_world_builder_last_kernel(const cge_world_builder *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Action-space sampler: `action_space.sample()` of a batched space on the device               */
 /*   Every reference script drives its env with env.action_space.sample() (snake_env_classic/    */
 /*   example.py:23, smart_parking_env/examples/test_env.py:52, traffic_management_env/demo.py:49, */

@@ -1,0 +1,209 @@
+"""CPU-side checks of the world-builder env: the NumPy model (tests/world_builder_model.py) reproduces, value for value, what the
+unmodified reference recorded (tests/golden/wb_*.npz, written by tests/golden/gen/gen_world_builder.py), its state checkpoints
+included; the fixtures cover what they are for; the C ABI is declared, exported and bound; there is no CPU path; the spaces of both
+layouts are the reference's."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import world_builder_model as wm
+from conftest import ROOT, golden
+
+FIXTURES = ["wb_hash.npz", "wb_builder.npz", "wb_fill.npz", "wb_g7.npz", "wb_g3.npz", "wb_g2.npz", "wb_flat.npz"]
+ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "state_bytes", "get_state",
+       "set_state", "device_bytes", "last_error", "last_kernel"]
+
+
+def draw_window():
+    src = open(os.path.join(ROOT, "custom_gymnasium_environments_amd", "csrc", "world_builder.hip")).read()
+    return int(re.search(r"constexpr int DRAW_WINDOW = (\d+);", src).group(1))
+
+
+def checkpoint_records(z):
+    """uint8 [S, n, state_bytes]: the fixture's checkpoints as canonical records."""
+    n, S = z["ck_header"].shape[:2]
+    return np.stack([wm.pack_state(z["ck_header"][:, s], z["ck_grid"][:, s], z["ck_key"][:, s]) for s in range(S)])
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_model_reproduces_the_reference(name):
+    z = golden(name)
+    n, T = z["reward"].shape
+    G, flat = int(z["grid_size"]), bool(z["flatten_obs"])
+    m = wm.WorldBuilderModel(int(z["seed0"]) + np.arange(n), G, wm.SAME_STEP)
+    ck = {int(s): j for j, s in enumerate(z["ck_steps"])} if "ck_steps" in z else {}
+    recs = checkpoint_records(z) if ck else None
+    obs = m.reset()
+    for k in wm.KEYS:
+        assert np.array_equal(obs[k].reshape(z["obs0_" + k].shape), z["obs0_" + k]) and obs[k].dtype == (np.int8 if k == "grid" else np.int32 if k == "win_steps" else np.float32), k
+    if flat:
+        assert np.array_equal(wm.flatten(obs), z["obs0_flat"]) and wm.flatten(obs).dtype == z["obs0_flat"].dtype == np.float32
+    if 0 in ck:
+        assert np.array_equal(m.get_state(), recs[ck[0]])
+    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
+    seen = 0
+    for t in range(T):
+        obs, reward, terminated, final = m.step(z["actions"][:, t])
+        assert np.array_equal(reward, z["reward"][:, t]), t
+        assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)), t
+        assert np.array_equal(m.words, z["words"][:, t]), t
+        for k in wm.KEYS:                                              # the reference's step() returns the terminal observation
+            assert np.array_equal(final[k].reshape(z["obs_" + k][:, t].shape), z["obs_" + k][:, t]), (t, k)
+        if flat:
+            assert np.array_equal(wm.flatten(final), z["obs_flat"][:, t]), t
+        for i in np.flatnonzero(terminated):                           # then reset() continues the env's stream
+            j = where[(int(i), t)]
+            seen += 1
+            for k in wm.KEYS:
+                assert np.array_equal(obs[k][i].reshape(z["reset_" + k][j].shape), z["reset_" + k][j]), (t, i, k)
+            if flat:
+                assert np.array_equal(wm.flatten(obs)[i], z["reset_flat"][j]), (t, i)
+        if t + 1 in ck:
+            assert np.array_equal(m.get_state(), recs[ck[t + 1]]), t
+    assert seen == len(where) and m.invalid == 0
+
+
+@pytest.mark.parametrize("name", ["wb_hash.npz", "wb_g2.npz"])
+def test_model_info_equals_the_recorded_info(name):
+    z = golden(name)
+    n, T = z["reward"].shape
+    assert json.loads(str(z["info_keys"])) == ["steps", "win_steps", "reached_win_population", "food", "wood", "stone", "population",
+                                              "population_capacity", "farm", "lumberyard", "quarry", "house"]
+    m = wm.WorldBuilderModel(int(z["seed0"]) + np.arange(n), int(z["grid_size"]), wm.DISABLED)
+    for t in range(min(T, 300)):
+        _, _, terminated, _ = m.step(z["actions"][:, t])
+        assert np.array_equal(m.info(), z["info"][:, t]), t            # the terminal step's info, before the reset
+        m.reset(terminated)
+
+
+def test_model_modes_and_invalid_actions():
+    z = golden("wb_g2.npz")
+    n, T = z["reward"].shape
+    seeds = int(z["seed0"]) + np.arange(n)
+    same, nxt = wm.WorldBuilderModel(seeds, 2, wm.SAME_STEP), wm.WorldBuilderModel(seeds, 2, wm.NEXT_STEP)
+    lag = np.zeros(n, int)                                             # NextStep spends one extra step per reset
+    done = np.zeros(n, bool)
+    t_same = np.zeros(n, int)
+    for t in range(60):
+        acts = np.array([z["actions"][i, min(t_same[i], T - 1)] for i in range(n)])
+        _, r, term, _ = nxt.step(acts)
+        assert np.array_equal(r[done], np.zeros(done.sum())) and not term[done].any()
+        for i in np.flatnonzero(~done):
+            assert r[i] == z["reward"][i, t_same[i]] and term[i] == bool(z["terminated"][i, t_same[i]])
+            t_same[i] += 1
+        done = term
+    assert (t_same < 60).any()
+    before = same.get_state()
+    obs, r, term, _ = same.step(np.array([-1, 5, 7, -3]))
+    assert same.invalid == 4 and not r.any() and not term.any() and np.array_equal(same.get_state(), before)
+
+
+def test_fixtures_cover_what_they_are_for():
+    h, b, f = golden("wb_hash.npz"), golden("wb_builder.npz"), golden("wb_fill.npz")
+    W = draw_window()
+    assert 1 <= W <= 8
+    # wb_fill: every bound 100 .. 2 is drawn, the last cell takes no word, refused builds on a full grid draw nothing
+    empties = (f["obs_grid"] == 0).sum((2, 3))                         # after the step
+    for i in range(f["reward"].shape[0]):
+        before = np.concatenate([[100], empties[i, :-1]])
+        built = before - empties[i]
+        assert set(before[built == 1]) == set(range(1, 101))
+        last = np.flatnonzero((before == 1) & (built == 1))
+        assert len(last) == 1 and f["words"][i, last[0]] == 0
+        full = before == 0
+        assert full.sum() >= 250 and not f["words"][i, full].any() and (f["reward"][i, full] <= 0).all() and (f["actions"][i, full] > 0).all()
+    assert f["obs_resources"].max() > 32767 and not f["terminated"].any()
+    assert f["words"].max() > W and h["words"].max() >= 9 and h["words"].max() > W and (h["words"] > W).sum() >= 3
+    assert (h["words"].sum(1) > 624).all() and h["reward"].shape == (16, 2400)
+    assert (b["reward"] == 100).any() and (b["reward"] == -100).any() and b["obs_win_steps"].max() == 50
+    assert (b["reward"] >= 14).any()                                   # a house with the capacity bonus: 4 + 10 (+ shaping)
+    for g, name in ((7, "wb_g7.npz"), (3, "wb_g3.npz"), (2, "wb_g2.npz")):
+        z = golden(name)
+        assert int(z["grid_size"]) == g and (z["obs_grid"] != 0).all((2, 3)).any()      # the grid fills
+    assert golden("wb_g2.npz")["terminated"].sum() >= 4
+    assert golden("wb_flat.npz")["obs_flat"].shape == (4, 200, 106)
+    # ck_steps holds MORE than the steps around each env's first crossing of word 624: also those around the regeneration the first draw
+    # after seeding causes (pos 624 -> 1), as the union over the envs (tests/golden/gen/gen_world_builder.py)
+    for s in (0, 1, 7, 500, 1999):
+        assert s in h["ck_steps"]
+    for s in (0, 1, 7, 99, 100, 399):
+        assert s in f["ck_steps"]
+    pos = h["ck_header"][:, :, 13]
+    assert (pos[:, 0] == 624).all() and (np.diff(pos.astype(int), axis=1) < 0).any(1).all()   # seeded, and every env's cursor wraps between checkpoints
+    for name in FIXTURES:
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", name)) < 1 << 20
+
+
+def test_abi_is_declared_exported_and_bound():
+    from custom_gymnasium_environments_amd import _native, build
+    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(cge_world_builder_[a-z0-9_]+)\s*\(", src))
+    assert declared == {f"cge_world_builder_{fn}" for fn in ABI}
+    assert {n for n in _native.SIGNATURES if n.startswith("cge_world_builder_")} == declared
+    build.build_native()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    assert not [n for n in declared if not hasattr(L, n)]
+    assert ctypes.sizeof(_native.WorldBuilderConfig) == 16
+    assert [f for f, _ in _native.WorldBuilderConfig._fields_] == ["grid_size", "flatten_obs", "autoreset_mode", "reserved"]
+    # create: argument, then config (grid_size 2..10, the mode), then device
+    create = L.cge_world_builder_create
+    for cfg, want in ((_native.WorldBuilderConfig(1, 0, 0, 0), -1), (_native.WorldBuilderConfig(11, 0, 0, 0), -1), (_native.WorldBuilderConfig(10, 0, 7, 0), -1)):
+        out = ctypes.c_void_p(0xdead)
+        assert create(ctypes.byref(cfg), ctypes.c_int64(4), 0, ctypes.c_int64(0), ctypes.byref(out)) == want and out.value is None
+
+
+def test_null_handle_is_an_argument_error():
+    from custom_gymnasium_environments_amd import _native
+    L = _native.lib()
+    buf = ctypes.create_string_buffer(64)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.cge_world_builder_step(None, ptr, ptr, ptr, ptr, None, None, None) == -1
+    assert L.cge_world_builder_rollout(None, 1, None, 0, 0, ptr, 0, None, None, None, None, None) == -1
+    assert L.cge_world_builder_reset(None, None, ptr, None) == -1 and L.cge_world_builder_seed(None, None, 0, None) == -1
+    assert L.cge_world_builder_info(None, 0, 0, ptr, None) == -1 and L.cge_world_builder_state_bytes(None) == 0
+    assert L.cge_world_builder_get_state(None, ptr, None) == -1 and L.cge_world_builder_set_state(None, ptr, None) == -1
+
+
+def test_no_cpu_path():
+    import torch
+    import custom_gymnasium_environments_amd as cge
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(cge.NativeLibraryError):
+        cge.WorldBuilderVectorEnv(8)
+    with pytest.raises(cge.NativeLibraryError):
+        cge.WorldBuilderVectorEnv(8, device="cpu", flatten_obs=True)
+
+
+@pytest.mark.parametrize("name", ["wb_hash.npz", "wb_g3.npz"])
+def test_spaces_equal_the_reference(name):
+    z = golden(name)
+    rec = json.loads(str(z["spaces"]))
+    G = int(z["grid_size"])
+    from custom_gymnasium_environments_amd import world_builder as wb
+    from custom_gymnasium_environments_amd._spaces import batch_space
+    sp, act = wb.make_spaces(G, False)
+    assert sorted(sp.spaces) == sorted(rec["dict_keys"]) == sorted(wm.KEYS) and [k for k, _, _ in wb.planes(G)] == list(wm.KEYS)   # the slab keeps the observation dict's order (:218-229)
+    for k, r in rec["observation"].items():
+        s = sp[k]
+        assert type(s).__name__ == r["kind"] == "Box" and tuple(s.shape) == tuple(r["shape"]) and str(s.dtype) == r["dtype"], k
+        assert float(s.low.min()) == float(s.low.max()) == r["low"] and float(s.high.min()) == float(s.high.max()) == r["high"], k
+    fl, act2 = wb.make_spaces(G, True)
+    r = rec["flat"]
+    assert type(fl).__name__ == r["kind"] and tuple(fl.shape) == tuple(r["shape"]) == (G * G + 6,) and str(fl.dtype) == r["dtype"] == "float32"
+    assert float(fl.low.min()) == r["low"] and float(fl.high.max()) == r["high"]
+    assert type(act).__name__ == type(act2).__name__ == rec["action"]["kind"] and int(act.n) == rec["action"]["n"] == 5
+    assert tuple(batch_space(fl, 6).shape) == (6, G * G + 6)
+    batched = batch_space(sp, 6)
+    assert tuple(batched["grid"].shape) == (6, G, G) and tuple(batched["resources"].shape) == (6, 4)
+    # the slab: planes in key order, each starting at a multiple of 16 bytes, the total a multiple of 16
+    for n in (1, 63, 65, 357):
+        offs, total = wb.slab_layout(n, G)
+        assert all(o % 16 == 0 for o in offs.values()) and total % 16 == 0
+        assert list(offs) == list(wm.KEYS) and offs["grid"] == 0 and offs["resources"] >= n * G * G
+        assert total >= offs["win_steps"] + 4 * n and wm.state_bytes(G) == 64 + (G * G + 3) // 4 * 4 + 2496
