@@ -18,6 +18,10 @@
 // The 50-candle window is a ring whose phase is the SAME for every env of a handle (each step()
 // appends exactly one candle; a reset rewrites all 50 slots and adopts the batch phase), so slot
 // indices are wave-uniform and every history access is a coalesced 8- or 16-byte-per-lane stream.
+// The phase lives in device memory that belongs to the handle, one word per workgroup of 64 envs
+// (`ring[i / 64]`, all equal): a workgroup reads its own word and the stepping kernel writes it back
+// advanced by the steps it ran, so no workgroup ever reads a word another one writes, and the host
+// holds no copy that a replayed HIP graph could leave behind.
 // Dominant traffic per env-step: 1200 B history read + 1044 B obs write (+ 24 B new candle, 128 B
 // scalars, RNG words) — HBM-bound, no reuse, no MFMA-shaped work.
 //
@@ -58,7 +62,8 @@ struct Params {
     uint32_t *mtP, *mtL;  // [n][MT_STRIDE]
     int64_t n, env0;
     Cfg cfg;
-    int32_t mode, phase;  // phase: slot of the OLDEST candle (= where the next one is written)
+    uint32_t *ring;       // [ceil(n / 64)], all equal: the ring phase = slot of the OLDEST candle (= where the next one is written); workgroup b owns word b
+    int32_t mode;
     const void *actions;
     const uint8_t *mask;
     float *obs, *final_obs;
@@ -787,7 +792,7 @@ __global__ __launch_bounds__(RES_WAVES * BLOCK) void resident_kernel(Params p) {
     }
     uint32_t *__restrict__ blkP = p.mtP + li * MT_STRIDE;
     uint32_t *__restrict__ blkL = p.mtL + li * MT_STRIDE;
-    int phase = p.phase;
+    int phase = (int)p.ring[blockIdx.x];                       // the workgroup's own word: nobody else writes it, wave A advances it at the end
 #ifdef CGE_CRYPTO_TIMING
     unsigned long long t_last = wall_clock64();
 #endif
@@ -1019,6 +1024,9 @@ __global__ __launch_bounds__(RES_WAVES * BLOCK) void resident_kernel(Params p) {
         phase = next_phase;
     }
     lds_barrier();                                              // closing barrier: B's last rows are out, C's stream state is in LDS
+    // the launch advances the phase itself: k_steps slots further on.  Every wave of the workgroup has used the old value by now
+    // (the barrier above), and the next launch on the stream reads the new one.
+    if (lane == 0) p.ring[blockIdx.x] = (uint32_t)phase;
     if (live) {
         lcur_unpack(e, m_lcur); e.gauss = m_lcache;
         e.store(p.scal, p.n, i);
@@ -1033,13 +1041,14 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p) {
     const int64_t i0 = (int64_t)blockIdx.x * BLOCK;
     const int64_t i = i0 + threadIdx.x;
     const bool live = i < p.n;
+    const int phase = (int)p.ring[blockIdx.x];                // read only: a reset adopts the batch phase, it does not move it (same 64 envs per workgroup as the resident kernel)
     Env e;
     e.load(p.scal, p.n, live ? i : i0);
     if (live && (!p.mask || p.mask[i])) {
-        do_reset(e, p, i, p.phase, tile + (threadIdx.x & 63u) * ROW);
+        do_reset(e, p, i, phase, tile + (threadIdx.x & 63u) * ROW);
         e.store(p.scal, p.n, i);
     }
-    if (p.obs) observe(e, p, i0, i, live, p.phase, p.obs + i0 * OBS, ~0ull, tile);
+    if (p.obs) observe(e, p, i0, i, live, phase, p.obs + i0 * OBS, ~0ull, tile);
 }
 
 // initial MarketSimulator state (:125-130) and balances; also rewinds the stream cursors after (re)seeding
@@ -1092,7 +1101,7 @@ struct cge_crypto : HandleBase {
     double *closes = nullptr;
     float4 *ohlv = nullptr;
     uint32_t *mtP = nullptr, *mtL = nullptr;
-    int phase = 0;
+    uint32_t *ring = nullptr;      // the ring phase, one word per workgroup of 64 envs: device-owned, see crypto::Params::ring
     bool resident_ready = false;   // resident_kernel's dynamic-LDS limit has been raised
 
     crypto::Params params() const {
@@ -1100,7 +1109,7 @@ struct cge_crypto : HandleBase {
         p.scal = scal; p.closes = closes; p.ohlv = ohlv; p.mtP = mtP; p.mtL = mtL; p.n = n; p.env0 = env0;
         p.cfg = crypto::Cfg{cfg.initial_balance, cfg.trading_fee_rate, cfg.slippage_rate, cfg.min_price, cfg.max_price,
                             cfg.volatility_base, cfg.market_psychology_factor, cfg.max_steps, cfg.action_type};
-        p.mode = cfg.autoreset_mode; p.phase = phase;
+        p.mode = cfg.autoreset_mode; p.ring = ring;
         p.ep_ret = ep_ret; p.ep_len = ep_len;
         return p;
     }
@@ -1117,6 +1126,7 @@ struct cge_crypto : HandleBase {
         CGE_HIP(alloc(ohlv, (size_t)crypto::HLEN * n * sizeof(float4), true, false));
         CGE_HIP(alloc(mtP, mb, false, false));
         CGE_HIP(alloc(mtL, mb, false, false));
+        CGE_HIP(alloc(ring, (size_t)blocks() * sizeof(uint32_t), true, false));   // a fresh handle starts at phase 0
         CGE_HIP(launch_mt_seed(mtP, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
         CGE_HIP(launch_mt_seed(mtL, MT_STRIDE, n, nullptr, 0, env0, 1, nullptr));
         // no reset here: a fresh handle is a freshly constructed env (:244-278) — the MarketSimulator state a
@@ -1189,7 +1199,6 @@ int cge_crypto_step(cge_crypto *h, const void *actions, float *obs_out, float *r
     p.actions = actions;
     // the four-wave resident kernel also serves a single step: its waves share the row, feature and market work of the 64 envs
     CGE_TRY(h, launch_resident(h, p, as_stream(stream), true));
-    h->phase = (h->phase + 1) % crypto::HLEN;
     return CGE_OK;
 }
 
@@ -1204,7 +1213,6 @@ int cge_crypto_rollout(cge_crypto *h, int32_t k_steps, const void *actions, uint
     DeviceGuard g(h->device);
     p.actions = actions;
     CGE_TRY(h, launch_resident(h, p, as_stream(stream), false));
-    h->phase = (h->phase + k_steps) % crypto::HLEN;
     return CGE_OK;
 }
 
@@ -1234,6 +1242,9 @@ int cge_crypto_get_state(cge_crypto *h, void *host_buf, void *stream) {
     CGE_TRY(h, hipMemcpy(oh.data(), h->ohlv, oh.size() * sizeof(float4), hipMemcpyDeviceToHost));
     CGE_TRY(h, hipMemcpy(mp.data(), h->mtP, mp.size() * 4, hipMemcpyDeviceToHost));
     CGE_TRY(h, hipMemcpy(ml.data(), h->mtL, ml.size() * 4, hipMemcpyDeviceToHost));
+    uint32_t phase = 0;
+    CGE_TRY(h, hipMemcpy(&phase, h->ring, sizeof phase, hipMemcpyDeviceToHost));
+    if (phase >= (uint32_t)crypto::HLEN) return h->fail(CGE_ERR_HIP, "cge_crypto_get_state: ring phase out of range");
     const size_t rec = cge_crypto_state_bytes(h);
     for (int64_t i = 0; i < n; ++i) {
         uint8_t *p = (uint8_t *)host_buf + (size_t)i * rec;
@@ -1249,7 +1260,7 @@ int cge_crypto_get_state(cge_crypto *h, void *host_buf, void *stream) {
         memcpy(p + 48, scv, 48);
         double *hh = (double *)(p + 96 + 2 * MT_N * 4);
         for (int k = 0; k < crypto::HLEN; ++k) {
-            const int slot = (h->phase + k) % crypto::HLEN;
+            const int slot = ((int)phase + k) % crypto::HLEN;
             const float4 v = oh[(size_t)slot * n + i];
             hh[5 * k] = v.x; hh[5 * k + 1] = v.y; hh[5 * k + 2] = v.z; hh[5 * k + 3] = cl[(size_t)slot * n + i]; hh[5 * k + 4] = v.w;
         }
@@ -1265,6 +1276,11 @@ int cge_crypto_set_state(cge_crypto *h, const void *host_buf, void *stream) {
     std::vector<double> cl((size_t)crypto::HLEN * n);
     std::vector<float4> oh((size_t)crypto::HLEN * n);
     std::vector<uint32_t> mp((size_t)n * MT_STRIDE, 0u), ml((size_t)n * MT_STRIDE, 0u);
+    // the records are laid out at the phase the device ring has after everything queued on `stream`
+    uint32_t phase = 0;
+    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
+    CGE_TRY(h, hipMemcpy(&phase, h->ring, sizeof phase, hipMemcpyDeviceToHost));
+    if (phase >= (uint32_t)crypto::HLEN) return h->fail(CGE_ERR_HIP, "cge_crypto_set_state: ring phase out of range");
     const size_t rec = cge_crypto_state_bytes(h);
     for (int64_t i = 0; i < n; ++i) {
         const uint8_t *p = (const uint8_t *)host_buf + (size_t)i * rec;
@@ -1289,12 +1305,11 @@ int cge_crypto_set_state(cge_crypto *h, const void *host_buf, void *stream) {
         memcpy(&mp[(size_t)i * MT_STRIDE + MT_N], &mp[(size_t)i * MT_STRIDE], MT_PAD * 4);       // mirror words (cge_device.hpp)
         memcpy(&ml[(size_t)i * MT_STRIDE + MT_N], &ml[(size_t)i * MT_STRIDE], MT_PAD * 4);
         for (int k = 0; k < crypto::HLEN; ++k) {
-            const int slot = (h->phase + k) % crypto::HLEN;
+            const int slot = ((int)phase + k) % crypto::HLEN;
             cl[(size_t)slot * n + i] = hh[5 * k + 3];
             oh[(size_t)slot * n + i] = make_float4((float)hh[5 * k], (float)hh[5 * k + 1], (float)hh[5 * k + 2], (float)hh[5 * k + 4]);
         }
     }
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
     CGE_TRY(h, hipMemcpy(h->scal, sc.data(), sc.size() * sizeof(uint4), hipMemcpyHostToDevice));
     CGE_TRY(h, hipMemcpy(h->closes, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
     CGE_TRY(h, hipMemcpy(h->ohlv, oh.data(), oh.size() * sizeof(float4), hipMemcpyHostToDevice));

@@ -10,12 +10,14 @@ pytestmark = pytest.mark.gpu
 MT = 640 * 4          # one MT19937 stream block: 624 words + 16 mirror words (cge_device.hpp: MT_STRIDE)
 SNAP_HEADER = 32      # cge_host.hpp: SnapHeader
 
-# name -> (ctor kwargs, device bytes per env, device bytes per handle, of those: bytes outside the snapshot; None = no snapshot)
+# name -> (ctor kwargs, device bytes per env, device bytes per handle (a function of n where it depends on it), of those: bytes outside the
+# snapshot; None = no snapshot)
 ENVS = {
     # state 3 uint4 columns (grid 10: 12 words) + stream block + digit ring 2 uint4 columns; one 8-byte error counter
     "Snake": (dict(grid_size=10), 3 * 16 + MT + 2 * 16, 8, None),
-    # scalars 4 uint4 + closes 50 doubles + ohlv 50 float4 + two stream blocks
-    "Crypto": (dict(action_type="discrete"), 4 * 16 + 50 * 8 + 50 * 16 + 2 * MT, 0, None),
+    # scalars 4 uint4 + closes 50 doubles + ohlv 50 float4 + two stream blocks; per handle: the candle ring's phase, one 4-byte word per
+    # workgroup of 64 envs
+    "Crypto": (dict(action_type="discrete"), 4 * 16 + 50 * 8 + 50 * 16 + 2 * MT, lambda n: 4 * -(-n // 64), None),
     # 9 intersections: record of (8 + 6 * 9 + 3) & ~3 = 64 words + stream block
     "Traffic": ({}, 64 * 4 + MT, 0, None),
     # state 18 uint4 columns + stream block
@@ -33,7 +35,7 @@ ENVS = {
     "Bus": ({}, 3 * 16 + MT, 8, 8),
 }
 # ... which is, written out (n = 1, n = 200):
-DEVICE_BYTES = {"Snake": (2648, 528008), "Crypto": (6384, 1276800), "Traffic": (2816, 563200), "Parking": (2848, 569600),
+DEVICE_BYTES = {"Snake": (2648, 528008), "Crypto": (6388, 1276816), "Traffic": (2816, 563200), "Parking": (2848, 569600),
                 "Climate": (80, 16000), "Fleet": (115872, 1166592), "Manufacturing": (25008, 5001600), "Hospital": (27472, 5494400),
                 "Bus": (2616, 521608)}
 SNAPSHOT_BYTES = {"Parking": (2880, 569632), "Climate": (112, 16032), "Fleet": (17600, 1068320), "Manufacturing": (25040, 5001632),
@@ -46,6 +48,8 @@ def test_device_and_snapshot_bytes(name, n):
     import custom_gymnasium_environments_amd as cge
     kw, per_env, per_handle, not_in_snapshot = ENVS[name]
     want = DEVICE_BYTES[name][n == 200]
+    if callable(per_handle):
+        per_handle = per_handle(n)
     assert want == per_env * n + per_handle          # the table above agrees with its own derivation
     Env = getattr(cge, name + "VectorEnv")
     env = Env(n, **kw)

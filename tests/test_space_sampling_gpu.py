@@ -30,6 +30,8 @@ ENVS = {
     "fleet": lambda n, **kw: cge.FleetVectorEnv(n, **kw),
     "traffic": lambda n, **kw: cge.TrafficVectorEnv(n, **kw),
     "climate": lambda n, **kw: cge.ClimateVectorEnv(n, **kw),
+    "bus": lambda n, **kw: cge.BusVectorEnv(n, **kw),                                     # Dict observations
+    "world_builder": lambda n, **kw: cge.WorldBuilderVectorEnv(n, **kw),
 }
 
 
@@ -219,9 +221,16 @@ def test_snake_one_million_envs():
     env.close()
 
 
+def _parts(obs):
+    """an observation as a list of tensors (a Dict observation: its tensors in key order)"""
+    return [obs[k] for k in sorted(obs)] if isinstance(obs, dict) else [obs]
+
+
 def _outputs(ret):
+    """step()'s outputs as (name, private copy) pairs; a Dict observation key by key"""
     obs, rew, term, trunc, _ = ret
-    return [t.clone() for t in (obs, rew, term, trunc)]
+    named = [(f"obs[{k}]", obs[k]) for k in sorted(obs)] if isinstance(obs, dict) else [("obs", obs)]
+    return [(what, t.clone()) for what, t in named + [("reward", rew), ("terminated", term), ("truncated", trunc)]]
 
 
 def _to_step(ref):
@@ -241,19 +250,20 @@ def test_step_on_sampled_actions_equals_step_on_numpy_actions(name):
     for t in range(20):
         ra = _outputs(a.step(s.sample()))
         rb = _outputs(b.step(_to_step(ref_sample(b.action_space, rng))))
-        for what, x, y in zip(("obs", "reward", "terminated", "truncated"), ra, rb):
+        assert [w for w, _ in ra] == [w for w, _ in rb]
+        for (what, x), (_, y) in zip(ra, rb):
             assert torch.equal(x, y), (name, t, what)
     a.close()
     b.close()
 
 
-K = 16
+K = 16          # not 0 mod 50 (nor is 2 K or 3 K): every replay meets crypto's 50-candle ring at another phase than the capture did
 
 
-@pytest.mark.parametrize("name", ["snake", "parking", "climate", "fleet", "traffic"])
+@pytest.mark.parametrize("name", list(ENVS))
 def test_sample_and_step_capture_in_one_graph(name):
-    """16 x (sample(out=buf) + step(buf)) in one torch.cuda.CUDAGraph, replayed twice: the sampler's stream advances on the device
-    at every replay, and actions and env outputs equal an eager run from the same seeds."""
+    """16 x (sample(out=buf) + step(buf)) in one torch.cuda.CUDAGraph, replayed twice (crypto: three times): the sampler's stream
+    advances on the device at every replay, and actions and env outputs equal an eager run from the same seeds."""
     n = 1000
     g_env, e_env = ENVS[name](n, reuse_buffers=True), ENVS[name](n)
     g_env.reset(seed=8)
@@ -268,27 +278,31 @@ def test_sample_and_step_capture_in_one_graph(name):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     we = e_env.step(es_first)
-    assert torch.equal(w[0], we[0])
+    assert all(torch.equal(x, y) for x, y in zip(_parts(w[0]), _parts(we[0])))
 
     def flat(x):
         return torch.cat([x[k].reshape(n, -1).to(torch.float32) for k in sorted(x)], 1) if isinstance(x, dict) else x.reshape(n, -1).to(torch.float32)
     width = flat(buf).shape[1]
-    hist = {"act": torch.empty((K, n, width), device="cuda"), "obs": torch.empty((K,) + tuple(w[0].shape), dtype=w[0].dtype, device="cuda"),
+    hist = {"act": torch.empty((K, n, width), device="cuda"),
+            "obs": [torch.empty((K,) + tuple(x.shape), dtype=x.dtype, device="cuda") for x in _parts(w[0])],
             "rew": torch.empty((K, n), device="cuda"), "done": torch.empty((K, n), dtype=torch.bool, device="cuda")}
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         for t in range(K):
             gs.sample(out=buf)
             ob, r, te, tr, _ = g_env.step(buf)
-            hist["act"][t].copy_(flat(buf)); hist["obs"][t].copy_(ob); hist["rew"][t].copy_(r); hist["done"][t].copy_(te | tr)
-    for rep in range(2):
+            hist["act"][t].copy_(flat(buf)); hist["rew"][t].copy_(r); hist["done"][t].copy_(te | tr)
+            for dst, src in zip(hist["obs"], _parts(ob)):
+                dst[t].copy_(src)
+    for rep in range(3 if name.startswith("crypto") else 2):
         g.replay()
         torch.cuda.synchronize()
         for t in range(K):
             act = es.sample()
             ob, r, te, tr, _ = e_env.step(act)
             assert torch.equal(hist["act"][t], flat(act)), (name, rep, t, "actions")
-            assert torch.equal(hist["obs"][t], ob), (name, rep, t, "obs")
+            for j, (x, y) in enumerate(zip(hist["obs"], _parts(ob))):
+                assert torch.equal(x[t], y), (name, rep, t, "obs", j)
             assert torch.equal(hist["rew"][t], r), (name, rep, t, "reward")
             assert torch.equal(hist["done"][t], te | tr), (name, rep, t, "done")
     assert gs.state == es.state
