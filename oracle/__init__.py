@@ -1,7 +1,8 @@
 """CPU oracle for the env-stepping hot path — TEST INFRASTRUCTURE ONLY.
 
-A plain-C restatement (oracle/orc_*.c) of the reference's step()/reset() dynamics, wrapped with
-ctypes.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
+A plain-C restatement (oracle/orc_<env>.c) of the reference's step()/reset() dynamics, wrapped with
+ctypes.  The batch driver around them (seed / reset(mask) / step / rollout, the autoreset modes, episode
+statistics) is written once, in oracle/orc_batch.h, and wrapped once, in _Oracle below.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
 package, and only as the checker / reported CPU baseline.  The product package
 (custom_gymnasium_environments_amd) never imports it and has no CPU fallback.
 
@@ -75,100 +76,121 @@ def _declare(L):
     L.orc_pcg_state_export.argtypes = [vp, vp]
     L.orc_hash_action_export.argtypes = [u64, u64, u64, u32, u32]; L.orc_hash_action_export.restype = u32
 
-    L.orc_snake_create.argtypes = [i64, i32, i32]; L.orc_snake_create.restype = vp
-    L.orc_snake_destroy.argtypes = [vp]
-    L.orc_snake_seed.argtypes = [vp, vp]
-    L.orc_snake_reset.argtypes = [vp, vp, vp]
-    L.orc_snake_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]; L.orc_snake_step.restype = i32
-    L.orc_snake_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_snake_info.argtypes = [vp, i32, vp]
-    L.orc_snake_state_bytes.argtypes = [vp]; L.orc_snake_state_bytes.restype = C.c_size_t
-    L.orc_snake_get_state.argtypes = [vp, vp]
-    L.orc_snake_set_state.argtypes = [vp, vp]
+    # the batch driver (oracle/orc_batch.h), name: (create's arguments after n, step's action arguments, has reward64, step's restype)
+    for nm, (create, nact, reward64, step_res) in {"snake": ([i32, i32], 1, False, i32), "crypto": ([i32, i32], 1, True, i32),
+                                                   "traffic": ([i32], 1, True, None), "parking": ([i32], 1, True, None),
+                                                   "climate": ([i32], 2, True, None), "fleet": ([i32], 1, True, None),
+                                                   "hospital": ([i32], 1, True, None), "manufacturing": ([i32], 1, True, None)}.items():
+        f = {k: getattr(L, f"orc_{nm}_{k}") for k in ("create", "destroy", "seed", "reset", "step", "rollout", "set_max_steps", "episode_stats")}
+        f["create"].argtypes = [i64] + create; f["create"].restype = vp
+        f["destroy"].argtypes = [vp]
+        f["seed"].argtypes = [vp, vp]
+        f["reset"].argtypes = [vp, vp, vp]
+        f["step"].argtypes = [vp] * (1 + nact + 5 + reward64); f["step"].restype = step_res
+        f["rollout"].argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
+        f["set_max_steps"].argtypes = [vp, i32]
+        f["episode_stats"].argtypes = [vp, vp, vp]
+    for nm in ("snake", "crypto", "climate", "fleet", "hospital", "manufacturing"):
+        getattr(L, f"orc_{nm}_info").argtypes = [vp, i32, vp]
+    for nm in ("snake", "crypto", "traffic"):
+        getattr(L, f"orc_{nm}_get_state").argtypes = [vp, vp]
+        getattr(L, f"orc_{nm}_set_state").argtypes = [vp, vp]
+        getattr(L, f"orc_{nm}_state_bytes").argtypes = [] if nm == "crypto" else [vp]
+        getattr(L, f"orc_{nm}_state_bytes").restype = C.c_size_t
     L.orc_snake_render_rgb.argtypes = [vp, vp]
-
-    L.orc_crypto_create.argtypes = [i64, i32, i32]; L.orc_crypto_create.restype = vp
     L.orc_crypto_set_config.argtypes = [vp, vp]
-    L.orc_crypto_destroy.argtypes = [vp]
-    L.orc_crypto_seed.argtypes = [vp, vp]
-    L.orc_crypto_reset.argtypes = [vp, vp, vp]
-    L.orc_crypto_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]; L.orc_crypto_step.restype = i32
-    L.orc_crypto_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_crypto_info.argtypes = [vp, i32, vp]
-    L.orc_crypto_state_bytes.argtypes = []; L.orc_crypto_state_bytes.restype = C.c_size_t
-    L.orc_crypto_get_state.argtypes = [vp, vp]
-    L.orc_crypto_set_state.argtypes = [vp, vp]
-
-    L.orc_traffic_create.argtypes = [i64, i32]; L.orc_traffic_create.restype = vp
-    L.orc_traffic_destroy.argtypes = [vp]
-    L.orc_traffic_seed.argtypes = [vp, vp]
-    L.orc_traffic_reset.argtypes = [vp, vp, vp]
-    L.orc_traffic_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_traffic_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
     L.orc_traffic_info.argtypes = [vp, i32, i32, vp]
     L.orc_traffic_total_reward.argtypes = [vp, vp]
-    L.orc_traffic_state_bytes.argtypes = [vp]; L.orc_traffic_state_bytes.restype = C.c_size_t
     L.orc_traffic_set_layout.argtypes = [vp, i32, i32, i32, i32, dbl]; L.orc_traffic_set_layout.restype = i32
     L.orc_traffic_obs_dim.argtypes = [vp]; L.orc_traffic_obs_dim.restype = i32
     L.orc_traffic_num_intersections.argtypes = [vp]; L.orc_traffic_num_intersections.restype = i32
-    L.orc_traffic_get_state.argtypes = [vp, vp]
-    L.orc_traffic_set_state.argtypes = [vp, vp]
-
-    L.orc_parking_create.argtypes = [i64, i32]; L.orc_parking_create.restype = vp
-    L.orc_parking_destroy.argtypes = [vp]
-    L.orc_parking_seed.argtypes = [vp, vp]
-    L.orc_parking_reset.argtypes = [vp, vp, vp]
-    L.orc_parking_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_parking_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
     L.orc_parking_info.argtypes = [vp, i32, i32, vp]
     L.orc_parking_info64.argtypes = [vp, i32, vp]
-
-    L.orc_climate_create.argtypes = [i64, i32]; L.orc_climate_create.restype = vp
-    L.orc_climate_destroy.argtypes = [vp]
-    L.orc_climate_seed.argtypes = [vp, vp]
-    L.orc_climate_reset.argtypes = [vp, vp, vp]
-    L.orc_climate_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_climate_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_climate_info.argtypes = [vp, i32, vp]
     L.orc_climate_hash_action.argtypes = [u64, u64, u64, vp, vp]
     L.orc_climate_set_max_occupancy.argtypes = [vp, i32]
-
-    L.orc_fleet_create.argtypes = [i64, i32]; L.orc_fleet_create.restype = vp
-    L.orc_fleet_destroy.argtypes = [vp]
-    L.orc_fleet_seed.argtypes = [vp, vp]
-    L.orc_fleet_reset.argtypes = [vp, vp, vp]
-    L.orc_fleet_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_fleet_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_fleet_info.argtypes = [vp, i32, vp]
-    L.orc_hospital_create.argtypes = [i64, i32]; L.orc_hospital_create.restype = vp
-    L.orc_hospital_destroy.argtypes = [vp]
-    L.orc_hospital_seed.argtypes = [vp, vp]
-    L.orc_hospital_reset.argtypes = [vp, vp, vp]
-    L.orc_hospital_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_hospital_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_hospital_info.argtypes = [vp, i32, vp]
-    L.orc_manufacturing_create.argtypes = [i64, i32]; L.orc_manufacturing_create.restype = vp
-    L.orc_manufacturing_destroy.argtypes = [vp]
-    L.orc_manufacturing_seed.argtypes = [vp, vp]
-    L.orc_manufacturing_reset.argtypes = [vp, vp, vp]
-    L.orc_manufacturing_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.orc_manufacturing_rollout.argtypes = [vp, i32, u64, i64, i64, vp, vp, vp]
-    L.orc_manufacturing_info.argtypes = [vp, i32, vp]
-    for _nm in ("snake", "crypto", "traffic", "parking", "climate", "fleet", "hospital", "manufacturing"):
-        getattr(L, f"orc_{_nm}_set_max_steps").argtypes = [vp, i32]
-        getattr(L, f"orc_{_nm}_episode_stats").argtypes = [vp, vp, vp]
 
 
 NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 
 
-class _EpisodeStats:
-    """(return float64[n], length int32[n]) of each env's LAST finished episode — what gymnasium's RecordEpisodeStatistics
-    would report in infos["episode"] = {"r", "l"} at the step the episode ended (oracle/orc_epstats.h)."""
+class _Oracle:
+    """ctypes plumbing of the batch driver every env type shares (oracle/orc_batch.h).  A subclass names its C functions (_name)
+    and says what differs: the observation rows (_obs_dtype, _obs_shape()), the action array (_act_dtype, _act_shape()), whether
+    step() has the float64 reward output (_reward64: all but snake; kept as self.last_reward64).  Where the C step() returns the
+    number of invalid actions (snake, discrete crypto; void elsewhere, see _declare) a nonzero count raises ValueError."""
+    _name = None
+    _obs = None                       # length of a flat observation row
+    _obs_dtype = np.float32
+    _act_dtype = np.int32
+    _reward64 = True
+
+    def __init__(self, n, mode=SAME_STEP, max_steps=None, create_args=()):
+        self.n, self.mode = int(n), int(mode)
+        self.h = self._fn("create")(self.n, *create_args, self.mode)
+        if not self.h:
+            raise ValueError(f"orc_{self._name}_create failed")
+        if max_steps is not None:                          # the env type's time limit (episode_minutes, max_timesteps, ...)
+            self._fn("set_max_steps")(self.h, int(max_steps))
+
+    def __del__(self):
+        if getattr(self, "h", None) and lib is not None:          # (module globals are None at interpreter shutdown)
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def _fn(self, f):
+        return getattr(lib(), f"orc_{self._name}_{f}")
+
+    def _obs_shape(self):
+        return (self._obs,)
+
+    def _act_shape(self):
+        return ()
+
+    def _new_obs(self):
+        return np.zeros((self.n,) + self._obs_shape(), self._obs_dtype)
+
+    def seed(self, seeds):
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert seeds.shape == (self.n,)
+        self._fn("seed")(self.h, _p(seeds))
+
+    def reset(self, mask=None):
+        obs = self._new_obs()
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        self._fn("reset")(self.h, _p(m), _p(obs))
+        return obs
+
+    def step(self, actions, want_final=False):
+        a = np.ascontiguousarray(actions, dtype=self._act_dtype)
+        assert a.shape == (self.n,) + self._act_shape()
+        return self._step((a,), want_final)
+
+    def _step(self, acts, want_final):
+        obs = self._new_obs()
+        rew = np.zeros(self.n, np.float32)
+        rew64 = (np.zeros(self.n, np.float64),) if self._reward64 else ()
+        te = np.zeros(self.n, np.uint8)
+        tr = np.zeros(self.n, np.uint8)
+        fin = np.zeros_like(obs) if want_final else None
+        bad = self._fn("step")(self.h, *map(_p, acts + (obs, rew) + rew64 + (te, tr, fin)))
+        if bad:
+            raise ValueError(f"Invalid action in {bad} env(s)")
+        if rew64:
+            self.last_reward64 = rew64[0]
+        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
+
+    def rollout(self, k, a_seed, t0=0, env0=0, want_obs=True):
+        obs = self._new_obs() if want_obs else None
+        rs = np.zeros(self.n, np.float64 if self._reward64 else np.float32)
+        dc = np.zeros(self.n, np.int32)
+        self._fn("rollout")(self.h, k, a_seed, t0, env0, _p(obs), _p(rs), _p(dc))
+        return obs, rs, dc
 
     def episode_stats(self):
+        """(return float64[n], length int32[n]) of each env's LAST finished episode — what gymnasium's RecordEpisodeStatistics
+        would report in infos["episode"] = {"r", "l"} at the step the episode ended (oracle/orc_epstats.h)."""
         ret, ln = np.zeros(self.n, np.float64), np.zeros(self.n, np.int32)
-        getattr(lib(), f"orc_{self._name}_episode_stats")(self.h, _p(ret), _p(ln))
+        self._fn("episode_stats")(self.h, _p(ret), _p(ln))
         return ret, ln
 
 
@@ -231,52 +253,19 @@ def hash_action(a_seed, env, t, n, j=0):
     return lib().orc_hash_action_export(a_seed, env, t, n, j)
 
 
-class SnakeOracle(_EpisodeStats):
-    """Batch of independent SnakeEnvClassic restatements (oracle/orc_snake.c)."""
-    _name = "snake"
+class SnakeOracle(_Oracle):
+    """Batch of independent SnakeEnvClassic restatements (oracle/orc_snake.c); int8 (grid, grid) observations, float32 rewards only."""
+    _name, _obs_dtype, _reward64 = "snake", np.int8, False
 
     def __init__(self, n, grid=10, mode=SAME_STEP, max_steps=None):
-        self.n, self.grid, self.mode = int(n), int(grid), int(mode)
-        self.h = lib().orc_snake_create(self.n, self.grid, self.mode)
-        if not self.h:
-            raise ValueError("orc_snake_create failed")
-        if max_steps is not None:
-            lib().orc_snake_set_max_steps(self.h, int(max_steps))
+        self.grid = int(grid)
+        super().__init__(n, mode, max_steps, (self.grid,))
 
-    def __del__(self):
-        if getattr(self, "h", None) and lib is not None:          # (module globals are None at interpreter shutdown)
-            lib().orc_snake_destroy(self.h)
-            self.h = None
-
-    def seed(self, seeds):
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        assert seeds.shape == (self.n,)
-        lib().orc_snake_seed(self.h, _p(seeds))
-
-    def reset(self, mask=None):
-        obs = np.zeros((self.n, self.grid, self.grid), np.int8)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        lib().orc_snake_reset(self.h, _p(m), _p(obs))
-        return obs
-
-    def step(self, actions, want_final=False):
-        a = np.ascontiguousarray(actions, dtype=np.int32)
-        obs = np.zeros((self.n, self.grid, self.grid), np.int8)
-        rew = np.zeros(self.n, np.float32)
-        te = np.zeros(self.n, np.uint8)
-        tr = np.zeros(self.n, np.uint8)
-        fin = np.zeros_like(obs) if want_final else None
-        bad = lib().orc_snake_step(self.h, _p(a), _p(obs), _p(rew), _p(te), _p(tr), _p(fin))
-        if bad:
-            raise ValueError(f"Invalid action in {bad} env(s)")
-        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
+    def _obs_shape(self):
+        return (self.grid, self.grid)
 
     def rollout(self, k, a_seed, t0=0, env0=0):
-        obs = np.zeros((self.n, self.grid, self.grid), np.int8)
-        rs = np.zeros(self.n, np.float32)
-        dc = np.zeros(self.n, np.int32)
-        lib().orc_snake_rollout(self.h, k, a_seed, t0, env0, _p(obs), _p(rs), _p(dc))
-        return obs, rs, dc
+        return super().rollout(k, a_seed, t0, env0)
 
     def info(self, field):
         out = np.zeros(self.n, np.int32)
@@ -305,22 +294,19 @@ CRYPTO_INFO = {"portfolio_value": 0, "cash": 1, "holdings": 2, "current_price": 
                "regime": 5, "step": 6, "trend_strength": 7, "episodes": 8, "needs_reset": 9, "cash_kind": 10}
 
 
-class CryptoOracle(_EpisodeStats):
-    """Batch of independent CryptoTradingEnv restatements (oracle/orc_crypto.c)."""
-    _name = "crypto"
+class CryptoOracle(_Oracle):
+    """Batch of independent CryptoTradingEnv restatements (oracle/orc_crypto.c); actions int32 (n,) or, continuous, float32 (n, 2)."""
+    _name, _obs = "crypto", CRYPTO_OBS
 
     # TradingConfig fields (crypto_trading_env.py:28-38) in the order orc_crypto_set_config takes them, with the reference defaults
     CONFIG_FIELDS = (("initial_balance", 10000.0), ("trading_fee_rate", 0.001), ("slippage_rate", 0.0005), ("min_price", 100.0),
                      ("max_price", 100000.0), ("volatility_base", 0.02), ("market_psychology_factor", 0.1))
 
     def __init__(self, n, action_type="discrete", mode=SAME_STEP, max_steps=None, config=None):
-        self.n, self.mode = int(n), int(mode)
         self.continuous = action_type == "continuous"
-        self.h = lib().orc_crypto_create(self.n, int(self.continuous), self.mode)
-        if not self.h:
-            raise ValueError("orc_crypto_create failed")
-        if max_steps is not None:
-            lib().orc_crypto_set_max_steps(self.h, int(max_steps))
+        if self.continuous:
+            self._act_dtype = np.float32
+        super().__init__(n, mode, max_steps, (int(self.continuous),))
         if config:
             unknown = set(config) - {k for k, _ in self.CONFIG_FIELDS}
             if unknown:
@@ -328,47 +314,8 @@ class CryptoOracle(_EpisodeStats):
             cfg = np.array([float(config.get(k, d)) for k, d in self.CONFIG_FIELDS], np.float64)
             lib().orc_crypto_set_config(self.h, _p(cfg))
 
-    def __del__(self):
-        if getattr(self, "h", None) and lib is not None:          # (module globals are None at interpreter shutdown)
-            lib().orc_crypto_destroy(self.h)
-            self.h = None
-
-    def seed(self, seeds):
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        assert seeds.shape == (self.n,)
-        lib().orc_crypto_seed(self.h, _p(seeds))
-
-    def reset(self, mask=None):
-        obs = np.zeros((self.n, CRYPTO_OBS), np.float32)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        lib().orc_crypto_reset(self.h, _p(m), _p(obs))
-        return obs
-
-    def step(self, actions, want_final=False):
-        if self.continuous:
-            a = np.ascontiguousarray(actions, dtype=np.float32)
-            assert a.shape == (self.n, 2)
-        else:
-            a = np.ascontiguousarray(actions, dtype=np.int32)
-            assert a.shape == (self.n,)
-        obs = np.zeros((self.n, CRYPTO_OBS), np.float32)
-        rew = np.zeros(self.n, np.float32)
-        rew64 = np.zeros(self.n, np.float64)
-        te = np.zeros(self.n, np.uint8)
-        tr = np.zeros(self.n, np.uint8)
-        fin = np.zeros_like(obs) if want_final else None
-        bad = lib().orc_crypto_step(self.h, _p(a), _p(obs), _p(rew), _p(rew64), _p(te), _p(tr), _p(fin))
-        if bad:
-            raise ValueError(f"Invalid action in {bad} env(s)")
-        self.last_reward64 = rew64
-        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
-
-    def rollout(self, k, a_seed, t0=0, env0=0, want_obs=True):
-        obs = np.zeros((self.n, CRYPTO_OBS), np.float32) if want_obs else None
-        rs = np.zeros(self.n, np.float64)
-        dc = np.zeros(self.n, np.int32)
-        lib().orc_crypto_rollout(self.h, k, a_seed, t0, env0, _p(obs), _p(rs), _p(dc))
-        return obs, rs, dc
+    def _act_shape(self):
+        return (2,) if self.continuous else ()
 
     def info(self, field):
         out = np.zeros(self.n, np.float64)
@@ -391,58 +338,23 @@ TRAFFIC_INFO = {"timestep": 0, "num_vehicles": 1, "light_phase": 2, "light_timer
                 "total_waiting_time": 5, "queue_len": 6, "queue_dest": 7, "queue_wait": 8, "episodes": 9, "needs_reset": 10}
 
 
-class TrafficOracle(_EpisodeStats):
+class TrafficOracle(_Oracle):
     """Batch of independent TrafficManagementEnv restatements (oracle/orc_traffic.c).  grid_size / num_intersections / max_vehicles /
     spawn_rate are the reference constructor's arguments (environment.py:62-83); num_intersections <= 16 here."""
     _name = "traffic"
 
     def __init__(self, n, mode=SAME_STEP, max_steps=None, grid_size=(5, 5), num_intersections=9, max_vehicles=50, spawn_rate=0.3):
-        self.n, self.mode = int(n), int(mode)
-        self.h = lib().orc_traffic_create(self.n, self.mode)
-        if not self.h:
-            raise ValueError("orc_traffic_create failed")
-        if max_steps is not None:
-            lib().orc_traffic_set_max_steps(self.h, int(max_steps))
+        super().__init__(n, mode, max_steps)
         if lib().orc_traffic_set_layout(self.h, int(grid_size[0]), int(grid_size[1]), int(num_intersections), int(max_vehicles), float(spawn_rate)):
             raise ValueError("layout outside the oracle's capacity (num_intersections <= 16)")
         self.obs_dim = int(lib().orc_traffic_obs_dim(self.h))
         self.ni = int(lib().orc_traffic_num_intersections(self.h))
 
-    def __del__(self):
-        if getattr(self, "h", None) and lib is not None:          # (module globals are None at interpreter shutdown)
-            lib().orc_traffic_destroy(self.h)
-            self.h = None
+    def _obs_shape(self):
+        return (self.obs_dim,)
 
-    def seed(self, seeds):
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        assert seeds.shape == (self.n,)
-        lib().orc_traffic_seed(self.h, _p(seeds))
-
-    def reset(self, mask=None):
-        obs = np.zeros((self.n, self.obs_dim), np.float32)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        lib().orc_traffic_reset(self.h, _p(m), _p(obs))
-        return obs
-
-    def step(self, actions, want_final=False):
-        a = np.ascontiguousarray(actions, dtype=np.int32)
-        assert a.shape == (self.n, self.ni)
-        obs = np.zeros((self.n, self.obs_dim), np.float32)
-        rew = np.zeros(self.n, np.float32)
-        rew64 = np.zeros(self.n, np.float64)
-        te = np.zeros(self.n, np.uint8)
-        tr = np.zeros(self.n, np.uint8)
-        fin = np.zeros_like(obs) if want_final else None
-        lib().orc_traffic_step(self.h, _p(a), _p(obs), _p(rew), _p(rew64), _p(te), _p(tr), _p(fin))
-        self.last_reward64 = rew64
-        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
-
-    def rollout(self, k, a_seed, t0=0, env0=0, want_obs=True):
-        obs = np.zeros((self.n, self.obs_dim), np.float32) if want_obs else None
-        rs = np.zeros(self.n, np.float64)
-        dc = np.zeros(self.n, np.int32)
-        lib().orc_traffic_rollout(self.h, k, a_seed, t0, env0, _p(obs), _p(rs), _p(dc))
-        return obs, rs, dc
+    def _act_shape(self):
+        return (self.ni,)
 
     def info(self, field, idx=0):
         out = np.zeros(self.n, np.int32)
@@ -470,58 +382,9 @@ PARKING_INFO = {"timestep": 0, "total_customers": 1, "rejected": 2, "satisfied":
                 "price_changes_this_hour": 6, "zone_occupied": 7, "price_level": 8, "episodes": 9, "needs_reset": 10}
 
 
-class _SimpleOracle(_EpisodeStats):
-    """Shared ctypes plumbing for the small discrete-action envs (int32 action per env, float32 obs)."""
-    _name = None
-    _obs = None
-    _nact = None
-    _adim = 1
-
-    def __init__(self, n, mode=SAME_STEP, max_steps=None):
-        self.n, self.mode = int(n), int(mode)
-        self.h = getattr(lib(), f"orc_{self._name}_create")(self.n, self.mode)
-        if not self.h:
-            raise ValueError("create failed")
-        if max_steps is not None:                          # the env type's time limit (episode_minutes, max_timesteps, ...)
-            getattr(lib(), f"orc_{self._name}_set_max_steps")(self.h, int(max_steps))
-
-    def __del__(self):
-        if getattr(self, "h", None) and lib is not None:          # (module globals are None at interpreter shutdown)
-            getattr(lib(), f"orc_{self._name}_destroy")(self.h)
-            self.h = None
-
-    def seed(self, seeds):
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        assert seeds.shape == (self.n,)
-        getattr(lib(), f"orc_{self._name}_seed")(self.h, _p(seeds))
-
-    def reset(self, mask=None):
-        obs = np.zeros((self.n, self._obs), np.float32)
-        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-        getattr(lib(), f"orc_{self._name}_reset")(self.h, _p(m), _p(obs))
-        return obs
-
-    def step(self, actions, want_final=False):
-        a = np.ascontiguousarray(actions, dtype=np.int32)
-        assert a.shape == ((self.n,) if self._adim == 1 else (self.n, self._adim))
-        obs = np.zeros((self.n, self._obs), np.float32)
-        rew = np.zeros(self.n, np.float32); rew64 = np.zeros(self.n, np.float64)
-        te = np.zeros(self.n, np.uint8); tr = np.zeros(self.n, np.uint8)
-        fin = np.zeros_like(obs) if want_final else None
-        getattr(lib(), f"orc_{self._name}_step")(self.h, _p(a), _p(obs), _p(rew), _p(rew64), _p(te), _p(tr), _p(fin))
-        self.last_reward64 = rew64
-        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
-
-    def rollout(self, k, a_seed, t0=0, env0=0, want_obs=True):
-        obs = np.zeros((self.n, self._obs), np.float32) if want_obs else None
-        rs = np.zeros(self.n, np.float64); dc = np.zeros(self.n, np.int32)
-        getattr(lib(), f"orc_{self._name}_rollout")(self.h, k, a_seed, t0, env0, _p(obs), _p(rs), _p(dc))
-        return obs, rs, dc
-
-
-class ParkingOracle(_SimpleOracle):
+class ParkingOracle(_Oracle):
     """Batch of independent SmartParkingEnv restatements (oracle/orc_parking.c)."""
-    _name, _obs, _nact = "parking", PARKING_OBS, 8
+    _name, _obs = "parking", PARKING_OBS
 
     def info(self, field, idx=0):
         out = np.zeros(self.n, np.int32)
@@ -539,7 +402,7 @@ CLIMATE_INFO = {"room_temp": 0, "outside_temp": 1, "ac_setting": 2, "energy_usag
                 "step": 6, "comfort_time": 7, "episodes": 8, "needs_reset": 9}
 
 
-class ClimateOracle(_SimpleOracle):
+class ClimateOracle(_Oracle):
     """Batch of independent SmartClimateEnv restatements (oracle/orc_climate.c).  max_occupancy / episode_minutes (= max_steps) are the
     reference constructor's arguments (smartclimate/env.py:16-28)."""
     _name, _obs = "climate", CLIMATE_OBS
@@ -553,13 +416,7 @@ class ClimateOracle(_SimpleOracle):
         ac = np.ascontiguousarray(ac_temp, dtype=np.float32).reshape(self.n)
         li = np.ascontiguousarray(lights, dtype=np.int8)
         assert li.shape == (self.n, 4)
-        obs = np.zeros((self.n, self._obs), np.float32)
-        rew = np.zeros(self.n, np.float32); rew64 = np.zeros(self.n, np.float64)
-        te = np.zeros(self.n, np.uint8); tr = np.zeros(self.n, np.uint8)
-        fin = np.zeros_like(obs) if want_final else None
-        lib().orc_climate_step(self.h, _p(ac), _p(li), _p(obs), _p(rew), _p(rew64), _p(te), _p(tr), _p(fin))
-        self.last_reward64 = rew64
-        return (obs, rew, te, tr, fin) if want_final else (obs, rew, te, tr)
+        return self._step((ac, li), want_final)
 
     def info(self, field):
         out = np.zeros(self.n, np.float64)
@@ -578,9 +435,12 @@ FLEET_INFO = {"timestep": 0, "missed_deadlines": 1, "completed_deliveries": 2, "
               "total_reward": 5, "episodes": 6, "needs_reset": 7, "fuel0": 8, "fuel1": 9, "fuel2": 10}
 
 
-class FleetOracle(_SimpleOracle):
+class FleetOracle(_Oracle):
     """Batch of independent FleetManagementEnv restatements (oracle/orc_fleet.c); actions int32 (n, 3)."""
-    _name, _obs, _nact, _adim = "fleet", FLEET_OBS, 8, 3
+    _name, _obs = "fleet", FLEET_OBS
+
+    def _act_shape(self):
+        return (3,)
 
     def info(self, field):
         out = np.zeros(self.n, np.float64)
@@ -594,9 +454,9 @@ MANUFACTURING_INFO = {"raw_material": 0, "energy_consumption": 1, "total_reward"
                       "timestep": 11, "episodes": 12, "needs_reset": 13, "overflow": 14}
 
 
-class ManufacturingOracle(_SimpleOracle):
+class ManufacturingOracle(_Oracle):
     """Batch of independent SmartManufacturingEnv restatements (oracle/orc_manufacturing.c); Discrete(25) actions."""
-    _name, _obs, _nact = "manufacturing", MANUFACTURING_OBS, 25
+    _name, _obs = "manufacturing", MANUFACTURING_OBS
 
     def info(self, field):
         out = np.zeros(self.n, np.float64)
@@ -610,9 +470,9 @@ HOSPITAL_INFO = {"deaths": 0, "patients_treated": 1, "total_wait_time": 2, "time
                  "occupied_beds": 13, "medicine_total": 14, "episodes": 15, "needs_reset": 16, "overflow": 17}
 
 
-class HospitalOracle(_SimpleOracle):
+class HospitalOracle(_Oracle):
     """Batch of independent HospitalManagementEnv restatements (oracle/orc_hospital.c); Discrete(35) actions."""
-    _name, _obs, _nact = "hospital", HOSPITAL_OBS, 35
+    _name, _obs = "hospital", HOSPITAL_OBS
 
     def info(self, field):
         out = np.zeros(self.n, np.float64)

@@ -6,6 +6,7 @@
  * Generator: family D — a private np.random.default_rng(seed) per env (PCG64; uniform, Lemire integers on
  * buffered 32-bit draws, ziggurat normal, choice(p) = cdf + random() + searchsorted(right)).
  * Parity pins: tests/golden/climate_hash.npz + climate_kat.json (KAT-K1) — tests/test_oracle_climate.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <math.h>
 #include <stdint.h>
@@ -83,52 +84,6 @@ static int env_step(const orc_climate *h, climate_env *e, float ac_in, const int
     return e->step >= h->episode_minutes;
 }
 
-orc_climate *orc_climate_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_climate *h = (orc_climate *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_occupancy = 8; h->episode_minutes = 1440;
-    h->e = (climate_env *)calloc((size_t)n, sizeof(climate_env));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) orc_pcg_seed(&h->e[i].g, (uint64_t)i);
-    return h;
-}
-void orc_climate_destroy(orc_climate *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-/* reset(seed=s): self.rng = np.random.default_rng(s) */
-void orc_climate_seed(orc_climate *h, const uint64_t *seeds) { for (int64_t i = 0; i < h->n; ++i) orc_pcg_seed(&h->e[i].g, seeds[i]); }
-
-void orc_climate_reset(orc_climate *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(h, &h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(&h->e[i], obs + i * COBS);
-    }
-}
-
-void orc_climate_step(orc_climate *h, const float *ac_temp, const int8_t *lights, float *obs, float *reward, double *reward64,
-                      uint8_t *terminated, uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        climate_env *e = &h->e[i];
-        float *o = obs + i * COBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(h, e); eps_clear(&h->eps, i); } write_obs(e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int term = env_step(h, e, ac_temp[i], lights + 4 * i, &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)term; truncated[i] = 0;
-        if (term) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (term && h->mode == 1) {
-            if (final_obs) write_obs(e, final_obs + i * COBS);
-            { env_reset(h, e); eps_clear(&h->eps, i); } write_obs(e, o);
-        } else {
-            write_obs(e, o);
-            if (term && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
 /* hash actions: ac = float32(16 + 16*(hash(j=0) >> 40) / 2^24), lights[k] = hash(n=2, j=1+k) */
 void orc_climate_hash_action(uint64_t a_seed, uint64_t env, uint64_t t, float *ac, int8_t *lights) {
     uint64_t u = orc_mix64(orc_mix64(a_seed + env * 0x9E3779B97F4A7C15ull) + t * 0xD1342543DE82EF95ull + 0) >> 40;
@@ -136,26 +91,29 @@ void orc_climate_hash_action(uint64_t a_seed, uint64_t env, uint64_t t, float *a
     for (int k = 0; k < 4; ++k) lights[k] = (int8_t)orc_hash_action(a_seed, env, t, 2, (uint32_t)(1 + k));
 }
 
-void orc_climate_rollout(orc_climate *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs,
-                         double *reward_sum, int32_t *done_count) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        climate_env *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(h, e); eps_clear(&h->eps, i); } continue; }
-            float ac; int8_t li[4];
-            orc_climate_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), &ac, li);
-            double r;
-            int term = env_step(h, e, ac, li, &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (term) { ++dc; e->episodes += 1; eps_done(&h->eps, i); if (h->mode == 1) { env_reset(h, e); eps_clear(&h->eps, i); } else if (h->mode == 0) e->needs_reset = 1; }
-        }
-        if (obs) write_obs(e, obs + i * COBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
+/* rollout() does not assemble per-step observations */
+static inline int hash_step(orc_climate *h, climate_env *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    float ac; int8_t li[4];
+    orc_climate_hash_action(a_seed, env, t, &ac, li);
+    return env_step(h, e, ac, li, r);
+}
+#define ORC_NAME climate
+#define ORC_ENV climate_env
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) COBS
+#define ORC_MAX_STEPS(h) (h)->episode_minutes
+/* reset(seed=s): self.rng = np.random.default_rng(s) */
+#define ORC_SEED(e, s) orc_pcg_seed(&(e)->g, s)
+#define ORC_RESET(h, e) env_reset(h, e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(e, o)
+#define ORC_STEP_PARAMS const float *ac_temp, const int8_t *lights
+#define ORC_STEP(h, e, i, r) env_step(h, e, ac_temp[i], lights + 4 * (i), r)
+#include "orc_batch.h"
+
+orc_climate *orc_climate_create(int64_t n, int mode) {
+    orc_climate *h = batch_create(n, mode);
+    if (h) { h->max_occupancy = 8; h->episode_minutes = 1440; }
+    return h;
 }
 
 /* float64 fields: 0 room_temp 1 outside_temp 2 ac_setting 3 energy_usage 4 total_reward 5 num_people 6 step
@@ -173,12 +131,6 @@ void orc_climate_info(const orc_climate *h, int field, double *out) {
     }
 }
 
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_climate_set_max_steps(orc_climate *h, int v) { h->episode_minutes = v; }
 /* SmartClimateEnv(max_occupancy=...) (env.py:18,26): bounds the reset draw integers(0, max_occupancy + 1) (:50) and the clip in
  * update_occupancy (utils.py:21).  Call right after create. */
 void orc_climate_set_max_occupancy(orc_climate *h, int v) { h->max_occupancy = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_climate_episode_stats(const orc_climate *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

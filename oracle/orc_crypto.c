@@ -18,6 +18,7 @@
  * float32, so `amount`, `fee` and — after a buy — `self.cash` are np.float32 until the next sell makes
  * cash np.float64 (after which amounts are float64 too).  `cash_kind` tracks that; under NumPy 1.x
  * the same code computes everything in float64.  Discrete actions (the BASELINE config) are float64 only.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <math.h>
 #include <stdint.h>
@@ -267,22 +268,48 @@ static int env_step(const orc_crypto *h, crypto_env *e, int a_disc, const float 
     return e->step >= h->c.max_steps || pv <= 0 || pv >= h->c.initial_balance * 10; /* :382-386 */
 }
 
+/* step(): actions are int32 [n] (discrete, 0..4; step() returns the number of invalid ones) or float32 [n,2] (continuous) */
+static inline int step_action(orc_crypto *h, crypto_env *e, const void *actions, int64_t i, double *r) {
+    int term = h->c.continuous ? env_step(h, e, 0, (const float *)actions + 2 * i, r) : env_step(h, e, ((const int32_t *)actions)[i], NULL, r);
+    e->last_reward = *r;
+    return term;
+}
+/* rollout(): hash actions (discrete: hash mod 5; continuous: the top 24 bits of j = 0, 1 scaled to [-1, 1)).  Observations are
+ * still assembled every step (that is where the reference spends its time) unless obs == NULL. */
+static inline int hash_step(orc_crypto *h, crypto_env *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    int a = (int)orc_hash_action(a_seed, env, t, 5, 0);
+    float ac[2] = {0, 0};
+    if (h->c.continuous)
+        for (int j = 0; j < 2; ++j)
+            ac[j] = (float)((double)(orc_mix64(orc_mix64(a_seed + env * 0x9E3779B97F4A7C15ull) + t * 0xD1342543DE82EF95ull + (uint64_t)j) >> 40) / 8388608.0 - 1.0);
+    return env_step(h, e, a, ac, r);
+}
+#define ORC_NAME crypto
+#define ORC_ENV crypto_env
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) CRYPTO_OBS
+#define ORC_MAX_STEPS(h) (h)->c.max_steps
+/* reset(seed=s): random.seed(s); np.random.seed(s)  (:305-307).  The MarketSimulator is NOT re-created. */
+#define ORC_SEED(e, s) do { orc_py_seed(&(e)->P, s); orc_np_seed(&(e)->L, (uint32_t)(s)); } while (0)
+#define ORC_RESET(h, e) env_reset(h, e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(h, e, o)
+#define ORC_STEP_PARAMS const void *actions
+#define ORC_STEP(h, e, i, r) step_action(h, e, actions, i, r)
+#define ORC_ACTION_OK(h, i) ((h)->c.continuous || (((const int32_t *)actions)[i] >= 0 && ((const int32_t *)actions)[i] <= 4))
+#define ORC_SCRATCH CRYPTO_OBS
+#include "orc_batch.h"
+
 orc_crypto *orc_crypto_create(int64_t n, int continuous, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_crypto *h = (orc_crypto *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode;
+    orc_crypto *h = batch_create(n, mode);
+    if (!h) return NULL;
     h->c = (crypto_cfg){10000.0, 0.001, 0.0005, 100.0, 100000.0, 0.02, 0.1, 1000, continuous};   /* :28-38, :278 */
-    h->e = (crypto_env *)calloc((size_t)n, sizeof(crypto_env));
-    eps_init(&h->eps, n);
     for (int64_t i = 0; i < n; ++i) {
         crypto_env *e = &h->e[i];
-        orc_py_seed(&e->P, (uint64_t)i); orc_np_seed(&e->L, (uint32_t)i);
         e->regime = SIDEWAYS; e->trend_strength = 0.0; e->psych = 0.5;              /* MarketSimulator.__init__, :125-130 */
         e->cash = h->c.initial_balance;
     }
     return h;
 }
-void orc_crypto_destroy(orc_crypto *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
 
 /* CryptoTradingEnv(config=TradingConfig(...)) (:28-38, :252): cfg = {initial_balance, trading_fee_rate, slippage_rate, min_price,
  * max_price, volatility_base, market_psychology_factor}; call right after create (history_length stays 50).  __init__ sets
@@ -291,92 +318,6 @@ void orc_crypto_set_config(orc_crypto *h, const double *cfg) {
     h->c.initial_balance = cfg[0]; h->c.fee_rate = cfg[1]; h->c.slippage_rate = cfg[2]; h->c.min_price = cfg[3];
     h->c.max_price = cfg[4]; h->c.volatility_base = cfg[5]; h->c.psychology_factor = cfg[6];
     for (int64_t i = 0; i < h->n; ++i) h->e[i].cash = h->c.initial_balance;
-}
-
-/* reset(seed=s): random.seed(s); np.random.seed(s)  (:305-307).  The MarketSimulator is NOT re-created. */
-void orc_crypto_seed(orc_crypto *h, const uint64_t *seeds) {
-    for (int64_t i = 0; i < h->n; ++i) { orc_py_seed(&h->e[i].P, seeds[i]); orc_np_seed(&h->e[i].L, (uint32_t)seeds[i]); }
-}
-
-void orc_crypto_reset(orc_crypto *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(h, &h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(h, &h->e[i], obs + i * CRYPTO_OBS);
-    }
-}
-
-/* actions: int32 [n] (discrete) or float32 [n,2] (continuous).  reward64 (nullable) gets the float64 reward. */
-int orc_crypto_step(orc_crypto *h, const void *actions, float *obs, float *reward, double *reward64,
-                    uint8_t *terminated, uint8_t *truncated, float *final_obs) {
-    int bad = 0;
-    for (int64_t i = 0; i < h->n; ++i) {
-        crypto_env *e = &h->e[i];
-        float *o = obs + i * CRYPTO_OBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(h, e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        int a = 0;
-        const float *ac = NULL;
-        if (h->c.continuous) ac = (const float *)actions + 2 * i;
-        else {
-            a = ((const int32_t *)actions)[i];
-            if (a < 0 || a > 4) { ++bad; write_obs(h, e, o); reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0; continue; }
-        }
-        double r;
-        int term = env_step(h, e, a, ac, &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)term; truncated[i] = 0;
-        e->last_reward = r;
-        if (term) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (term && h->mode == 1) {
-            if (final_obs) write_obs(h, e, final_obs + i * CRYPTO_OBS);
-            { env_reset(h, e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-        } else {
-            write_obs(h, e, o);
-            if (term && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-    return bad;
-}
-
-/* K fused steps with hash actions (discrete: hash mod 5); obs of the last step; used by the
- * cpu_baseline leg and to check the device rollout.  Observations are still assembled every step
- * (that is where the reference spends its time) unless obs == NULL. */
-void orc_crypto_rollout(orc_crypto *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs,
-                        double *reward_sum, int32_t *done_count) {
-    float scratch[CRYPTO_OBS];
-    for (int64_t i = 0; i < h->n; ++i) {
-        crypto_env *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(h, e); eps_clear(&h->eps, i); } continue; }
-            int a = (int)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 5, 0);
-            float ac[2] = {0, 0};
-            if (h->c.continuous) {
-                ac[0] = (float)((double)(orc_mix64(orc_mix64(a_seed + (uint64_t)(env0 + i) * 0x9E3779B97F4A7C15ull) + (uint64_t)(t0 + t) * 0xD1342543DE82EF95ull + 0) >> 40) / 8388608.0 - 1.0);
-                ac[1] = (float)((double)(orc_mix64(orc_mix64(a_seed + (uint64_t)(env0 + i) * 0x9E3779B97F4A7C15ull) + (uint64_t)(t0 + t) * 0xD1342543DE82EF95ull + 1) >> 40) / 8388608.0 - 1.0);
-            }
-            double r;
-            int term = env_step(h, e, a, ac, &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (obs) write_obs(h, e, scratch);
-            if (term) {
-                ++dc; e->episodes += 1; eps_done(&h->eps, i);
-                if (h->mode == 1) { env_reset(h, e); eps_clear(&h->eps, i); }
-                else if (h->mode == 0) e->needs_reset = 1;
-            }
-        }
-        if (obs) write_obs(h, e, obs + i * CRYPTO_OBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
 }
 
 /* field: 0 portfolio_value 1 cash 2 holdings 3 current_price 4 market_psychology 5 regime 6 step 7 trend_strength
@@ -438,10 +379,3 @@ void orc_crypto_set_state(orc_crypto *h, const void *buf) {
         memcpy(e->hist, p + 96 + 2 * 2496, HLEN * 40);
     }
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_crypto_set_max_steps(orc_crypto *h, int v) { h->c.max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_crypto_episode_stats(const orc_crypto *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

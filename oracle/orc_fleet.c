@@ -13,6 +13,7 @@
  * reference.  Quirks kept: `missed_deadlines` grows every step for every overdue urgent delivery (:530-535);
  * positions are clamped so the "invalid move" branch is dead (:331-347).
  * Parity pins: tests/golden/fleet_*.npz + fleet_kat.json (KAT-F1) — tests/test_oracle_fleet.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -189,72 +190,30 @@ static int env_step(const orc_fleet *h, fleet_env *e, const int32_t *a, double *
     return (term ? 1 : 0) | (e->timestep >= h->max_steps ? 2 : 0);
 }
 
+/* step(): actions int32 [n, 3].  rollout(): vehicle j's action is hash(.., 8, j); no per-step observations. */
+static inline int hash_step(orc_fleet *h, fleet_env *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    int32_t a[3];
+    for (int j = 0; j < 3; ++j) a[j] = (int32_t)orc_hash_action(a_seed, env, t, 8, (uint32_t)j);
+    return env_step(h, e, a, r);
+}
+#define ORC_NAME fleet
+#define ORC_ENV fleet_env
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) FOBS
+#define ORC_MAX_STEPS(h) (h)->max_steps
+#define ORC_SEED(e, s) do { orc_py_seed(&(e)->P, s); orc_np_seed(&(e)->L, (uint32_t)(s)); } while (0)
+#define ORC_RESET(h, e) env_reset(h, e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions + 3 * (i), r)
+#include "orc_batch.h"
+
 orc_fleet *orc_fleet_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_fleet *h = (orc_fleet *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_steps = 800;
-    h->e = (fleet_env *)calloc((size_t)n, sizeof(fleet_env));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) { orc_py_seed(&h->e[i].P, (uint64_t)i); orc_np_seed(&h->e[i].L, (uint32_t)i); h->e[i].weather = 1.0; }
+    orc_fleet *h = batch_create(n, mode);
+    if (!h) return NULL;
+    h->max_steps = 800;
+    for (int64_t i = 0; i < n; ++i) h->e[i].weather = 1.0;
     return h;
-}
-void orc_fleet_destroy(orc_fleet *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-void orc_fleet_seed(orc_fleet *h, const uint64_t *seeds) {
-    for (int64_t i = 0; i < h->n; ++i) { orc_py_seed(&h->e[i].P, seeds[i]); orc_np_seed(&h->e[i].L, (uint32_t)seeds[i]); }
-}
-void orc_fleet_reset(orc_fleet *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(h, &h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(&h->e[i], obs + i * FOBS);
-    }
-}
-
-void orc_fleet_step(orc_fleet *h, const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *terminated,
-                    uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        fleet_env *e = &h->e[i];
-        float *o = obs + i * FOBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(h, e); eps_clear(&h->eps, i); } write_obs(e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int f = env_step(h, e, actions + 3 * i, &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)(f & 1); truncated[i] = (uint8_t)((f >> 1) & 1);
-        if (f) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (f && h->mode == 1) {
-            if (final_obs) write_obs(e, final_obs + i * FOBS);
-            { env_reset(h, e); eps_clear(&h->eps, i); } write_obs(e, o);
-        } else {
-            write_obs(e, o);
-            if (f && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
-void orc_fleet_rollout(orc_fleet *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs, double *reward_sum,
-                       int32_t *done_count) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        fleet_env *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(h, e); eps_clear(&h->eps, i); } continue; }
-            int32_t a[3];
-            for (int j = 0; j < 3; ++j) a[j] = (int32_t)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 8, (uint32_t)j);
-            double r;
-            int f = env_step(h, e, a, &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (f) { ++dc; e->episodes += 1; eps_done(&h->eps, i); if (h->mode == 1) { env_reset(h, e); eps_clear(&h->eps, i); } else if (h->mode == 0) e->needs_reset = 1; }
-        }
-        if (obs) write_obs(e, obs + i * FOBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
 }
 
 /* float64 fields: 0 timestep 1 missed_deadlines 2 completed_deliveries 3 num_requests 4 weather_effect 5 total_reward
@@ -271,10 +230,3 @@ void orc_fleet_info(const orc_fleet *h, int field, double *out) {
         out[i] = v;
     }
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_fleet_set_max_steps(orc_fleet *h, int v) { h->max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_fleet_episode_stats(const orc_fleet *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

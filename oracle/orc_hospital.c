@@ -10,6 +10,7 @@
  * The queues are kept as plain arrays of patient records in deque order (this file favours the obvious data structure; the
  * device kernel uses per-severity sub-queues and is checked against this).
  * Parity pins: tests/golden/hospital_{hash,surge}.npz + hospital_kat.json (KAT-H1) — tests/test_oracle_hospital.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <math.h>
 #include <stdint.h>
@@ -283,69 +284,26 @@ static int env_step(const orc_hospital *h, henv *e, int action, double *reward_o
     return term | ((e->time >= h->max_steps) << 1);
 }
 
+/* rollout(): hash mod 35; no per-step observations */
+static inline int hash_step(orc_hospital *h, henv *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    return env_step(h, e, (int)orc_hash_action(a_seed, env, t, 35, 0), r);
+}
+#define ORC_NAME hospital
+#define ORC_ENV henv
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) HOBS
+#define ORC_MAX_STEPS(h) (h)->max_steps
+#define ORC_SEED(e, s) orc_py_seed(&(e)->P, s)
+#define ORC_RESET(h, e) env_reset(e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(h, e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions[i], r)
+#include "orc_batch.h"
+
 orc_hospital *orc_hospital_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_hospital *h = (orc_hospital *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_steps = 1440;
-    h->e = (henv *)calloc((size_t)n, sizeof(henv));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) orc_py_seed(&h->e[i].P, (uint64_t)i);
+    orc_hospital *h = batch_create(n, mode);
+    if (h) h->max_steps = 1440;
     return h;
-}
-void orc_hospital_destroy(orc_hospital *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-void orc_hospital_seed(orc_hospital *h, const uint64_t *seeds) { for (int64_t i = 0; i < h->n; ++i) orc_py_seed(&h->e[i].P, seeds[i]); }
-
-void orc_hospital_reset(orc_hospital *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(&h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(h, &h->e[i], obs + i * HOBS);
-    }
-}
-
-void orc_hospital_step(orc_hospital *h, const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *terminated,
-                       uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        henv *e = &h->e[i];
-        float *o = obs + i * HOBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(h, e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int f = env_step(h, e, actions[i], &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)(f & 1); truncated[i] = (uint8_t)(f >> 1);
-        if (f) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (f && h->mode == 1) {
-            if (final_obs) write_obs(h, e, final_obs + i * HOBS);
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(h, e, o);
-        } else {
-            write_obs(h, e, o);
-            if (f && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
-void orc_hospital_rollout(orc_hospital *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs, double *reward_sum,
-                          int32_t *done_count) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        henv *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(e); eps_clear(&h->eps, i); } continue; }
-            double r;
-            int f = env_step(h, e, (int)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 35, 0), &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (f) { ++dc; e->episodes += 1; eps_done(&h->eps, i); if (h->mode == 1) { env_reset(e); eps_clear(&h->eps, i); } else if (h->mode == 0) e->needs_reset = 1; }
-        }
-        if (obs) write_obs(h, e, obs + i * HOBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
 }
 
 /* float64 fields: 0 deaths 1 patients_treated 2 total_wait_time 3 time 4 outbreak 5 mass_casualty 6 next_patient_id
@@ -366,10 +324,3 @@ void orc_hospital_info(const orc_hospital *h, int field, double *out) {
         out[i] = v;
     }
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_hospital_set_max_steps(orc_hospital *h, int v) { h->max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_hospital_episode_stats(const orc_hospital *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

@@ -9,6 +9,7 @@
  * 32-bit draws, uniform/random = 53-bit doubles).  np.mean = NumPy pairwise summation / n, restated below for any n.
  * Parity pins: tests/golden/manufacturing_{hash,biased,typea}.npz + manufacturing_kat.json (KAT-M1) —
  * tests/test_oracle_manufacturing.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <math.h>
 #include <stdint.h>
@@ -232,70 +233,29 @@ static int env_step(const orc_manufacturing *h, menv *e, int action, double *rew
     return term | (trunc << 1);
 }
 
-orc_manufacturing *orc_manufacturing_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_manufacturing *h = (orc_manufacturing *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_steps = 1500;
-    h->e = (menv *)calloc((size_t)n, sizeof(menv));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) { orc_pcg_seed(&h->e[i].g, (uint64_t)i); h->e[i].thr[0] = 0.70; h->e[i].thr[1] = 0.80; h->e[i].thr[2] = 0.85; h->e[i].raw = 250; }
-    return h;
+/* rollout(): hash mod 25; no per-step observations */
+static inline int hash_step(orc_manufacturing *h, menv *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    return env_step(h, e, (int)orc_hash_action(a_seed, env, t, 25, 0), r);
 }
-void orc_manufacturing_destroy(orc_manufacturing *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
+#define ORC_NAME manufacturing
+#define ORC_ENV menv
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) MOBS
+#define ORC_MAX_STEPS(h) (h)->max_steps
 /* reset(seed=s): self.np_random = Generator(PCG64(SeedSequence(s))) */
-void orc_manufacturing_seed(orc_manufacturing *h, const uint64_t *seeds) { for (int64_t i = 0; i < h->n; ++i) orc_pcg_seed(&h->e[i].g, seeds[i]); }
+#define ORC_SEED(e, s) orc_pcg_seed(&(e)->g, s)
+#define ORC_RESET(h, e) env_reset(e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions[i], r)
+#include "orc_batch.h"
 
-void orc_manufacturing_reset(orc_manufacturing *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(&h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(&h->e[i], obs + i * MOBS);
-    }
-}
-
-void orc_manufacturing_step(orc_manufacturing *h, const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *terminated,
-                            uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        menv *e = &h->e[i];
-        float *o = obs + i * MOBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int f = env_step(h, e, actions[i], &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)(f & 1); truncated[i] = (uint8_t)(f >> 1);
-        if (f) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (f && h->mode == 1) {
-            if (final_obs) write_obs(e, final_obs + i * MOBS);
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(e, o);
-        } else {
-            write_obs(e, o);
-            if (f && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
-void orc_manufacturing_rollout(orc_manufacturing *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs,
-                               double *reward_sum, int32_t *done_count) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        menv *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(e); eps_clear(&h->eps, i); } continue; }
-            double r;
-            int f = env_step(h, e, (int)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 25, 0), &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (f) { ++dc; e->episodes += 1; eps_done(&h->eps, i); if (h->mode == 1) { env_reset(e); eps_clear(&h->eps, i); } else if (h->mode == 0) e->needs_reset = 1; }
-        }
-        if (obs) write_obs(e, obs + i * MOBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
+orc_manufacturing *orc_manufacturing_create(int64_t n, int mode) {
+    orc_manufacturing *h = batch_create(n, mode);
+    if (!h) return NULL;
+    h->max_steps = 1500;
+    for (int64_t i = 0; i < n; ++i) { h->e[i].thr[0] = 0.70; h->e[i].thr[1] = 0.80; h->e[i].thr[2] = 0.85; h->e[i].raw = 250; }
+    return h;
 }
 
 /* float64 fields: 0 raw_material 1 energy 2 total_reward 3 in_system 4 completed 5 scrapped 6 product_ids 7 history_len
@@ -317,10 +277,3 @@ void orc_manufacturing_info(const orc_manufacturing *h, int field, double *out) 
         out[i] = v;
     }
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_manufacturing_set_max_steps(orc_manufacturing *h, int v) { h->max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_manufacturing_episode_stats(const orc_manufacturing *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

@@ -18,6 +18,7 @@
  * queue are dropped but counted; a failed assignment re-queues the customer at the BACK (parking_env.py:231-234).
  * Generator: family P = CPython global `random`, never seeded by the env (parking_env.py:81) — per-env stream.
  * Parity pins: tests/golden/parking_*.npz + parking_kat.json — checked by tests/test_oracle_parking.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -171,71 +172,29 @@ static int env_step(const orc_parking *h, parking_env *e, int a, double *reward)
     return e->t >= h->max_steps;
 }
 
+/* rollout(): hash mod 8; every step's observation is assembled */
+static inline int hash_step(orc_parking *h, parking_env *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    return env_step(h, e, (int)orc_hash_action(a_seed, env, t, 8, 0), r);
+}
+#define ORC_NAME parking
+#define ORC_ENV parking_env
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) POBS
+#define ORC_MAX_STEPS(h) (h)->max_steps
+#define ORC_SEED(e, s) orc_py_seed(&(e)->P, s)
+#define ORC_RESET(h, e) env_reset(e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions[i], r)
+#define ORC_SCRATCH POBS
+#include "orc_batch.h"
+
 orc_parking *orc_parking_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_parking *h = (orc_parking *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_steps = 1440;
-    h->e = (parking_env *)calloc((size_t)n, sizeof(parking_env));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) { orc_py_seed(&h->e[i].P, (uint64_t)i); { env_reset(&h->e[i]); eps_clear(&h->eps, i); } }
+    orc_parking *h = batch_create(n, mode);
+    if (!h) return NULL;
+    h->max_steps = 1440;
+    for (int64_t i = 0; i < n; ++i) batch_reset_env(h, &h->e[i], i);
     return h;
-}
-void orc_parking_destroy(orc_parking *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-void orc_parking_seed(orc_parking *h, const uint64_t *seeds) { for (int64_t i = 0; i < h->n; ++i) orc_py_seed(&h->e[i].P, seeds[i]); }
-
-void orc_parking_reset(orc_parking *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(&h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(&h->e[i], obs + i * POBS);
-    }
-}
-
-void orc_parking_step(orc_parking *h, const int32_t *actions, float *obs, float *reward, double *reward64,
-                      uint8_t *terminated, uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        parking_env *e = &h->e[i];
-        float *o = obs + i * POBS;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int term = env_step(h, e, actions[i], &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)term; truncated[i] = 0;
-        if (term) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (term && h->mode == 1) {
-            if (final_obs) write_obs(e, final_obs + i * POBS);
-            { env_reset(e); eps_clear(&h->eps, i); } write_obs(e, o);
-        } else {
-            write_obs(e, o);
-            if (term && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
-void orc_parking_rollout(orc_parking *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs,
-                         double *reward_sum, int32_t *done_count) {
-    float scratch[POBS];
-    for (int64_t i = 0; i < h->n; ++i) {
-        parking_env *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(e); eps_clear(&h->eps, i); } continue; }
-            double r;
-            int term = env_step(h, e, (int)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 8, 0), &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (obs) write_obs(e, scratch);
-            if (term) { ++dc; e->episodes += 1; eps_done(&h->eps, i); if (h->mode == 1) { env_reset(e); eps_clear(&h->eps, i); } else if (h->mode == 0) e->needs_reset = 1; }
-        }
-        if (obs) write_obs(e, obs + i * POBS);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
 }
 
 /* int fields: 0 timestep 1 total_customers 2 rejected 3 satisfied 4 total_wait_time 5 queue_length
@@ -264,10 +223,3 @@ void orc_parking_info(const orc_parking *h, int field, int idx, int32_t *out) {
 void orc_parking_info64(const orc_parking *h, int field, double *out) {
     for (int64_t i = 0; i < h->n; ++i) out[i] = field == 0 ? h->e[i].revenue : h->e[i].satisfaction_sum;
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_parking_set_max_steps(orc_parking *h, int v) { h->max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_parking_episode_stats(const orc_parking *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

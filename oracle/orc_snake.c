@@ -8,13 +8,7 @@
  * Parity pins: tests/golden/snake_*.npz + snake_kat.json (produced by tests/golden/gen/gen_snake.py
  * running the reference itself) — checked by tests/test_oracle_snake.py.
  *
- * Batch/auto-reset semantics are the build's own (the reference has no vector API); they mirror
- * include/cge_amd.h so the parity tests drive both sides with the same calls:
- *   mode 0 NEXT_STEP : a done env returns its terminal obs; the NEXT step() ignores the action,
- *                      resets it (no reseed, stream continues) and returns (reset obs, 0, 0, 0).
- *   mode 1 SAME_STEP : a done env is reset inside the same step(); obs = reset obs, the terminal
- *                      obs goes to final_obs (if not NULL).
- *   mode 2 DISABLED  : no reset at all; stepping a finished env does what the reference does.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -102,91 +96,30 @@ static int env_step(orc_snake *h, snake_env *e, int action, float *reward) {   /
     return e->steps >= h->max_steps;                                          /* :113-114 */
 }
 
+/* env i's private stream := CPython random.seed(seeds[i]).  step() returns the number of invalid actions (the reference raises
+ * ValueError, snake_env.py:69-70).  rollout() does not assemble per-step observations. */
+static inline int hash_step(orc_snake *h, snake_env *e, uint64_t a_seed, uint64_t env, uint64_t t, float *r) {
+    return env_step(h, e, (int)orc_hash_action(a_seed, env, t, 4, 0), r);
+}
+#define ORC_NAME snake
+#define ORC_ENV snake_env
+#define ORC_OBS_T int8_t
+#define ORC_OBS_LEN(h) ((h)->G * (h)->G)
+#define ORC_FLOAT_REWARD
+#define ORC_MAX_STEPS(h) (h)->max_steps
+#define ORC_SEED(e, s) orc_py_seed(&(e)->rng, s)
+#define ORC_RESET(h, e) env_reset(h, e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(h, e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_ACTION_OK(h, i) (actions[i] >= 0 && actions[i] <= 3)
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions[i], r)
+#include "orc_batch.h"
+
 orc_snake *orc_snake_create(int64_t n, int grid, int mode) {
-    if (n <= 0 || grid < 2 || grid > SNAKE_MAX_G || mode < 0 || mode > 2) return NULL;
-    orc_snake *h = (orc_snake *)calloc(1, sizeof(*h));
-    h->n = n; h->G = grid; h->mode = mode; h->max_steps = 1000;              /* :47 */
-    h->e = (snake_env *)calloc((size_t)n, sizeof(snake_env));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) orc_py_seed(&h->e[i].rng, (uint64_t)i);
+    if (grid < 2 || grid > SNAKE_MAX_G) return NULL;
+    orc_snake *h = batch_create(n, mode);
+    if (h) { h->G = grid; h->max_steps = 1000; }                             /* :47 */
     return h;
-}
-
-void orc_snake_destroy(orc_snake *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-
-/* env i's private stream := CPython random.seed(seeds[i]) */
-void orc_snake_seed(orc_snake *h, const uint64_t *seeds) {
-    for (int64_t i = 0; i < h->n; ++i) orc_py_seed(&h->e[i].rng, seeds[i]);
-}
-
-void orc_snake_reset(orc_snake *h, const uint8_t *mask, int8_t *obs) {
-    int cells = h->G * h->G;
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(h, &h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(h, &h->e[i], obs + i * cells);   /* every row is written, like the device ABI */
-    }
-}
-
-/* returns the number of invalid actions (reference raises ValueError, snake_env.py:69-70);
- * an env with an invalid action is left untouched. */
-int orc_snake_step(orc_snake *h, const int32_t *actions, int8_t *obs, float *reward,
-                   uint8_t *terminated, uint8_t *truncated, int8_t *final_obs) {
-    int cells = h->G * h->G, bad = 0;
-    for (int64_t i = 0; i < h->n; ++i) {
-        snake_env *e = &h->e[i];
-        int8_t *o = obs + i * cells;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(h, e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-            reward[i] = 0.0f; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        int a = actions[i];
-        if (a < 0 || a > 3) { ++bad; write_obs(h, e, o); reward[i] = 0.0f; terminated[i] = 0; truncated[i] = 0; continue; }
-        float r;
-        int term = env_step(h, e, a, &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = r; terminated[i] = (uint8_t)term; truncated[i] = 0;
-        if (term) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (term && h->mode == 1) {
-            if (final_obs) write_obs(h, e, final_obs + i * cells);
-            { env_reset(h, e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-        } else {
-            write_obs(h, e, o);
-            if (term && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-    return bad;
-}
-
-/* K fused steps with the shared counter-hash action source; obs of the LAST step is written,
- * per-env reward sums and done counts are accumulated (used as bench.py's cpu_baseline leg and
- * to check the device rollout entry point). */
-void orc_snake_rollout(orc_snake *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0,
-                       int8_t *obs, float *reward_sum, int32_t *done_count) {
-    int cells = h->G * h->G;
-    for (int64_t i = 0; i < h->n; ++i) {
-        snake_env *e = &h->e[i];
-        float rs = 0.0f;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(h, e); eps_clear(&h->eps, i); } continue; }
-            int a = (int)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 4, 0);
-            float r;
-            int term = env_step(h, e, a, &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (term) {
-                ++dc; e->episodes += 1; eps_done(&h->eps, i);
-                if (h->mode == 1) { env_reset(h, e); eps_clear(&h->eps, i); }
-                else if (h->mode == 0) e->needs_reset = 1;
-            }
-        }
-        if (obs) write_obs(h, e, obs + i * cells);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
 }
 
 /* field: 0 score, 1 snake_length, 2 steps, 3 direction, 4 food_r, 5 food_c, 6 board_full, 7 episodes,
@@ -254,9 +187,6 @@ void orc_snake_set_state(orc_snake *h, const void *buf) {
     }
 }
 
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_snake_set_max_steps(orc_snake *h, int v) { h->max_steps = v; }
 
 /* _render_rgb_array (snake_env.py:175-188): rgb[obs == 0] = (0,0,0), rgb[obs == 1] = (0,255,0), rgb[obs == 2] = (255,0,0) */
 void orc_snake_render_rgb(const orc_snake *h, uint8_t *rgb) {
@@ -268,6 +198,3 @@ void orc_snake_render_rgb(const orc_snake *h, uint8_t *rgb) {
         for (int c = 0; c < cells; ++c) { o[3 * c] = obs[c] == 2 ? 255 : 0; o[3 * c + 1] = obs[c] == 1 ? 255 : 0; o[3 * c + 2] = 0; }
     }
 }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_snake_episode_stats(const orc_snake *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }

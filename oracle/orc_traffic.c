@@ -18,6 +18,7 @@
  * vehicles that passed without reaching their destination stay in `self.vehicles` forever (only the count matters).
  * Generator: family P = CPython global `random`, one private stream per env, seeded by reset(seed=) (:145-146).
  * Parity pins: tests/golden/traffic_*.npz + traffic_kat.json — checked by tests/test_oracle_traffic.py.
+ * The batch driver (seed / reset / step / rollout, the autoreset modes, episode statistics) is orc_batch.h.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -185,14 +186,30 @@ static int env_step(const orc_traffic *h, traffic_env *e, const int32_t *a, doub
     return e->timestep >= h->max_steps;
 }
 
+/* step(): actions int32 [n, ni].  rollout(): action j of an env is hash(.., 3, j); every step's observation is assembled. */
+static inline int hash_step(orc_traffic *h, traffic_env *e, uint64_t a_seed, uint64_t env, uint64_t t, double *r) {
+    int32_t a[NI];
+    for (int j = 0; j < h->ni; ++j) a[j] = (int32_t)orc_hash_action(a_seed, env, t, 3, (uint32_t)j);
+    return env_step(h, e, a, r);
+}
+#define ORC_NAME traffic
+#define ORC_ENV traffic_env
+#define ORC_OBS_T float
+#define ORC_OBS_LEN(h) (h)->obs
+#define ORC_MAX_STEPS(h) (h)->max_steps
+#define ORC_SEED(e, s) orc_py_seed(&(e)->P, s)
+#define ORC_RESET(h, e) env_reset(e)
+#define ORC_WRITE_OBS(h, e, o) write_obs(h, e, o)
+#define ORC_STEP_PARAMS const int32_t *actions
+#define ORC_STEP(h, e, i, r) env_step(h, e, actions + (i) * (h)->ni, r)
+#define ORC_SCRATCH TOBS_MAX
+#include "orc_batch.h"
+
 orc_traffic *orc_traffic_create(int64_t n, int mode) {
-    if (n <= 0 || mode < 0 || mode > 2) return NULL;
-    orc_traffic *h = (orc_traffic *)calloc(1, sizeof(*h));
-    h->n = n; h->mode = mode; h->max_steps = 1000; h->max_vehicles = 50; h->spawn_rate = 0.3;
+    orc_traffic *h = batch_create(n, mode);
+    if (!h) return NULL;
+    h->max_steps = 1000; h->max_vehicles = 50; h->spawn_rate = 0.3;
     h->rows = 5; h->cols = 5; h->ni = 9; h->obs = 130;                   /* config.py:6-7 */
-    h->e = (traffic_env *)calloc((size_t)n, sizeof(traffic_env));
-    eps_init(&h->eps, n);
-    for (int64_t i = 0; i < n; ++i) orc_py_seed(&h->e[i].P, (uint64_t)i);
     return h;
 }
 /* TrafficManagementEnv(grid_size=(rows, cols), num_intersections, max_vehicles, spawn_rate) (environment.py:62-83); call
@@ -207,71 +224,6 @@ int orc_traffic_set_layout(orc_traffic *h, int rows, int cols, int num_intersect
 }
 int orc_traffic_obs_dim(const orc_traffic *h) { return h->obs; }
 int orc_traffic_num_intersections(const orc_traffic *h) { return h->ni; }
-void orc_traffic_destroy(orc_traffic *h) { if (h) { free(h->e); eps_free(&h->eps); free(h); } }
-void orc_traffic_seed(orc_traffic *h, const uint64_t *seeds) { for (int64_t i = 0; i < h->n; ++i) orc_py_seed(&h->e[i].P, seeds[i]); }
-
-void orc_traffic_reset(orc_traffic *h, const uint8_t *mask, float *obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!mask || mask[i]) { env_reset(&h->e[i]); eps_clear(&h->eps, i); }
-        if (obs) write_obs(h, &h->e[i], obs + i * h->obs);
-    }
-}
-
-void orc_traffic_step(orc_traffic *h, const int32_t *actions, float *obs, float *reward, double *reward64,
-                      uint8_t *terminated, uint8_t *truncated, float *final_obs) {
-    for (int64_t i = 0; i < h->n; ++i) {
-        traffic_env *e = &h->e[i];
-        float *o = obs + i * h->obs;
-        if (h->mode == 0 && e->needs_reset) {
-            { env_reset(e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-            reward[i] = 0.0f; if (reward64) reward64[i] = 0.0; terminated[i] = 0; truncated[i] = 0;
-            continue;
-        }
-        double r;
-        int term = env_step(h, e, actions + i * h->ni, &r);
-        eps_add(&h->eps, i, (double)r);
-        reward[i] = (float)r; if (reward64) reward64[i] = r;
-        terminated[i] = (uint8_t)term; truncated[i] = 0;
-        if (term) { e->episodes += 1; eps_done(&h->eps, i); }
-        if (term && h->mode == 1) {
-            if (final_obs) write_obs(h, e, final_obs + i * h->obs);
-            { env_reset(e); eps_clear(&h->eps, i); }
-            write_obs(h, e, o);
-        } else {
-            write_obs(h, e, o);
-            if (term && h->mode == 0) e->needs_reset = 1;
-        }
-    }
-}
-
-void orc_traffic_rollout(orc_traffic *h, int k_steps, uint64_t a_seed, int64_t t0, int64_t env0, float *obs,
-                         double *reward_sum, int32_t *done_count) {
-    float scratch[TOBS_MAX];
-    for (int64_t i = 0; i < h->n; ++i) {
-        traffic_env *e = &h->e[i];
-        double rs = 0.0;
-        int dc = 0;
-        for (int t = 0; t < k_steps; ++t) {
-            if (h->mode == 0 && e->needs_reset) { { env_reset(e); eps_clear(&h->eps, i); } continue; }
-            int32_t a[NI];
-            for (int j = 0; j < h->ni; ++j) a[j] = (int32_t)orc_hash_action(a_seed, (uint64_t)(env0 + i), (uint64_t)(t0 + t), 3, (uint32_t)j);
-            double r;
-            int term = env_step(h, e, a, &r);
-            eps_add(&h->eps, i, (double)r);
-            rs += r;
-            if (obs) write_obs(h, e, scratch);
-            if (term) {
-                ++dc; e->episodes += 1; eps_done(&h->eps, i);
-                if (h->mode == 1) { env_reset(e); eps_clear(&h->eps, i); }
-                else if (h->mode == 0) e->needs_reset = 1;
-            }
-        }
-        if (obs) write_obs(h, e, obs + i * h->obs);
-        if (reward_sum) reward_sum[i] = rs;
-        if (done_count) done_count[i] = dc;
-    }
-}
 
 /* field: 0 timestep 1 num_vehicles 2 light_phase[idx] 3 light_timer[idx] 4 vehicles_passed[idx]
  *        5 total_waiting_time[idx] 6 queue_len[idx<36] 7 queue_dest[idx] 8 queue_wait[idx] 9 episodes 10 needs_reset */
@@ -331,10 +283,3 @@ void orc_traffic_set_state(orc_traffic *h, const void *buf) {
         memcpy(e->P.mt, w + 16 * ni, 2496);
     }
 }
-
-/* Time-limit override for the short-horizon parity tests (the reference's limit is a constructor constant /
- * config value; the device ABI takes it in its config struct).  Call before reset(). */
-void orc_traffic_set_max_steps(orc_traffic *h, int v) { h->max_steps = v; }
-
-/* return and length of each env's last finished episode (orc_epstats.h) */
-void orc_traffic_episode_stats(const orc_traffic *h, double *ret, int32_t *len) { eps_get(&h->eps, h->n, ret, len); }
