@@ -53,6 +53,7 @@ struct HandleBase {
     }
     uint32_t snap_extra() const { return 0u; }       // host-side state a snapshot carries in its header (fleet has its own pair)
     void set_snap_extra(uint32_t v) { (void)v; }
+    int record_prologue(const char *who) { (void)who; return CGE_OK; }   // get_records / set_records: nothing to read per call (crypto has its own)
 
     int fail(int status, const char *what, hipError_t e = hipSuccess) {
         char buf[512];
@@ -308,6 +309,113 @@ inline bool mt_export_cpython(const uint32_t *w, uint32_t pos, uint32_t pretw, u
     *idx = (int32_t)pos;
     return true;
 }
+
+// CPython layout (624 words, index) -> device stream: the block with its 16 mirror words (624..639 repeat 0..15, cge_device.hpp) and
+// the cursor.  Every word from the index on is generated but unconsumed, so the whole generation is ready (mark 624); index 624
+// means "regenerate at the next draw": cursor 0 with nothing ready.
+inline void mt_import_cpython(const uint32_t *words624, int32_t index, uint32_t *block640, uint32_t *pos, uint32_t *pretw) {
+    memcpy(block640, words624, 624 * 4);
+    memcpy(block640 + 624, block640, 16 * 4);
+    const bool regenerate = index >= 624;
+    *pos = regenerate ? 0u : (uint32_t)index;
+    *pretw = regenerate ? 0u : 624u;
+}
+
+// Canonical per-env records (get_state / set_state), for the env types that have them.  The driver below owns the null checks, the
+// device guard, the stream synchronisation, the rounds of STATE_CHUNK envs, the host staging (sized by the chunk, never by n), the
+// copies and the error return.  A handle H supplies what is its own:
+//   static constexpr const char *abi         "cge_<env>", the prefix of the error texts
+//   size_t record_bytes() const
+//   std::vector<RecordArray> record_arrays() const     the device arrays a record is made from, in the order stage.at() names them
+//   int record_prologue(const char *who)     handle-level values read once per call, after the synchronisation (default: none)
+//   const char *check_record(const uint8_t *rec)       nullptr, or why set_state refuses the record; reads the record only
+//   int to_record(const RecordStage &, int64_t j, uint8_t *rec, const char **why) const     env j of the staged round -> record;
+//                                            CGE_OK, or a status and *why
+//   void from_record(const uint8_t *rec, RecordStage &, int64_t j) const                    a checked record -> env j of the round
+constexpr int64_t STATE_CHUNK = 4096;      // envs per host staging round: bounds the host memory of a large batch's export
+struct RecordArray {
+    void *dev;
+    size_t elem;          // bytes per element
+    int64_t rows;         // elements per env
+    bool env_major;       // true: env i owns `rows` consecutive elements; false (column-major): element (row r, env i) at r * n + i
+    bool get;             // false: get_state does not read it; set_state uploads it as zeros unless from_record writes it
+};
+struct RecordStage {
+    std::vector<RecordArray> arrays;
+    int64_t n, cap;       // envs of the handle, envs per round
+    std::vector<std::vector<uint8_t>> buf;
+    RecordStage(std::vector<RecordArray> a, int64_t n_) : arrays(std::move(a)), n(n_), cap(n_ < STATE_CHUNK ? n_ : STATE_CHUNK) {
+        for (const RecordArray &d : arrays) buf.emplace_back(d.elem * (size_t)d.rows * (size_t)cap, (uint8_t)0);
+    }
+    // element `row` of env j of the round in array a
+    template <class T>
+    T *at(int a, int64_t j, int64_t row = 0) const {
+        const RecordArray &d = arrays[a];
+        return reinterpret_cast<T *>(const_cast<uint8_t *>(buf[a].data())) + (d.env_major ? j * d.rows + row : row * cap + j);
+    }
+    // envs [c0, c0 + m) of array a between the device and the stage: one contiguous piece (env-major), or one piece per row
+    hipError_t copy(int a, int64_t c0, int64_t m, bool to_device) {
+        const RecordArray &d = arrays[a];
+        const int64_t pieces = d.env_major ? 1 : d.rows;
+        const size_t bytes = (size_t)m * d.elem * (d.env_major ? (size_t)d.rows : 1u);
+        for (int64_t r = 0; r < pieces; ++r) {
+            char *dev = static_cast<char *>(d.dev) + (d.env_major ? (size_t)c0 * d.rows : (size_t)r * n + c0) * d.elem;
+            uint8_t *host = buf[a].data() + (size_t)r * cap * d.elem;
+            const hipError_t e = to_device ? hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice) : hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+};
+template <class H>
+int record_fail(H *h, int status, const char *fn, int64_t env, const char *why) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s_%s: env %lld: %s", H::abi, fn, (long long)env, why);
+    return h->fail(status, msg);
+}
+template <class H>
+int get_records(H *h, void *host_buf, hipStream_t s) {
+    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    CGE_TRY(h, hipStreamSynchronize(s));
+    if (int st = h->record_prologue("get_state")) return st;
+    const size_t rec = h->record_bytes();
+    RecordStage stage(h->record_arrays(), h->n);
+    for (int64_t c0 = 0; c0 < h->n; c0 += stage.cap) {
+        const int64_t m = h->n - c0 < stage.cap ? h->n - c0 : stage.cap;
+        for (int a = 0; a < (int)stage.arrays.size(); ++a)
+            if (stage.arrays[a].get) CGE_TRY(h, stage.copy(a, c0, m, false));
+        for (int64_t j = 0; j < m; ++j) {
+            const char *why = "";
+            if (int st = h->to_record(stage, j, static_cast<uint8_t *>(host_buf) + (size_t)(c0 + j) * rec, &why)) return record_fail(h, st, "get_state", c0 + j, why);
+        }
+    }
+    return CGE_OK;
+}
+// Every record is checked before the stream is waited for and before anything is written: a malformed record anywhere leaves the
+// device state of every env as it was.
+template <class H>
+int set_records(H *h, const void *host_buf, hipStream_t s) {
+    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    const size_t rec = h->record_bytes();
+    const uint8_t *in = static_cast<const uint8_t *>(host_buf);
+    for (int64_t i = 0; i < h->n; ++i)
+        if (const char *bad = h->check_record(in + (size_t)i * rec)) return record_fail(h, CGE_ERR_INVALID_ARG, "set_state", i, bad);
+    CGE_TRY(h, hipStreamSynchronize(s));
+    if (int st = h->record_prologue("set_state")) return st;
+    RecordStage stage(h->record_arrays(), h->n);
+    for (int64_t c0 = 0; c0 < h->n; c0 += stage.cap) {
+        const int64_t m = h->n - c0 < stage.cap ? h->n - c0 : stage.cap;
+        for (int64_t j = 0; j < m; ++j) h->from_record(in + (size_t)(c0 + j) * rec, stage, j);
+        for (int a = 0; a < (int)stage.arrays.size(); ++a) CGE_TRY(h, stage.copy(a, c0, m, true));
+    }
+    return CGE_OK;
+}
+#define CGE_DEFINE_RECORDS(ENV)                                                                                                                \
+    size_t cge_##ENV##_state_bytes(const cge_##ENV *h) { return h ? h->record_bytes() : 0; }                                                   \
+    int cge_##ENV##_get_state(cge_##ENV *h, void *host_buf, void *stream) { return cge::get_records(h, host_buf, cge::as_stream(stream)); }    \
+    int cge_##ENV##_set_state(cge_##ENV *h, const void *host_buf, void *stream) { return cge::set_records(h, host_buf, cge::as_stream(stream)); }
 
 
 // Seeds n MT19937 stream blocks (cge_device.hpp layout, `stride_words` apart starting at `mt`).

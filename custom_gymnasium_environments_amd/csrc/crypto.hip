@@ -1134,6 +1134,71 @@ struct cge_crypto : HandleBase {
         hipLaunchKernelGGL(crypto::init_kernel, dim3(grid256(n)), dim3(256), 0, nullptr, scal, n, cfg.initial_balance, 0);
         return hipGetLastError();
     }
+
+    // canonical records (cge_host.hpp: get_records / set_records): int32[12] = {regime, step, needs_reset, cash_kind, index P, index L,
+    // has_gauss, episodes, 0...}, double[6] = {cash, holdings, psychology, trend, gauss, episode return so far}, the 624 words of
+    // stream P and of stream L, and the HLEN history rows {open, high, low, close, volume} as doubles, oldest first
+    static constexpr const char *abi = "cge_crypto";
+    enum { A_SCAL, A_CLOSES, A_OHLV, A_MTP, A_MTL };
+    uint32_t phase = 0;            // the device ring's phase, read once per get_state / set_state call (record_prologue)
+    size_t record_bytes() const { return 12 * 4 + 6 * 8 + 2 * MT_N * 4 + crypto::HLEN * 5 * 8; }
+    std::vector<RecordArray> record_arrays() const {
+        return {{scal, sizeof(uint4), 4, false, true}, {closes, sizeof(double), crypto::HLEN, false, true}, {ohlv, sizeof(float4), crypto::HLEN, false, true},
+                {mtP, sizeof(uint32_t), MT_STRIDE, true, true}, {mtL, sizeof(uint32_t), MT_STRIDE, true, true}};
+    }
+    // the records are laid out at the phase the device ring has after everything queued on the stream
+    int record_prologue(const char *who) {
+        CGE_TRY(this, hipMemcpy(&phase, ring, sizeof phase, hipMemcpyDeviceToHost));
+        if (phase < (uint32_t)crypto::HLEN) return CGE_OK;
+        return fail(CGE_ERR_HIP, (std::string(abi) + "_" + who + ": ring phase out of range").c_str());
+    }
+    const char *check_record(const uint8_t *p) const {
+        int32_t hd[12];
+        memcpy(hd, p, 48);
+        const bool ok = hd[0] >= 0 && hd[0] <= 4 && hd[1] >= 0 && hd[1] <= crypto::MAX_STEPS_LIMIT && hd[4] >= 0 && hd[4] <= MT_N && hd[5] >= 0 && hd[5] <= MT_N;
+        return ok ? nullptr : "malformed record";
+    }
+    int to_record(const RecordStage &st, int64_t j, uint8_t *p, const char **why) const {
+        crypto::Env e;
+        e.unpack(*st.at<uint4>(A_SCAL, j, 0), *st.at<uint4>(A_SCAL, j, 1), *st.at<uint4>(A_SCAL, j, 2), *st.at<uint4>(A_SCAL, j, 3));
+        int32_t hd[12] = {(int32_t)e.regime, (int32_t)e.step, (int32_t)e.needs_reset, (int32_t)e.cash_kind,
+                          0, 0, (int32_t)e.has_gauss, (int32_t)e.episodes, 0, 0, 0, 0};
+        const double scv[6] = {e.cash, e.holdings, e.psych, e.trend, e.gauss, e.ep_return};
+        if (!mt_export_cpython(st.at<uint32_t>(A_MTP, j), e.ppos, e.ppretw, (uint32_t *)(p + 96), &hd[4]) ||
+            !mt_export_cpython(st.at<uint32_t>(A_MTL, j), e.lpos, e.lpretw, (uint32_t *)(p + 96 + MT_N * 4), &hd[5])) {
+            *why = "a generator stream is twisted further ahead than the export can take back";
+            return CGE_ERR_UNSUPPORTED;
+        }
+        memcpy(p, hd, 48);
+        memcpy(p + 48, scv, 48);
+        double *hh = (double *)(p + 96 + 2 * MT_N * 4);
+        for (int k = 0; k < crypto::HLEN; ++k) {
+            const int slot = ((int)phase + k) % crypto::HLEN;
+            const float4 v = *st.at<float4>(A_OHLV, j, slot);
+            hh[5 * k] = v.x; hh[5 * k + 1] = v.y; hh[5 * k + 2] = v.z; hh[5 * k + 3] = *st.at<double>(A_CLOSES, j, slot); hh[5 * k + 4] = v.w;
+        }
+        return CGE_OK;
+    }
+    void from_record(const uint8_t *p, RecordStage &st, int64_t j) const {
+        int32_t hd[12];
+        double scv[6];
+        memcpy(hd, p, 48);
+        memcpy(scv, p + 48, 48);
+        const double *hh = (const double *)(p + 96 + 2 * MT_N * 4);
+        crypto::Env e;
+        e.cash = scv[0]; e.holdings = scv[1]; e.psych = scv[2]; e.trend = scv[3]; e.gauss = scv[4]; e.ep_return = scv[5];
+        e.close = hh[5 * (crypto::HLEN - 1) + 3];
+        e.regime = (uint32_t)hd[0]; e.step = (uint32_t)hd[1]; e.needs_reset = (uint32_t)(hd[2] & 1); e.cash_kind = (uint32_t)(hd[3] & 3);
+        e.has_gauss = (uint32_t)(hd[6] & 1); e.episodes = hd[7] < 0 ? 0u : (uint32_t)hd[7];
+        mt_import_cpython((const uint32_t *)(p + 96), hd[4], st.at<uint32_t>(A_MTP, j), &e.ppos, &e.ppretw);
+        mt_import_cpython((const uint32_t *)(p + 96 + MT_N * 4), hd[5], st.at<uint32_t>(A_MTL, j), &e.lpos, &e.lpretw);
+        e.pack(*st.at<uint4>(A_SCAL, j, 0), *st.at<uint4>(A_SCAL, j, 1), *st.at<uint4>(A_SCAL, j, 2), *st.at<uint4>(A_SCAL, j, 3));
+        for (int k = 0; k < crypto::HLEN; ++k) {
+            const int slot = ((int)phase + k) % crypto::HLEN;
+            *st.at<double>(A_CLOSES, j, slot) = hh[5 * k + 3];
+            *st.at<float4>(A_OHLV, j, slot) = make_float4((float)hh[5 * k], (float)hh[5 * k + 1], (float)hh[5 * k + 2], (float)hh[5 * k + 4]);
+        }
+    }
 };
 
 static hipError_t launch_resident(cge_crypto *h, const crypto::Params &p, hipStream_t s, bool one_step) {
@@ -1226,96 +1291,6 @@ int cge_crypto_info(cge_crypto *h, int32_t field_id, double *out, void *stream) 
     return launched(h);
 }
 
-size_t cge_crypto_state_bytes(const cge_crypto *h) { return h ? 12 * 4 + 6 * 8 + 2 * MT_N * 4 + crypto::HLEN * 5 * 8 : 0; }
-
-int cge_crypto_get_state(cge_crypto *h, void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    std::vector<uint4> sc((size_t)4 * n);
-    std::vector<double> cl((size_t)crypto::HLEN * n);
-    std::vector<float4> oh((size_t)crypto::HLEN * n);
-    std::vector<uint32_t> mp((size_t)n * MT_STRIDE), ml((size_t)n * MT_STRIDE);
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(sc.data(), h->scal, sc.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(cl.data(), h->closes, cl.size() * sizeof(double), hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(oh.data(), h->ohlv, oh.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(mp.data(), h->mtP, mp.size() * 4, hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(ml.data(), h->mtL, ml.size() * 4, hipMemcpyDeviceToHost));
-    uint32_t phase = 0;
-    CGE_TRY(h, hipMemcpy(&phase, h->ring, sizeof phase, hipMemcpyDeviceToHost));
-    if (phase >= (uint32_t)crypto::HLEN) return h->fail(CGE_ERR_HIP, "cge_crypto_get_state: ring phase out of range");
-    const size_t rec = cge_crypto_state_bytes(h);
-    for (int64_t i = 0; i < n; ++i) {
-        uint8_t *p = (uint8_t *)host_buf + (size_t)i * rec;
-        crypto::Env e;
-        e.unpack(sc[i], sc[n + i], sc[2 * n + i], sc[3 * n + i]);
-        int32_t hd[12] = {(int32_t)e.regime, (int32_t)e.step, (int32_t)e.needs_reset, (int32_t)e.cash_kind,
-                          0, 0, (int32_t)e.has_gauss, (int32_t)e.episodes, 0, 0, 0, 0};
-        double scv[6] = {e.cash, e.holdings, e.psych, e.trend, e.gauss, e.ep_return};   // [5]: episode return so far
-        if (!mt_export_cpython(&mp[(size_t)i * MT_STRIDE], e.ppos, e.ppretw, (uint32_t *)(p + 96), &hd[4]) ||
-            !mt_export_cpython(&ml[(size_t)i * MT_STRIDE], e.lpos, e.lpretw, (uint32_t *)(p + 96 + MT_N * 4), &hd[5]))
-            return h->fail(CGE_ERR_UNSUPPORTED, "cge_crypto_get_state: a generator stream is twisted further ahead than the export can take back");
-        memcpy(p, hd, 48);
-        memcpy(p + 48, scv, 48);
-        double *hh = (double *)(p + 96 + 2 * MT_N * 4);
-        for (int k = 0; k < crypto::HLEN; ++k) {
-            const int slot = ((int)phase + k) % crypto::HLEN;
-            const float4 v = oh[(size_t)slot * n + i];
-            hh[5 * k] = v.x; hh[5 * k + 1] = v.y; hh[5 * k + 2] = v.z; hh[5 * k + 3] = cl[(size_t)slot * n + i]; hh[5 * k + 4] = v.w;
-        }
-    }
-    return CGE_OK;
-}
-
-int cge_crypto_set_state(cge_crypto *h, const void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    std::vector<uint4> sc((size_t)4 * n);
-    std::vector<double> cl((size_t)crypto::HLEN * n);
-    std::vector<float4> oh((size_t)crypto::HLEN * n);
-    std::vector<uint32_t> mp((size_t)n * MT_STRIDE, 0u), ml((size_t)n * MT_STRIDE, 0u);
-    // the records are laid out at the phase the device ring has after everything queued on `stream`
-    uint32_t phase = 0;
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(&phase, h->ring, sizeof phase, hipMemcpyDeviceToHost));
-    if (phase >= (uint32_t)crypto::HLEN) return h->fail(CGE_ERR_HIP, "cge_crypto_set_state: ring phase out of range");
-    const size_t rec = cge_crypto_state_bytes(h);
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *p = (const uint8_t *)host_buf + (size_t)i * rec;
-        int32_t hd[12];
-        double scv[6];
-        memcpy(hd, p, 48);
-        memcpy(scv, p + 48, 48);
-        if (hd[0] < 0 || hd[0] > 4 || hd[1] < 0 || hd[1] > crypto::MAX_STEPS_LIMIT || hd[4] < 0 || hd[4] > MT_N || hd[5] < 0 || hd[5] > MT_N)
-            return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_set_state: malformed record");
-        const double *hh = (const double *)(p + 96 + 2 * MT_N * 4);
-        crypto::Env e;
-        e.cash = scv[0]; e.holdings = scv[1]; e.psych = scv[2]; e.trend = scv[3]; e.gauss = scv[4]; e.ep_return = scv[5];
-        e.close = hh[5 * (crypto::HLEN - 1) + 3];
-        e.regime = (uint32_t)hd[0]; e.step = (uint32_t)hd[1]; e.needs_reset = (uint32_t)(hd[2] & 1); e.cash_kind = (uint32_t)(hd[3] & 3);
-        e.has_gauss = (uint32_t)(hd[6] & 1); e.episodes = hd[7] < 0 ? 0u : (uint32_t)hd[7];
-        // a CPython state: every word from the index on is generated-but-unconsumed (ready); index 624 = regenerate first
-        e.ppos = hd[4] >= MT_N ? 0u : (uint32_t)hd[4]; e.ppretw = hd[4] >= MT_N ? 0u : (uint32_t)MT_N;
-        e.lpos = hd[5] >= MT_N ? 0u : (uint32_t)hd[5]; e.lpretw = hd[5] >= MT_N ? 0u : (uint32_t)MT_N;
-        e.pack(sc[i], sc[n + i], sc[2 * n + i], sc[3 * n + i]);
-        memcpy(&mp[(size_t)i * MT_STRIDE], p + 96, MT_N * 4);
-        memcpy(&ml[(size_t)i * MT_STRIDE], p + 96 + MT_N * 4, MT_N * 4);
-        memcpy(&mp[(size_t)i * MT_STRIDE + MT_N], &mp[(size_t)i * MT_STRIDE], MT_PAD * 4);       // mirror words (cge_device.hpp)
-        memcpy(&ml[(size_t)i * MT_STRIDE + MT_N], &ml[(size_t)i * MT_STRIDE], MT_PAD * 4);
-        for (int k = 0; k < crypto::HLEN; ++k) {
-            const int slot = ((int)phase + k) % crypto::HLEN;
-            cl[(size_t)slot * n + i] = hh[5 * k + 3];
-            oh[(size_t)slot * n + i] = make_float4((float)hh[5 * k], (float)hh[5 * k + 1], (float)hh[5 * k + 2], (float)hh[5 * k + 4]);
-        }
-    }
-    CGE_TRY(h, hipMemcpy(h->scal, sc.data(), sc.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->closes, cl.data(), cl.size() * sizeof(double), hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->ohlv, oh.data(), oh.size() * sizeof(float4), hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->mtP, mp.data(), mp.size() * 4, hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->mtL, ml.data(), ml.size() * 4, hipMemcpyHostToDevice));
-    return CGE_OK;
-}
+CGE_DEFINE_RECORDS(crypto)
 
 }  // extern "C"

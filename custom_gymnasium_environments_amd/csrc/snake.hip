@@ -982,7 +982,7 @@ struct Ops {
     void (*info)(const uint4 *, int64_t, int, int32_t *, hipStream_t);
     void (*render)(const uint4 *, int64_t, uint32_t *, hipStream_t);
     void (*decode)(const uint32_t *raw, int32_t *hdr, uint16_t *body, uint32_t *mt_pos, uint32_t *mt_pretw, uint32_t *dq_left);
-    bool (*encode)(const int32_t *hdr, const uint16_t *body, uint32_t *raw);
+    bool (*encode)(const int32_t *hdr, const uint16_t *body, uint32_t mt_pos, uint32_t mt_pretw, uint32_t *raw);
 };
 
 template <int G>
@@ -1008,7 +1008,7 @@ void decode_env(const uint32_t *raw, int32_t *hdr, uint16_t *body, uint32_t *mt_
 
 // false: the body is not a path of unit moves inside the board (no such list can arise from the reference's step())
 template <int G>
-bool encode_env(const int32_t *hdr, const uint16_t *body, uint32_t *raw) {
+bool encode_env(const int32_t *hdr, const uint16_t *body, uint32_t mt_pos, uint32_t mt_pretw, uint32_t *raw) {
     Env<G> e;
     memset(&e, 0, sizeof e);
     const int len = hdr[0];
@@ -1036,9 +1036,7 @@ bool encode_env(const int32_t *hdr, const uint16_t *body, uint32_t *raw) {
     e.steps = (uint32_t)hdr[5];
     e.flags = (hdr[6] ? F_NEEDS_RESET : 0u) | (fv ? F_FOOD_VALID : 0u);
     e.episodes = 0;                        // not part of the canonical record: a restored env starts counting again
-    // canonical CPython cursor -> incremental cursor
-    if (hdr[7] >= MT_N) { e.mt_pos = 0; e.mt_pretw = 0; }
-    else { e.mt_pos = (uint32_t)hdr[7]; e.mt_pretw = MT_N; }
+    e.mt_pos = mt_pos; e.mt_pretw = mt_pretw;      // the incremental cursor of the canonical index hdr[7] (mt_import_cpython)
     e.pack(raw);
     return true;
 }
@@ -1068,6 +1066,8 @@ void launch_any(const Params &p, bool rollout, hipStream_t s, std::string *name)
     else if (p.mode == CGE_AUTORESET_NEXT_STEP) launch_mode<G, BLOCK, MINW, CGE_AUTORESET_NEXT_STEP>(p, rollout, s, name);
     else launch_mode<G, BLOCK, MINW, CGE_AUTORESET_DISABLED>(p, rollout, s, name);
 }
+
+constexpr int MAX_RAW = 4 * Lay<30>::COLS;      // words of the largest grid's device record
 
 template <int G>
 Ops make_ops() {
@@ -1145,6 +1145,52 @@ struct cge_snake : HandleBase {
         CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
         ops.reset(params(), nullptr);
         return hipGetLastError();
+    }
+
+    // canonical records (cge_host.hpp: get_records / set_records): header int32[8] = {length, direction, food row, food col, score,
+    // steps, needs_reset, CPython index}, the 624 generator words, the body head -> tail as uint16 cells (0xFFFF beyond the length)
+    static constexpr const char *abi = "cge_snake";
+    enum { A_STATE, A_MT };
+    size_t record_bytes() const { return (8 * 4 + (size_t)MT_N * 4 + (size_t)ops.cells * 2 + 3) & ~(size_t)3; }
+    std::vector<RecordArray> record_arrays() const {
+        return {{state, sizeof(uint4), ops.cols, false, true}, {mt, sizeof(uint32_t), MT_STRIDE, true, true}};
+    }
+    const char *check_record(const uint8_t *p) const {
+        const int32_t *hdr = (const int32_t *)p;
+        const uint16_t *body = (const uint16_t *)(p + 32 + MT_N * 4);
+        const int cells = ops.cells, G = cfg.grid_size;
+        if (hdr[0] < 1 || hdr[0] > cells || hdr[1] < 0 || hdr[1] > 3 || hdr[7] < 0 || hdr[7] > MT_N) return "malformed record";
+        const bool no_food = hdr[2] == -1 && hdr[3] == -1;
+        if ((!no_food && (hdr[2] < 0 || hdr[2] >= G || hdr[3] < 0 || hdr[3] >= G)) || hdr[4] < 0 || hdr[4] > cells || hdr[5] < 0 ||
+            hdr[5] > ops.max_steps_limit || (hdr[6] != 0 && hdr[6] != 1))
+            return "food / score / steps / needs_reset out of range";
+        for (int k = 0; k < hdr[0]; ++k)
+            if (body[k] >= cells) return "body cell out of range";
+        uint32_t raw[snake::MAX_RAW];                              // encoded and discarded: the path check is the encoder's
+        return ops.encode(hdr, body, 0u, 0u, raw) ? nullptr : "the body is not a path of unit moves";
+    }
+    int to_record(const RecordStage &st, int64_t j, uint8_t *p, const char **why) const {
+        uint32_t raw[snake::MAX_RAW];
+        for (int c = 0; c < ops.cols; ++c) memcpy(raw + 4 * c, st.at<uint4>(A_STATE, j, c), 16);
+        int32_t *hdr = (int32_t *)p;
+        uint32_t pos = 0, pretw = 0, left = 0;
+        ops.decode(raw, hdr, (uint16_t *)(p + 32 + MT_N * 4), &pos, &pretw, &left);
+        if (left > pos) { *why = "corrupted digit-ring cursor"; return CGE_ERR_INVALID_ARG; }
+        // Words [pos - left, pos) are twisted already and wait in the env's digit ring (snake::DigitQ): the CPython index is the
+        // exported one minus `left`, and since a ring never holds digits of two generations, the export's "twist the rest" completes
+        // the generation.  The record keeps the ready mark as one bit (0 or 624), so the export never has a next generation to take
+        // back and cannot refuse; with cursor 0 and nothing ready (index 624) left is 0.
+        int32_t idx = 0;
+        mt_export_cpython(st.at<uint32_t>(A_MT, j), pos, pretw, (uint32_t *)(p + 32), &idx);
+        hdr[7] = idx - (int32_t)left;
+        return CGE_OK;
+    }
+    void from_record(const uint8_t *p, RecordStage &st, int64_t j) const {
+        const int32_t *hdr = (const int32_t *)p;
+        uint32_t raw[snake::MAX_RAW], pos, pretw;
+        mt_import_cpython((const uint32_t *)(p + 32), hdr[7], st.at<uint32_t>(A_MT, j), &pos, &pretw);
+        ops.encode(hdr, (const uint16_t *)(p + 32 + MT_N * 4), pos, pretw, raw);
+        for (int c = 0; c < ops.cols; ++c) memcpy(st.at<uint4>(A_STATE, j, c), raw + 4 * c, 16);
     }
 };
 
@@ -1230,91 +1276,7 @@ int cge_snake_render_rgb(cge_snake *h, uint8_t *rgb_out, void *stream) {
     return launched(h);
 }
 
-size_t cge_snake_state_bytes(const cge_snake *h) {
-    if (!h) return 0;
-    size_t b = 8 * 4 + (size_t)MT_N * 4 + (size_t)h->ops.cells * 2;
-    return (b + 3) & ~(size_t)3;
-}
-
-int cge_snake_get_state(cge_snake *h, void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    const int cols = h->ops.cols;
-    std::vector<uint4> st((size_t)cols * n);
-    std::vector<uint32_t> mt((size_t)n * MT_STRIDE);
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(st.data(), h->state, st.size() * sizeof(uint4), hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(mt.data(), h->mt, mt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const size_t rec = cge_snake_state_bytes(h);
-    std::vector<uint32_t> raw((size_t)cols * 4);
-    for (int64_t i = 0; i < n; ++i) {
-        for (int c = 0; c < cols; ++c) {
-            const uint4 v = st[(size_t)c * n + i];
-            raw[4 * c] = v.x; raw[4 * c + 1] = v.y; raw[4 * c + 2] = v.z; raw[4 * c + 3] = v.w;
-        }
-        uint8_t *p = (uint8_t *)host_buf + (size_t)i * rec;
-        int32_t *hdr = (int32_t *)p;
-        uint32_t *omt = (uint32_t *)(p + 32);
-        uint16_t *body = (uint16_t *)(p + 32 + MT_N * 4);
-        uint32_t pos = 0, pretw = 0, left = 0;
-        h->ops.decode(raw.data(), hdr, body, &pos, &pretw, &left);
-        // incremental-twist stream -> CPython layout (words >= idx generated but unconsumed).  Words [pos - left, pos) are twisted
-        // already and wait in the env's digit ring (snake::DigitQ): the CPython cursor is pos - left, and since a ring never
-        // holds digits of two generations, twisting the words from pos on completes the generation.
-        const uint32_t *w = &mt[(size_t)i * MT_STRIDE];
-        memcpy(omt, w, MT_N * 4);
-        if (left > pos) return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_get_state: corrupted digit-ring cursor");
-        if (pretw >= (uint32_t)MT_N) {
-            hdr[7] = (int32_t)(pos - left);
-        } else if (pos == 0) {
-            hdr[7] = MT_N;
-        } else {
-            for (uint32_t k = pos; k < (uint32_t)MT_N; ++k) {
-                const uint32_t k1 = k + 1 == (uint32_t)MT_N ? 0 : k + 1;
-                const uint32_t km = k + MT_M >= (uint32_t)MT_N ? k + MT_M - MT_N : k + MT_M;
-                const uint32_t t = (omt[k] & 0x80000000u) | (omt[k1] & 0x7fffffffu);
-                omt[k] = omt[km] ^ (t >> 1) ^ ((t & 1u) ? 0x9908b0dfu : 0u);
-            }
-            hdr[7] = (int32_t)(pos - left);
-        }
-    }
-    return CGE_OK;
-}
-
-int cge_snake_set_state(cge_snake *h, const void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    const int cols = h->ops.cols, cells = h->ops.cells;
-    const size_t rec = cge_snake_state_bytes(h);
-    std::vector<uint4> st((size_t)cols * n);
-    std::vector<uint32_t> mt((size_t)n * MT_STRIDE, 0u);
-    std::vector<uint32_t> raw((size_t)cols * 4);
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *p = (const uint8_t *)host_buf + (size_t)i * rec;
-        const int32_t *hdr = (const int32_t *)p;
-        const uint16_t *body = (const uint16_t *)(p + 32 + MT_N * 4);
-        if (hdr[0] < 1 || hdr[0] > cells || hdr[1] < 0 || hdr[1] > 3 || hdr[7] < 0 || hdr[7] > MT_N)
-            return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_set_state: malformed record");
-        const int G = h->cfg.grid_size;
-        const bool no_food = hdr[2] == -1 && hdr[3] == -1;
-        if ((!no_food && (hdr[2] < 0 || hdr[2] >= G || hdr[3] < 0 || hdr[3] >= G)) || hdr[4] < 0 || hdr[4] > cells || hdr[5] < 0 ||
-            hdr[5] > h->ops.max_steps_limit || (hdr[6] != 0 && hdr[6] != 1))
-            return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_set_state: food / score / steps / needs_reset out of range");
-        for (int k = 0; k < hdr[0]; ++k)
-            if (body[k] >= cells) return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_set_state: body cell out of range");
-        if (!h->ops.encode(hdr, body, raw.data())) return h->fail(CGE_ERR_INVALID_ARG, "cge_snake_set_state: the body is not a path of unit moves");
-        for (int c = 0; c < cols; ++c) st[(size_t)c * n + i] = make_uint4(raw[4 * c], raw[4 * c + 1], raw[4 * c + 2], raw[4 * c + 3]);
-        uint32_t *w = &mt[(size_t)i * MT_STRIDE];
-        memcpy(w, p + 32, MT_N * 4);
-        memcpy(w + MT_N, w, MT_PAD * 4);                           // words 624.. mirror words 0..15 (cge_device.hpp)
-    }
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(h->state, st.data(), st.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->mt, mt.data(), mt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return CGE_OK;
-}
+CGE_DEFINE_RECORDS(snake)
 
 CGE_DEFINE_ERROR_COUNT(snake)
 

@@ -952,41 +952,67 @@ struct cge_traffic : HandleBase {
             default: traffic::launch_step<0, 4>(p, rollout, s); break;
         }
     }
-};
 
-// device record <-> the canonical record's fields (w: phase[ni], timer[ni], passed[ni], total_wait[ni], qlen, qdest, qwait [4 ni])
-static void to_record(const uint32_t *rec, int ni, int32_t *hd, double *total_reward, int32_t *w, uint32_t *mt_pos, uint32_t *mt_pretw, uint32_t *mt_old0) {
-    using namespace traffic;
-    const uint32_t m0 = rec[0], m1 = rec[1];
-    hd[0] = (int32_t)(m0 & 0xFFFFu); hd[1] = (int32_t)((m0 >> 16) & 127u); hd[2] = (int32_t)((m0 >> 23) & 1u); hd[3] = 0; hd[4] = (int32_t)rec[2]; hd[5] = 0;
-    const uint64_t u = ((uint64_t)rec[5] << 32) | rec[4];
-    memcpy(total_reward, &u, 8);
-    *mt_pos = m1 & 1023u; *mt_pretw = mt_ready_decode((m1 >> 10) & 31u); *mt_old0 = rec[3];
-    for (int k = 0; k < ni; ++k) {
-        const uint32_t lp = rec[O_Q + 4 * ni + 2 * k];
-        w[k] = (int32_t)(lp & 3u); w[ni + k] = (int32_t)((lp >> 2) & 31u); w[2 * ni + k] = (int32_t)(lp >> 8); w[3 * ni + k] = (int32_t)rec[O_Q + 4 * ni + 2 * k + 1];
+    // canonical records (cge_host.hpp: get_records / set_records): int32[6] = {step, episodes, needs_reset, CPython index, spawned, 0},
+    // the float64 total reward, w = int32 phase[ni], timer[ni], passed[ni], total_wait[ni], qlen, qdest, qwait [4 ni], the 624 words
+    static constexpr const char *abi = "cge_traffic";
+    enum { A_STATE, A_MT };
+    size_t record_bytes() const { return 6 * 4 + 8 + (size_t)16 * ni * 4 + MT_N * 4; }
+    std::vector<RecordArray> record_arrays() const {
+        return {{state, sizeof(uint32_t), recw, true, true}, {mt, sizeof(uint32_t), MT_STRIDE, true, true}};
     }
-    for (int k = 0; k < 4 * ni; ++k) {
-        const uint32_t qq = rec[O_Q + k];
-        w[4 * ni + k] = (int32_t)(qq & QM); w[8 * ni + k] = (int32_t)((qq >> QS_DEST) & QM); w[12 * ni + k] = (int32_t)(qq >> QS_WAIT);
+    // every field fits the bit-field of the device record it is packed into
+    const char *check_record(const uint8_t *p) const {
+        int32_t hd[6];
+        memcpy(hd, p, 24);
+        const int32_t *w = (const int32_t *)(p + 32);
+        bool ok = hd[0] >= 0 && hd[0] <= 65535 && hd[1] >= 0 && hd[1] <= 127 && hd[3] >= 0 && hd[3] <= MT_N;
+        for (int k = 0; ok && k < ni; ++k) ok = w[k] >= 0 && w[k] <= 3 && w[ni + k] >= 0 && w[ni + k] <= 31 && w[2 * ni + k] >= 0 && w[2 * ni + k] <= 65535 && w[3 * ni + k] >= 0;
+        for (int k = 0; ok && k < 4 * ni; ++k) ok = w[4 * ni + k] >= 0 && w[4 * ni + k] <= 127 && w[8 * ni + k] >= 0 && w[8 * ni + k] <= 127 && w[12 * ni + k] >= 0 && w[12 * ni + k] <= 262143;
+        return ok ? nullptr : "malformed record (a field does not fit the device record)";
     }
-}
-static void from_record(const int32_t *hd, double total_reward, const int32_t *w, int ni, int recw, uint32_t *rec) {
-    using namespace traffic;
-    memset(rec, 0, (size_t)recw * 4);
-    rec[0] = (uint32_t)hd[0] | ((uint32_t)hd[1] << 16) | ((uint32_t)(hd[2] & 1) << 23);
-    // a CPython state: index >= 624 = nothing of this generation twisted yet; otherwise the whole generation is ready
-    rec[1] = hd[3] >= MT_N ? 0u : ((uint32_t)hd[3] | (mt_ready_encode(MT_N) << 10));
-    rec[2] = (uint32_t)hd[4];
-    uint64_t u;
-    memcpy(&u, &total_reward, 8);
-    rec[4] = (uint32_t)u; rec[5] = (uint32_t)(u >> 32);
-    for (int k = 0; k < ni; ++k) {
-        rec[O_Q + 4 * ni + 2 * k] = ((uint32_t)w[k] & 3u) | (((uint32_t)w[ni + k] & 31u) << 2) | ((uint32_t)w[2 * ni + k] << 8);
-        rec[O_Q + 4 * ni + 2 * k + 1] = (uint32_t)w[3 * ni + k];
+    int to_record(const RecordStage &st, int64_t j, uint8_t *p, const char **why) const {
+        using namespace traffic;
+        const uint32_t *rec = st.at<uint32_t>(A_STATE, j);
+        int32_t *w = (int32_t *)(p + 32);
+        const uint32_t m0 = rec[0], m1 = rec[1];
+        int32_t hd[6] = {(int32_t)(m0 & 0xFFFFu), (int32_t)((m0 >> 16) & 127u), (int32_t)((m0 >> 23) & 1u), 0, (int32_t)rec[2], 0};
+        for (int k = 0; k < ni; ++k) {
+            const uint32_t lp = rec[O_Q + 4 * ni + 2 * k];
+            w[k] = (int32_t)(lp & 3u); w[ni + k] = (int32_t)((lp >> 2) & 31u); w[2 * ni + k] = (int32_t)(lp >> 8); w[3 * ni + k] = (int32_t)rec[O_Q + 4 * ni + 2 * k + 1];
+        }
+        for (int k = 0; k < 4 * ni; ++k) {
+            const uint32_t qq = rec[O_Q + k];
+            w[4 * ni + k] = (int32_t)(qq & QM); w[8 * ni + k] = (int32_t)((qq >> QS_DEST) & QM); w[12 * ni + k] = (int32_t)(qq >> QS_WAIT);
+        }
+        // rec[3]: the saved word 0 of the current generation (its dead low bits come back with it)
+        if (!mt_export_cpython(st.at<uint32_t>(A_MT, j), m1 & 1023u, mt_ready_decode((m1 >> 10) & 31u), (uint32_t *)(w + 16 * ni), &hd[3], &rec[3])) {
+            *why = "the generator stream is twisted further ahead than the export can take back";
+            return CGE_ERR_UNSUPPORTED;
+        }
+        memcpy(p, hd, 24);
+        memcpy(p + 24, &rec[4], 8);                          // total reward: the float64's two halves, low word first
+        return CGE_OK;
     }
-    for (int k = 0; k < 4 * ni; ++k) rec[O_Q + k] = ((uint32_t)w[4 * ni + k] & QM) | (((uint32_t)w[8 * ni + k] & QM) << QS_DEST) | ((uint32_t)w[12 * ni + k] << QS_WAIT);
-}
+    void from_record(const uint8_t *p, RecordStage &st, int64_t j) const {
+        using namespace traffic;
+        int32_t hd[6];
+        memcpy(hd, p, 24);
+        const int32_t *w = (const int32_t *)(p + 32);
+        uint32_t *rec = st.at<uint32_t>(A_STATE, j), pos, pretw;
+        memset(rec, 0, (size_t)recw * 4);
+        mt_import_cpython((const uint32_t *)(w + 16 * ni), hd[3], st.at<uint32_t>(A_MT, j), &pos, &pretw);
+        rec[0] = (uint32_t)hd[0] | ((uint32_t)hd[1] << 16) | ((uint32_t)(hd[2] & 1) << 23);
+        rec[1] = pos | ((pretw > pos ? mt_ready_encode(pretw) : 0u) << 10);
+        rec[2] = (uint32_t)hd[4];
+        memcpy(&rec[4], p + 24, 8);
+        for (int k = 0; k < ni; ++k) {
+            rec[O_Q + 4 * ni + 2 * k] = ((uint32_t)w[k] & 3u) | (((uint32_t)w[ni + k] & 31u) << 2) | ((uint32_t)w[2 * ni + k] << 8);
+            rec[O_Q + 4 * ni + 2 * k + 1] = (uint32_t)w[3 * ni + k];
+        }
+        for (int k = 0; k < 4 * ni; ++k) rec[O_Q + k] = ((uint32_t)w[4 * ni + k] & QM) | (((uint32_t)w[8 * ni + k] & QM) << QS_DEST) | ((uint32_t)w[12 * ni + k] << QS_WAIT);
+    }
+};
 
 extern "C" {
 
@@ -1073,61 +1099,6 @@ int cge_traffic_total_reward(cge_traffic *h, double *out, void *stream) {
     return launched(h);
 }
 
-size_t cge_traffic_state_bytes(const cge_traffic *h) { return h ? 6 * 4 + 8 + (size_t)16 * h->ni * 4 + MT_N * 4 : 0; }
-
-int cge_traffic_get_state(cge_traffic *h, void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    const int recw = h->recw, ni = h->ni;
-    std::vector<uint32_t> st((size_t)recw * n);
-    std::vector<uint32_t> mt((size_t)n * MT_STRIDE);
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(st.data(), h->state, st.size() * 4, hipMemcpyDeviceToHost));
-    CGE_TRY(h, hipMemcpy(mt.data(), h->mt, mt.size() * 4, hipMemcpyDeviceToHost));
-    const size_t rec = cge_traffic_state_bytes(h);
-    for (int64_t i = 0; i < n; ++i) {
-        uint8_t *p = (uint8_t *)host_buf + (size_t)i * rec;
-        int32_t hd[6];
-        int32_t *w = (int32_t *)(p + 32);
-        double total_reward;
-        uint32_t mt_pos, mt_pretw, mt_old0;
-        to_record(&st[(size_t)i * recw], ni, hd, &total_reward, w, &mt_pos, &mt_pretw, &mt_old0);
-        if (!mt_export_cpython(&mt[(size_t)i * MT_STRIDE], mt_pos, mt_pretw, (uint32_t *)(w + 16 * ni), &hd[3], &mt_old0))
-            return h->fail(CGE_ERR_UNSUPPORTED, "cge_traffic_get_state: the generator stream is twisted further ahead than the export can take back");
-        memcpy(p, hd, 24);
-        memcpy(p + 24, &total_reward, 8);
-    }
-    return CGE_OK;
-}
-
-int cge_traffic_set_state(cge_traffic *h, const void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n;
-    const int recw = h->recw, ni = h->ni;
-    std::vector<uint32_t> st((size_t)recw * n);
-    std::vector<uint32_t> mt((size_t)n * MT_STRIDE, 0u);
-    const size_t rec = cge_traffic_state_bytes(h);
-    for (int64_t i = 0; i < n; ++i) {
-        const uint8_t *p = (const uint8_t *)host_buf + (size_t)i * rec;
-        int32_t hd[6];
-        memcpy(hd, p, 24);
-        const int32_t *w = (const int32_t *)(p + 32);
-        bool ok = hd[0] >= 0 && hd[0] <= 65535 && hd[1] >= 0 && hd[1] <= 127 && hd[3] >= 0 && hd[3] <= MT_N;
-        for (int k = 0; ok && k < ni; ++k) ok = w[k] >= 0 && w[k] <= 3 && w[ni + k] >= 0 && w[ni + k] <= 31 && w[2 * ni + k] >= 0 && w[2 * ni + k] <= 65535 && w[3 * ni + k] >= 0;
-        for (int k = 0; ok && k < 4 * ni; ++k) ok = w[4 * ni + k] >= 0 && w[4 * ni + k] <= 127 && w[8 * ni + k] >= 0 && w[8 * ni + k] <= 127 && w[12 * ni + k] >= 0 && w[12 * ni + k] <= 262143;
-        if (!ok) return h->fail(CGE_ERR_INVALID_ARG, "cge_traffic_set_state: malformed record (a field does not fit the device record)");
-        double total_reward;
-        memcpy(&total_reward, p + 24, 8);
-        from_record(hd, total_reward, w, ni, recw, &st[(size_t)i * recw]);
-        memcpy(&mt[(size_t)i * MT_STRIDE], w + 16 * ni, MT_N * 4);
-        memcpy(&mt[(size_t)i * MT_STRIDE + MT_N], &mt[(size_t)i * MT_STRIDE], MT_PAD * 4);     // mirror words (cge_device.hpp)
-    }
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    CGE_TRY(h, hipMemcpy(h->state, st.data(), st.size() * 4, hipMemcpyHostToDevice));
-    CGE_TRY(h, hipMemcpy(h->mt, mt.data(), mt.size() * 4, hipMemcpyHostToDevice));
-    return CGE_OK;
-}
+CGE_DEFINE_RECORDS(traffic)
 
 }  // extern "C"

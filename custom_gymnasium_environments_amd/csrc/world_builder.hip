@@ -434,6 +434,64 @@ struct cge_world_builder : HandleBase {
         launch_reset(params(), 1, 0, nullptr);
         return hipGetLastError();
     }
+
+    // canonical records (cge_host.hpp: get_records / set_records; layout: include/cge_amd.h): the int32[16] header below, the grid
+    // one byte per cell padded to whole dwords, NumPy's 624 key words
+    static constexpr const char *abi = "cge_world_builder";
+    enum { H_FOOD, H_WOOD, H_STONE, H_POP, H_CAP, H_FARM, H_LUMBER, H_QUARRY, H_HOUSE, H_STEPS, H_WIN, H_LATCH, H_NEEDS_RESET, H_MT_POS, H_INTS = 16 };
+    enum { A_STATE, A_MT, A_RET };
+    size_t grid_bytes() const { return (size_t)((cells() + 3) / 4 * 4); }
+    std::vector<RecordArray> record_arrays() const {            // ret: the record holds no running return, set_state zeroes it
+        return {{state, sizeof(uint4), wb::COLS, false, true}, {mt, sizeof(uint32_t), MT_STRIDE, true, true}, {ret, sizeof(int32_t), 1, false, false}};
+    }
+    const char *check_record(const uint8_t *in) const {
+        int32_t hd[H_INTS];
+        memcpy(hd, in, 64);
+        int32_t census[5] = {0, 0, 0, 0, 0};
+        for (int64_t c = 0; c < cells(); ++c) {
+            if (in[64 + c] > 4) return "a grid cell above 4";
+            census[in[64 + c]] += 1;
+        }
+        if (hd[H_FARM] != census[1] || hd[H_LUMBER] != census[2] || hd[H_QUARRY] != census[3] || hd[H_HOUSE] != census[4])
+            return "building counts that differ from the grid's census";
+        if (hd[H_CAP] != 10 + 5 * hd[H_HOUSE]) return "population_capacity != 10 + 5 * houses";
+        if (hd[H_POP] < 0 || hd[H_POP] > 1023) return "population outside 0..1023";
+        if (hd[H_STEPS] < 0 || hd[H_WIN] < 0 || hd[H_WIN] > hd[H_STEPS]) return "steps / win_steps out of range";
+        if ((hd[H_LATCH] | hd[H_NEEDS_RESET]) & ~1) return "a flag that is not 0 or 1";
+        if (hd[H_MT_POS] < 0 || hd[H_MT_POS] > MT_N) return "mt_pos outside 0..624";
+        return nullptr;
+    }
+    int to_record(const RecordStage &st, int64_t j, uint8_t *out, const char **why) const {
+        uint32_t gw[wb::GW + 3];
+        for (int c = 0; c < 4; ++c) memcpy(gw + 4 * c, st.at<uint4>(A_STATE, j, c), 16);
+        const uint4 f = *st.at<uint4>(A_STATE, j, 4);
+        int32_t hd[H_INTS] = {0};
+        hd[H_FOOD] = (int32_t)gw[13]; hd[H_WOOD] = (int32_t)gw[14]; hd[H_STONE] = (int32_t)gw[15];
+        hd[H_FARM] = f.x & 127; hd[H_LUMBER] = (f.x >> 7) & 127; hd[H_QUARRY] = (f.x >> 14) & 127; hd[H_HOUSE] = (f.x >> 21) & 127;
+        hd[H_LATCH] = (f.x >> 28) & 1; hd[H_NEEDS_RESET] = (f.x >> 29) & 1;
+        hd[H_POP] = f.y & 1023; hd[H_CAP] = 10 + 5 * hd[H_HOUSE]; hd[H_STEPS] = (int32_t)f.z; hd[H_WIN] = (int32_t)f.w;
+        if (!mt_export_cpython(st.at<uint32_t>(A_MT, j), (f.y >> 10) & 1023u, mt_ready_decode((f.y >> 20) & 31u), (uint32_t *)(out + 64 + grid_bytes()), &hd[H_MT_POS])) {
+            *why = "generator block twisted too far ahead";
+            return CGE_ERR_UNSUPPORTED;
+        }
+        memcpy(out, hd, 64);
+        memset(out + 64, 0, grid_bytes());
+        for (int64_t c = 0; c < cells(); ++c) out[64 + c] = (uint8_t)((gw[c >> 3] >> (4 * (c & 7))) & 15u);
+        return CGE_OK;
+    }
+    void from_record(const uint8_t *in, RecordStage &st, int64_t j) const {
+        int32_t hd[H_INTS];
+        memcpy(hd, in, 64);
+        uint32_t gw[wb::GW + 3] = {0}, pos, ready;
+        for (int64_t c = 0; c < cells(); ++c) gw[c >> 3] |= (uint32_t)in[64 + c] << (4 * (c & 7));
+        gw[13] = (uint32_t)hd[H_FOOD]; gw[14] = (uint32_t)hd[H_WOOD]; gw[15] = (uint32_t)hd[H_STONE];
+        for (int c = 0; c < 4; ++c) memcpy(st.at<uint4>(A_STATE, j, c), gw + 4 * c, 16);
+        mt_import_cpython((const uint32_t *)(in + 64 + grid_bytes()), hd[H_MT_POS], st.at<uint32_t>(A_MT, j), &pos, &ready);
+        *st.at<uint4>(A_STATE, j, 4) = make_uint4(
+            (uint32_t)hd[H_FARM] | ((uint32_t)hd[H_LUMBER] << 7) | ((uint32_t)hd[H_QUARRY] << 14) | ((uint32_t)hd[H_HOUSE] << 21) |
+                ((uint32_t)hd[H_LATCH] << 28) | ((uint32_t)hd[H_NEEDS_RESET] << 29),
+            (uint32_t)hd[H_POP] | (pos << 10) | ((ready > pos ? mt_ready_encode(ready) : 0u) << 20), (uint32_t)hd[H_STEPS], (uint32_t)hd[H_WIN]);
+    }
 };
 
 template <int MODE, bool FLAT>
@@ -455,12 +513,6 @@ static void launch_wb(cge_world_builder *h, const wb::Params &p, int kind, hipSt
 }
 static std::string kernel_name(const cge_world_builder *h, const char *which, const char *tail) {
     return std::string("cge::wb::") + which + "<" + std::to_string(h->cfg.autoreset_mode) + (h->cfg.flatten_obs ? ", true" : ", false") + tail + ">";
-}
-
-// ---------------------------------------------------------------------------------------------- canonical records (host side)
-namespace {
-constexpr int64_t STATE_CHUNK = 4096;      // envs per host staging round: bounds the host memory of a large batch's export
-enum { H_FOOD, H_WOOD, H_STONE, H_POP, H_CAP, H_FARM, H_LUMBER, H_QUARRY, H_HOUSE, H_STEPS, H_WIN, H_LATCH, H_NEEDS_RESET, H_MT_POS, H_INTS = 16 };
 }
 
 extern "C" {
@@ -526,103 +578,6 @@ int cge_world_builder_info(cge_world_builder *h, int32_t field_id, int32_t index
 
 CGE_DEFINE_ERROR_COUNT(world_builder)
 
-size_t cge_world_builder_state_bytes(const cge_world_builder *h) { return h ? h->record_bytes() : 0; }
-
-int cge_world_builder_get_state(cge_world_builder *h, void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    const int64_t n = h->n, gg = h->cells();
-    const size_t rec = h->record_bytes(), grid_bytes = rec - 64 - 4 * MT_N;
-    std::vector<uint4> cols((size_t)wb::COLS * STATE_CHUNK);
-    std::vector<uint32_t> blocks((size_t)STATE_CHUNK * MT_STRIDE);
-    for (int64_t c0 = 0; c0 < n; c0 += STATE_CHUNK) {
-        const int64_t m = std::min(STATE_CHUNK, n - c0);
-        for (int c = 0; c < wb::COLS; ++c)
-            CGE_TRY(h, hipMemcpy(cols.data() + (size_t)c * STATE_CHUNK, h->state + (size_t)c * n + c0, (size_t)m * sizeof(uint4), hipMemcpyDeviceToHost));
-        CGE_TRY(h, hipMemcpy(blocks.data(), h->mt + (size_t)c0 * MT_STRIDE, (size_t)m * MT_STRIDE * 4, hipMemcpyDeviceToHost));
-        for (int64_t j = 0; j < m; ++j) {
-            uint8_t *out = static_cast<uint8_t *>(host_buf) + (size_t)(c0 + j) * rec;
-            uint32_t gw[wb::GW + 3];
-            for (int c = 0; c < 4; ++c) memcpy(gw + 4 * c, &cols[(size_t)c * STATE_CHUNK + j], 16);
-            const uint4 f = cols[(size_t)4 * STATE_CHUNK + j];
-            int32_t hd[H_INTS] = {0};
-            hd[H_FOOD] = (int32_t)gw[13]; hd[H_WOOD] = (int32_t)gw[14]; hd[H_STONE] = (int32_t)gw[15];
-            hd[H_FARM] = f.x & 127; hd[H_LUMBER] = (f.x >> 7) & 127; hd[H_QUARRY] = (f.x >> 14) & 127; hd[H_HOUSE] = (f.x >> 21) & 127;
-            hd[H_LATCH] = (f.x >> 28) & 1; hd[H_NEEDS_RESET] = (f.x >> 29) & 1;
-            hd[H_POP] = f.y & 1023; hd[H_CAP] = 10 + 5 * hd[H_HOUSE]; hd[H_STEPS] = (int32_t)f.z; hd[H_WIN] = (int32_t)f.w;
-            uint32_t key[MT_N];
-            int32_t idx = 0;
-            if (!mt_export_cpython(blocks.data() + (size_t)j * MT_STRIDE, (f.y >> 10) & 1023u, mt_ready_decode((f.y >> 20) & 31u), key, &idx))
-                return h->fail(CGE_ERR_UNSUPPORTED, "cge_world_builder_get_state: generator block twisted too far ahead");
-            hd[H_MT_POS] = idx;
-            memcpy(out, hd, 64);
-            memset(out + 64, 0, grid_bytes);
-            for (int64_t c = 0; c < gg; ++c) out[64 + c] = (uint8_t)((gw[c >> 3] >> (4 * (c & 7))) & 15u);
-            memcpy(out + 64 + grid_bytes, key, 4 * MT_N);
-        }
-    }
-    return CGE_OK;
-}
-
-int cge_world_builder_set_state(cge_world_builder *h, const void *host_buf, void *stream) {
-    if (!h || !host_buf) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    const int64_t n = h->n, gg = h->cells();
-    const size_t rec = h->record_bytes(), grid_bytes = rec - 64 - 4 * MT_N;
-    char msg[200];
-    for (int64_t i = 0; i < n; ++i) {                                // validate everything before anything is written
-        const uint8_t *in = static_cast<const uint8_t *>(host_buf) + (size_t)i * rec;
-        int32_t hd[H_INTS];
-        memcpy(hd, in, 64);
-        int32_t census[5] = {0, 0, 0, 0, 0};
-        const char *bad = nullptr;
-        for (int64_t c = 0; c < gg && !bad; ++c) {
-            if (in[64 + c] > 4) bad = "a grid cell above 4";
-            else census[in[64 + c]] += 1;
-        }
-        if (!bad && (hd[H_FARM] != census[1] || hd[H_LUMBER] != census[2] || hd[H_QUARRY] != census[3] || hd[H_HOUSE] != census[4]))
-            bad = "building counts that differ from the grid's census";
-        if (!bad && hd[H_CAP] != 10 + 5 * hd[H_HOUSE]) bad = "population_capacity != 10 + 5 * houses";
-        if (!bad && (hd[H_POP] < 0 || hd[H_POP] > 1023)) bad = "population outside 0..1023";
-        if (!bad && (hd[H_STEPS] < 0 || hd[H_WIN] < 0 || hd[H_WIN] > hd[H_STEPS])) bad = "steps / win_steps out of range";
-        if (!bad && ((hd[H_LATCH] | hd[H_NEEDS_RESET]) & ~1)) bad = "a flag that is not 0 or 1";
-        if (!bad && (hd[H_MT_POS] < 0 || hd[H_MT_POS] > MT_N)) bad = "mt_pos outside 0..624";
-        if (bad) {
-            snprintf(msg, sizeof msg, "cge_world_builder_set_state: env %lld: %s", (long long)i, bad);
-            return h->fail(CGE_ERR_INVALID_ARG, msg);
-        }
-    }
-    CGE_TRY(h, hipStreamSynchronize(as_stream(stream)));
-    std::vector<uint4> cols((size_t)wb::COLS * STATE_CHUNK);
-    std::vector<uint32_t> blocks((size_t)STATE_CHUNK * MT_STRIDE);
-    std::vector<int32_t> zero((size_t)STATE_CHUNK, 0);
-    for (int64_t c0 = 0; c0 < n; c0 += STATE_CHUNK) {
-        const int64_t m = std::min(STATE_CHUNK, n - c0);
-        for (int64_t j = 0; j < m; ++j) {
-            const uint8_t *in = static_cast<const uint8_t *>(host_buf) + (size_t)(c0 + j) * rec;
-            int32_t hd[H_INTS];
-            memcpy(hd, in, 64);
-            uint32_t gw[wb::GW + 3] = {0};
-            for (int64_t c = 0; c < gg; ++c) gw[c >> 3] |= (uint32_t)in[64 + c] << (4 * (c & 7));
-            gw[13] = (uint32_t)hd[H_FOOD]; gw[14] = (uint32_t)hd[H_WOOD]; gw[15] = (uint32_t)hd[H_STONE];
-            for (int c = 0; c < 4; ++c) memcpy(&cols[(size_t)c * STATE_CHUNK + j], gw + 4 * c, 16);
-            // NumPy's pos 624 = "regenerate at the next draw": cursor 0 with nothing twisted; otherwise the whole generation is ready
-            const uint32_t pos = hd[H_MT_POS] == MT_N ? 0u : (uint32_t)hd[H_MT_POS], ready = hd[H_MT_POS] == MT_N ? 0u : (uint32_t)MT_N;
-            cols[(size_t)4 * STATE_CHUNK + j] = make_uint4(
-                (uint32_t)hd[H_FARM] | ((uint32_t)hd[H_LUMBER] << 7) | ((uint32_t)hd[H_QUARRY] << 14) | ((uint32_t)hd[H_HOUSE] << 21) |
-                    ((uint32_t)hd[H_LATCH] << 28) | ((uint32_t)hd[H_NEEDS_RESET] << 29),
-                (uint32_t)hd[H_POP] | (pos << 10) | ((ready > pos ? mt_ready_encode(ready) : 0u) << 20), (uint32_t)hd[H_STEPS], (uint32_t)hd[H_WIN]);
-            uint32_t *blk = blocks.data() + (size_t)j * MT_STRIDE;
-            memcpy(blk, in + 64 + grid_bytes, 4 * MT_N);
-            memcpy(blk + MT_N, blk, 4 * MT_PAD);                    // the mirror of words 0..15
-        }
-        for (int c = 0; c < wb::COLS; ++c)
-            CGE_TRY(h, hipMemcpy(h->state + (size_t)c * n + c0, cols.data() + (size_t)c * STATE_CHUNK, (size_t)m * sizeof(uint4), hipMemcpyHostToDevice));
-        CGE_TRY(h, hipMemcpy(h->mt + (size_t)c0 * MT_STRIDE, blocks.data(), (size_t)m * MT_STRIDE * 4, hipMemcpyHostToDevice));
-        CGE_TRY(h, hipMemcpy(h->ret + c0, zero.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));   // the record holds no running return
-    }
-    return CGE_OK;
-}
+CGE_DEFINE_RECORDS(world_builder)
 
 }  // extern "C"

@@ -307,7 +307,8 @@ class DeviceVectorEnv(VectorEnvBase):
         raise NotImplementedError
 
     def get_state(self):
-        """Canonical per-env state records, uint8 [N, state_bytes] on the host (snake, crypto, traffic; the others: `snapshot()`)."""
+        """Canonical per-env state records, uint8 [N, state_bytes] on the host (snake, crypto, traffic, world builder; the others:
+        `snapshot()`).  `set_state` checks every record before it writes one: a refused buffer leaves the batch as it was."""
         buf = np.zeros((self.num_envs, int(self._fn("state_bytes")(self._h))), np.uint8)
         self._check(self._fn("get_state")(self._h, buf.ctypes.data, self._stream()), "get_state")
         return buf

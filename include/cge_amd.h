@@ -45,6 +45,11 @@
  *     pointers are HOST pointers.  `stream` is a hipStream_t passed as void* (NULL = default stream).
  *   - all work is enqueued on `stream`; no call synchronises except get_state/set_state/
  *     error_count/destroy.
+ *   - get_state / set_state (snake, crypto, traffic, world builder) move the batch in rounds of
+ *     4,096 envs: the host memory they stage is bounded by the round, not by n_envs.  set_state
+ *     validates the WHOLE buffer before it writes anything: a malformed record anywhere returns
+ *     CGE_ERR_INVALID_ARG, last_error names the env ("cge_<env>_set_state: env I: reason"), and
+ *     the device state of every env is as it was.
  *   - the library owns the struct-of-arrays env state inside the handle.  A handle is bound to one
  *     device and is not thread-safe; different handles are independent.
  *   - observations are written row-major as (n_envs, *single_obs_shape), exactly the layout

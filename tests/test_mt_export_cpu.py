@@ -109,6 +109,9 @@ def shim(tmp_path_factory):
     L.mt_export_shim_max_ahead.restype = C.c_uint32
     L.mt_ready_decode_shim.argtypes = [C.c_uint32]
     L.mt_ready_decode_shim.restype = C.c_uint32
+    L.mt_import_shim.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mt_import_shim.restype = None
+    L.state_chunk_shim.restype = C.c_int64
     return L
 
 
@@ -191,3 +194,65 @@ def test_export_matches_cpython_at_every_cursor(shim, stream, with_old0):
     assert refused == sum(1 for p in range(N) for m in marks if _legal(p, m) and
                           ((m > N and m - N > EXPORT_MAX_AHEAD) or (p == 0 and EXPORT_MAX_AHEAD < m < N)))
     assert checked + refused + unreachable == N * 32 and checked > 16000
+
+
+# ------------------------------------------------------------------ mt_import_cpython, and the snake's use of the export
+def _import(shim, words, index):
+    blk = np.full(STRIDE, 0xDEADBEEF, np.uint32)
+    cur = np.zeros(2, np.uint32)
+    w = np.ascontiguousarray(words, np.uint32)
+    shim.mt_import_shim(w.ctypes.data, index, blk.ctypes.data, cur[0:].ctypes.data, cur[1:].ctypes.data)
+    return blk, int(cur[0]), int(cur[1])
+
+
+def test_import_then_export_is_the_identity_at_every_index(shim, stream):
+    """set_state's half: (624 words, index) -> block, cursor, ready mark.  The block carries its 16 mirror words, the cursor rule is
+    the one every set_state used to spell out (index 624: cursor 0 with nothing ready; else cursor = index, whole generation ready),
+    and the export gives the same (words, index) back."""
+    gens, _ = stream
+    words = gens[2]
+    for index in range(N + 1):
+        blk, pos, pretw = _import(shim, words, index)
+        assert np.array_equal(blk[:N], words) and np.array_equal(blk[N:], words[:STRIDE - N]), index
+        assert (pos, pretw) == ((0, 0) if index == N else (index, N)), index
+        st, omt, idx = _export(shim, blk, pos, pretw, None)
+        assert st == 0 and idx == index and np.array_equal(omt, words), index
+
+
+def test_state_chunk_is_the_constant_the_gpu_tests_read(shim):
+    assert shim.state_chunk_shim() == _src_int("cge_host.hpp", r"constexpr int64_t STATE_CHUNK = (\d+);") == 4096
+
+
+def test_snake_style_export_is_cpythons_getstate(shim, stream):
+    """cge_snake's to_record: the device record keeps the ready mark as one bit (0, or 624 after an import) and `left` consumed words
+    wait as digits in the env's ring, so the record's index is the exported one minus left.  For every cursor the snake can leave —
+    mark below the cursor (0 < pos, any left < pos), mark at 624, cursor 0 with nothing ready — that is CPython's getstate() after
+    drawing pos - left words of the generation, byte for byte."""
+    gens, _ = stream
+    prev, cur, nxt = gens[1], gens[2], gens[3]
+    r = random.Random()
+
+    def cpython_after(draws):
+        r.setstate((3, tuple(int(x) for x in prev) + (N,), None))          # generation `cur` is regenerated by the first draw
+        for _ in range(draws):
+            r.getrandbits(32)
+        return r.getstate()[1]
+
+    checked = 0
+    for pos in range(N):
+        for pretw in (0, N):
+            if pos == 0 and pretw == 0:                    # nothing drawn, nothing ready: CPython's index 624 over the old words
+                st, omt, idx = _export(shim, _block(prev, cur, nxt, 0, 0), 0, 0, None)
+                assert st == 0 and tuple(int(x) for x in omt) + (idx,) == cpython_after(0)
+                checked += 1
+                continue
+            if pos == 0:                                   # imported at index 0 (CPython never says so itself): it comes back as imported
+                st, omt, idx = _export(shim, _block(prev, cur, nxt, 0, N), 0, N, None)
+                assert st == 0 and idx == 0 and np.array_equal(omt, cur)
+                checked += 1
+                continue
+            for left in sorted({0, 1, pos // 2, min(pos - 1, 63)} & set(range(pos))):
+                st, omt, idx = _export(shim, _block(prev, cur, nxt, pos, pretw), pos, pretw, None)
+                assert st == 0 and tuple(int(x) for x in omt) + (idx - left,) == cpython_after(pos - left), (pos, pretw, left)
+                checked += 1
+    assert checked > 3000

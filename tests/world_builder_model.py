@@ -162,3 +162,18 @@ class WorldBuilderModel:
         st = [r.get_state() for r in self.rng]
         hdr[:, 13] = [s[2] for s in st]
         return pack_state(hdr.astype(np.int32), self.grid, np.stack([s[1] for s in st]))
+
+    def set_state(self, rec):
+        """the inverse of get_state(); the running return restarts at zero, as the device's does"""
+        rec = np.ascontiguousarray(rec, np.uint8)
+        gg = self.G * self.G
+        hdr = rec[:, :64].copy().view("<i4").astype(np.int64)
+        self.food, self.wood, self.stone, self.pop, self.cap = (hdr[:, k].copy() for k in range(5))
+        self.counts[:, 1:5] = hdr[:, 5:9]
+        self.steps, self.win = hdr[:, 9].copy(), hdr[:, 10].copy()
+        self.latch, self.needs_reset = hdr[:, 11].astype(bool), hdr[:, 12].astype(bool)
+        self.grid = rec[:, 64:64 + gg].copy().view(np.int8)
+        key = rec[:, -4 * KEY_WORDS:].copy().view("<u4")
+        for i, r in enumerate(self.rng):
+            r.set_state(("MT19937", key[i], int(hdr[i, 13]), 0, 0.0))
+        self.ret[:] = 0.0
