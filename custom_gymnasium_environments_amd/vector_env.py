@@ -197,7 +197,8 @@ class DeviceVectorEnv(VectorEnvBase):
 
     # ------------------------------------------------------------------ gymnasium API
     # hooks; None = the plain case, which the hot path then handles without a call
-    _device_actions = None    # (actions, k=None) -> the tuple of device tensors whose pointers the C call takes (climate: ac_temp, lights)
+    _device_actions = None    # (actions, k=None) -> the tuple of device tensors whose pointers the C call takes (climate: ac_temp, lights;
+                              # restaurant: its Dict action packed into one tensor)
     _wrap_obs = None          # an observation buffer -> what the caller sees (bus: its dict of views)
 
     def reset(self, *, seed=None, options=None):
@@ -240,6 +241,8 @@ class DeviceVectorEnv(VectorEnvBase):
         fin_ptr = fin.data_ptr() if same else None
         if split is None:                                          # spelled out, not splatted: ~0.5 us per call on a 10 us step
             status = self._c_step(self._h, a.data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc_ptr, fin_ptr, self._stream())
+        elif self._action_ptrs == 1:                               # restaurant: the hook packs a mapping into the one tensor the C call takes
+            status = self._c_step(self._h, a[0].data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc_ptr, fin_ptr, self._stream())
         else:
             status = self._c_step(self._h, a[0].data_ptr(), a[1].data_ptr(), obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc_ptr,
                                   fin_ptr, self._stream())

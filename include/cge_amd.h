@@ -644,6 +644,90 @@ const char *cge_bus_last_error(const cge_bus *h);
 const char *cge_bus_last_kernel(const cge_bus *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Restaurant  (restaurant_env_updated/restaurant_env.py: RestaurantEnv, entities.py)            */
+/*   10 tables, 10 waiters, a waiting line, a kitchen; one arrival draw per step; truncated only  */
+/*   (:171).  action int32 [4] = (type 0..3, waiter_id 0..9, customer_id 0..49, table_id 0..9),   */
+/*   the reference's Dict action (:41-46) in its key order.                                       */
+/*   obs: the Dict of :47-55 as KEY-MAJOR PLANES of int32 — gymnasium's batched-Dict layout.      */
+/*   One observation of the whole batch is a slab of CGE_RESTAURANT_OBS_INTS * n_envs ints        */
+/*   holding, in this order, one contiguous [n_envs, ...] array per key:                          */
+/*     waiting_customers [n,50,2]  waiter_status [n,10,3]  table_occupancy [n,10]                 */
+/*     table_cleanliness [n,10]  kitchen_queue [n,50,3]  ready_orders [n,20,2]                    */
+/*     current_timestep [n,1]                                                                     */
+/*   Bit-exact (the reward is the reference's float64 sum, rounded to float32 on output) EXCEPT   */
+/*   the three id columns waiting_customers[:,0], kitchen_queue[:,0], ready_orders[:,0]: the      */
+/*   reference shows hash(str(uuid.uuid4())) % 100, unreproducible; here a per-env serial number  */
+/*   mod 100, restarted by reset, taken by each arrival and each order in creation order.         */
+/*   Generator: the process-global CPython `random`, one random.random() per step (:382); the     */
+/*   env never seeds it, so cge_restaurant_seed is the caller's random.seed(s_i) for env i.       */
+/*   reset() draws nothing: the stream goes on across episodes.                                   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_restaurant cge_restaurant;
+
+typedef struct {
+    int32_t max_episode_steps;   /* :21 sets 500, the reference's inference.py:14-17 runs 1000; 1..1000, anything else is refused.
+                                  * The record keeps the timestep in 16 bits and saturates it at 65,535: a CGE_AUTORESET_DISABLED batch
+                                  * that is never reset stays truncated (the reference counts on; nothing else depends on it by then) */
+    int32_t autoreset_mode;      /* CGE_AUTORESET_* */
+} cge_restaurant_config;
+
+enum { CGE_RESTAURANT_OBS_INTS = 341 };
+
+enum { /* cge_restaurant_info float64 fields — the values behind _get_info (:478-494) */
+    CGE_RESTAURANT_INFO_TIMESTEP = 0,
+    CGE_RESTAURANT_INFO_WAITING_CUSTOMERS = 1,
+    CGE_RESTAURANT_INFO_IDLE_WAITERS = 2,
+    CGE_RESTAURANT_INFO_KITCHEN_QUEUE_LENGTH = 3,
+    CGE_RESTAURANT_INFO_READY_ORDERS = 4,
+    CGE_RESTAURANT_INFO_DIRTY_TABLES = 5,
+    CGE_RESTAURANT_INFO_CUSTOMERS_SERVED = 6,
+    CGE_RESTAURANT_INFO_CUSTOMERS_LEFT = 7,
+    CGE_RESTAURANT_INFO_TABLES_CLEANED = 8,
+    CGE_RESTAURANT_INFO_ORDERS_SERVED = 9,
+    CGE_RESTAURANT_INFO_WAIT_TIME_SUM = 10,   /* over everything in the reference's self.customers: waiting, carried by a waiter, */
+    CGE_RESTAURANT_INFO_NUM_CUSTOMERS = 11,   /* seated, and the ghosts a failed seating leaves behind (:312)                    */
+    CGE_RESTAURANT_INFO_TOTAL_REWARD = 12,    /* self.total_reward: the returned rewards plus the completion rewards and -5 per leaver */
+    CGE_RESTAURANT_INFO_NEEDS_RESET = 13
+};
+
+/* RestaurantEnv.__init__ :17-72 */
+int cge_restaurant_create(const cge_restaurant_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_restaurant **out);
+int cge_restaurant_destroy(cge_restaurant *h);
+/* random.seed(s_i) for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Does not reset the envs. */
+int cge_restaurant_seed(cge_restaurant *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :74-93 for envs with mask[i] != 0 (all if NULL); writes the whole slab if obs_out != NULL */
+int cge_restaurant_reset(cge_restaurant *h, const uint8_t *mask, int32_t *obs_out, void *stream);
+/* step :95-175.  actions int32 [n_envs, 4], 16-byte aligned (one load per env; a misaligned pointer is CGE_ERR_INVALID_ARG, here
+ * and in the rollout).  An action outside the action space — a component negative or not below its bound
+ * (4, 10, 50, 10) — has no effect, like the reference's "invalid_*" results (:103-166; the reference would index from the end with a
+ * negative value and ignore a customer_id >= 50 on a serve or clean action), and bumps a device-side counter
+ * (cge_restaurant_error_count); the step itself always runs.
+ * terminated_out is always 0; truncated_out is REQUIRED.  final_obs_out (nullable; a slab): SAME_STEP writes the pieces of every
+ * wave of 64 envs that holds an env truncated in this step; valid where truncated. */
+int cge_restaurant_step(cge_restaurant *h, const int32_t *actions, int32_t *obs_out, float *reward_out, uint8_t *terminated_out,
+                        uint8_t *truncated_out, int32_t *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs, 4], or NULL: column c of env i takes
+ * cge_hash_action(action_seed, env_index0 + i, t0 + t, (4, 10, 50, 10)[c], c).
+ * obs_out: k slabs obs_step_stride ints apart (>= CGE_RESTAURANT_OBS_INTS * n_envs), or with stride 0 the last step's slab.
+ * truncated_traj_out [k, n_envs]; done_count counts truncated steps. */
+int cge_restaurant_rollout(cge_restaurant *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
+                           int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
+                           int32_t *done_count_out, void *stream);
+/* _get_info :478-494 */
+int cge_restaurant_info(cge_restaurant *h, int32_t field_id, double *out, void *stream);
+/* env-steps whose action had a component out of range since the last call; synchronises */
+int64_t cge_restaurant_error_count(cge_restaurant *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_restaurant_snapshot_bytes(const cge_restaurant *h);
+int cge_restaurant_snapshot_get(cge_restaurant *h, void *host_buf, void *stream);
+int cge_restaurant_snapshot_set(cge_restaurant *h, const void *host_buf, void *stream);
+size_t cge_restaurant_device_bytes(const cge_restaurant *h);
+int cge_restaurant_episode_stats(cge_restaurant *h, double *return_out, int32_t *length_out);
+const char *cge_restaurant_last_error(const cge_restaurant *h);
+const char *cge_restaurant_last_kernel(const cge_restaurant *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
 /*   game_logic.py: GameLogic)                                                                    */
 /*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */

@@ -1,0 +1,167 @@
+"""CPU-side checks of the restaurant env: the counts-and-lists model (tests/restaurant_model.py) reproduces, value for value and bit for
+bit, what the unmodified reference recorded (tests/golden/restaurant_*.npz, written by tests/golden/gen/gen_restaurant.py); the C ABI is
+declared, exported and bound; there is no CPU path; the spaces are the reference's."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import restaurant_model as rm
+from conftest import ROOT, golden
+
+FIXTURES = ["restaurant_hash.npz", "restaurant_busy.npz", "restaurant_short.npz", "restaurant_short40.npz", "restaurant_long.npz"]
+ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
+       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_model_reproduces_the_reference(name):
+    z = golden(name)
+    n, T = z["reward"].shape
+    assert json.loads(str(z["info_fields"])) == list(rm.INFO)
+    m = rm.RestaurantModel(int(z["seed0"]) + np.arange(n), int(z["max_episode_steps"]), rm.SAME_STEP)
+    obs = m.reset()
+    for k in rm.KEYS:
+        assert np.array_equal(obs[k], z["obs0_" + k]), k
+    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
+    seen = 0
+    for t in range(T):
+        obs, reward, terminated, truncated, final = m.step(z["actions"][:, t])
+        assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
+        assert not terminated.any() and np.array_equal(truncated, z["truncated"][:, t].astype(bool)), t
+        for k in rm.KEYS:                                                                  # the reference's step() returns the terminal observation
+            assert np.array_equal(final[k], z["obs_" + k][:, t]), (t, k)
+        live = ~truncated                                                                  # (a truncated env has been reset already: checked below)
+        assert np.array_equal(m.info()[live], z["info"][:, t][live]), t
+        assert np.array_equal(bits(m.total_reward()[live]), bits(z["total_reward"][:, t][live])), t
+        for i in np.flatnonzero(truncated):                                                # then reset() continues the env's stream
+            j = where[(int(i), t)]
+            seen += 1
+            for k in rm.KEYS:
+                assert np.array_equal(obs[k][i], z["reset_" + k][j]), (t, i, k)
+    assert seen == len(where) and seen >= (2 * n if T >= 2 * int(z["max_episode_steps"]) else n)
+
+
+@pytest.mark.parametrize("name", ["restaurant_busy.npz", "restaurant_short.npz"])
+def test_model_info_at_the_time_limit(name):
+    """Disabled mode never resets inside step(): the info counters and total_reward of the truncated steps too."""
+    z = golden(name)
+    n, T = z["reward"].shape
+    m = rm.RestaurantModel(int(z["seed0"]) + np.arange(n), int(z["max_episode_steps"]), rm.DISABLED)
+    m.reset()
+    ends = 0
+    for t in range(T):
+        _, reward, _, truncated, _ = m.step(z["actions"][:, t])
+        assert np.array_equal(m.info(), z["info"][:, t]) and np.array_equal(bits(m.total_reward()), bits(z["total_reward"][:, t])), t
+        info = m.info().astype(np.float64)
+        assert np.array_equal(bits(info[:, 10] / np.maximum(info[:, 11], 1.0)), bits(z["average_wait_time"][:, t])), t
+        if truncated.any():
+            assert truncated.all()
+            ends += 1
+            m.reset()
+    assert ends >= 2
+
+
+def test_fixtures_cover_what_they_are_for():
+    h, b, s, s40, lg = (golden(f) for f in FIXTURES)
+    for z in (h, b, s, s40):
+        assert z["reward"].shape[1] >= 1100
+    assert int(h["max_episode_steps"]) == int(b["max_episode_steps"]) == 500 and (h["truncated"].sum(1) >= 2).all()
+    assert int(s["max_episode_steps"]) == 9 and np.array_equal(np.flatnonzero(s["truncated"][0]), np.arange(8, s["reward"].shape[1], 9))
+    assert int(s40["max_episode_steps"]) == 40 and int(lg["max_episode_steps"]) == 1000
+    assert (lg["truncated"].sum(1) == 1).all() and lg["truncated"][:, 999].all() and lg["obs_current_timestep"].max() == 1000
+    assert len(np.unique(h["actions"][..., 2])) == 50 and h["actions"][..., 0].max() == 3
+    assert b["actions"][..., 0].max() == 2 and b["actions"][..., 2].max() == 2 and len(np.unique(b["actions"][..., 3])) == 10
+    events = json.loads(str(b["events"]))
+    assert len(events) == 10 and all(v >= 1 for v in events.values()), events               # every event the dynamics have, at least once
+    rewards = set(b["reward"].ravel().tolist())
+    assert -1.4000000000000001 in rewards and -0.1 in rewards                              # float64 sums in the reference's order, not decimals
+    assert b["obs_waiting_customers"][..., 1].max() == 19 and (b["obs_waiting_customers"][:, :, 21:] == 0).all()
+    assert b["obs_kitchen_queue"][..., 2].max() == 3 and b["info"][..., 3].max() == 3
+    for f in FIXTURES:
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) <= 614 * 1024
+
+
+def test_hash_actions_equal_the_shared_hash():
+    from _hash_actions import common
+    a = rm.hash_actions(77, 5, 6, t0=40, env0=1000)
+    assert a.shape == (5, 6, 4) and a.dtype == np.int32
+    for t in range(5):
+        for i in range(6):
+            assert [int(v) for v in a[t, i]] == [common.hash_action(77, 1000 + i, 40 + t, rm.NVEC[c], c) for c in range(4)]
+    z = golden("restaurant_busy.npz")
+    n = z["reward"].shape[0]
+    assert np.array_equal(rm.busy_actions(int(z["a_seed"]), 30, n).transpose(1, 0, 2), z["actions"][:, :30])
+
+
+def test_kernel_dynamics_replay_the_fixtures_on_the_host():
+    """csrc/restaurant_env.hpp — the record's packing and the step logic the kernels run — compiled for the CPU and replayed over every
+    fixture: rewards and total_reward bit for bit, every observation plane and info counter (tools/probes/restaurant_host_check.py, which
+    takes the PATH's host compiler or the clang++ behind hipcc: the test fails, it does not skip, where neither is there)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probes", "restaurant_host_check.py")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = [line for line in out.stdout.splitlines() if "mismatching" in line]
+    assert len(lines) == len(FIXTURES) and all(line.endswith(" 0 mismatching steps") for line in lines), out.stdout
+
+
+def test_abi_is_declared_exported_and_bound():
+    from custom_gymnasium_environments_amd import _native, build
+    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(cge_restaurant_[a-z0-9_]+)\s*\(", src))
+    assert declared == {f"cge_restaurant_{fn}" for fn in ABI}
+    assert {n for n in _native.SIGNATURES if n.startswith("cge_restaurant_")} == declared
+    build.build_native()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    assert not [n for n in declared if not hasattr(L, n)]
+    assert ctypes.sizeof(_native.RestaurantConfig) == 8
+
+
+def test_no_cpu_path():
+    import torch
+    import custom_gymnasium_environments_amd as cge
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(cge.NativeLibraryError):
+        cge.RestaurantVectorEnv(8)
+    with pytest.raises(cge.NativeLibraryError):
+        cge.RestaurantVectorEnv(8, device="cpu")
+
+
+@pytest.mark.parametrize("name", ["restaurant_hash.npz", "restaurant_long.npz"])
+def test_spaces_equal_the_reference(name):
+    z = golden(name)
+    rec = json.loads(str(z["spaces"]))
+    from custom_gymnasium_environments_amd import restaurant
+    from custom_gymnasium_environments_amd._spaces import batch_space
+    sp, act = restaurant.make_spaces()
+    assert sorted(sp.spaces) == sorted(rec["observation"]) == sorted(rm.KEYS)
+    for k, r in rec["observation"].items():
+        s = sp[k]
+        assert type(s).__name__ == r["kind"] == "Box", k
+        assert tuple(s.shape) == tuple(r["shape"]) == rm.KEY_SHAPES[k], k
+        assert float(s.low.min()) == float(s.low.max()) == r["low"] and float(s.high.min()) == float(s.high.max()) == r["high"], k
+        assert str(s.dtype) == r["dtype"] == "int32", k
+    assert list(rec["action"]) == list(rm.ACTION_KEYS) and sorted(act.spaces) == sorted(rm.ACTION_KEYS)
+    for c, k in enumerate(rm.ACTION_KEYS):
+        assert type(act[k]).__name__ == rec["action"][k]["kind"] == "Discrete" and int(act[k].n) == rec["action"][k]["n"] == rm.NVEC[c], k
+    batched = batch_space(act, 6)                                      # gymnasium's layout: a Dict of MultiDiscrete([n] * N)
+    for c, k in enumerate(rm.ACTION_KEYS):
+        assert [int(v) for v in batched[k].nvec] == [rm.NVEC[c]] * 6, k
+    bo = batch_space(sp, 6)
+    for k in rm.KEYS:
+        assert tuple(bo[k].shape) == (6,) + rm.KEY_SHAPES[k], k
+    assert [name for name, _ in restaurant.PLANES] == list(rm.KEYS) and dict(restaurant.PLANES) == rm.KEY_SHAPES and restaurant.OBS_INTS == 341
+    assert tuple(restaurant.ACTION_KEYS) == rm.ACTION_KEYS and tuple(restaurant.ACTION_NVEC) == rm.NVEC
+    for k in rm.KEYS:                                                  # the recorded observations lie inside the declared bounds, except the
+        lo, hi = float(sp[k].low.min()), float(sp[k].high.max())      # timestep of a 1000-step episode (the reference declares 500 and runs 1000)
+        assert z["obs_" + k].min() >= lo and (z["obs_" + k].max() <= hi or k == "current_timestep"), k

@@ -1,0 +1,36 @@
+"""Waves per SIMD of the restaurant kernels, read from the BUILT library's code-object notes as tests/test_kernel_occupancy.py does (no
+GPU, no recompilation).  The record (eleven uint4 columns, unpacked: the waiting line, ten waiters, ten ready orders, the table
+masks) lives in registers for a whole launch; the fused rollouts hold 16 ready generator words on top.  The floors are what the
+measurements in profiles/restaurant_timing.txt were taken at: the step kernels at three waves per SIMD, the fused rollouts at two."""
+import os
+
+import pytest
+
+from test_kernel_occupancy import LIB, LLVM, _kernels
+
+# mangled-name fragment -> minimum waves per SIMD; template arguments: autoreset mode (0 NextStep, 1 SameStep, 2 Disabled), caller's actions
+FLOORS = {
+    "10restaurant11step_kernelILi0E": 3,
+    "10restaurant11step_kernelILi1E": 3,
+    "10restaurant11step_kernelILi2E": 3,
+    "10restaurant14rollout_kernelILi0ELb1E": 2,
+    "10restaurant14rollout_kernelILi0ELb0E": 2,
+    "10restaurant14rollout_kernelILi1ELb1E": 2,
+    "10restaurant14rollout_kernelILi1ELb0E": 2,
+    "10restaurant14rollout_kernelILi2ELb1E": 2,
+    "10restaurant14rollout_kernelILi2ELb0E": 2,
+}
+
+
+@pytest.mark.skipif(not (os.path.exists(LIB) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))), reason="needs the built library and the ROCm LLVM tools")
+def test_restaurant_kernels_keep_their_waves_per_simd(tmp_path):
+    ks = _kernels(str(tmp_path))
+    seen = set()
+    for name, (vgpr, agpr) in ks.items():
+        for frag, floor in FLOORS.items():
+            if frag in name:
+                seen.add(frag)
+                total = -(-vgpr // 8) * 8 + -(-agpr // 8) * 8
+                waves = min(8, 512 // max(total, 8))
+                assert waves >= floor, f"{name}: {vgpr} + {agpr} registers = {waves} waves per SIMD, the floor is {floor}"
+    assert seen == set(FLOORS), f"kernels not found in the library: {sorted(set(FLOORS) - seen)}"
