@@ -53,8 +53,6 @@ static const int BED_DEPT_FIRST[4] = {0, 8, 14, 18}, BED_DEPT_COUNT[4] = {8, 6, 
 static const int BED_DEPTS[4] = {0, 1, 2, 3};
 static const int TREATMENT[6] = {0, 15, 30, 45, 60, 120};                                 /* treatment_times :148-154 by severity */
 
-static int bed_dept(int b) { return b < 8 ? 0 : b < 14 ? 1 : b < 18 ? 2 : 3; }
-
 static void q_push(henv *e, int d, patient p) { if (e->q[d].n < QCAP) e->q[d].p[e->q[d].n++] = p; else e->overflow += 1; }
 static void q_remove(pqueue *q, int k) { memmove(&q->p[k], &q->p[k + 1], (size_t)(q->n - k - 1) * sizeof(patient)); q->n -= 1; }
 
@@ -205,7 +203,6 @@ static int process_treatments(henv *e) {                                        
             q_remove(&e->q[d], 0);
         }
     }
-    (void)bed_dept;
     return reward;
 }
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, HASH_ROLLOUTS, climate_uniform
 
 pytestmark = pytest.mark.gpu
 
@@ -62,16 +63,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 500, 1500
-    env = cge.ClimateVectorEnv(n, autoreset_mode=mode, env_index0=6)
+    R = RUNS["climate_all_modes"]
+    n, T = R["n"], R["T"]
+    env = cge.ClimateVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.ClimateOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(6 + 80))
-    od, _ = env.reset(seed=80)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert _close(_np(od), o.reset(), 1e-6).all()
-    rng = np.random.default_rng(8)
-    for t in range(T):
-        ac = rng.uniform(10, 38, (n, 1)).astype(np.float32)
-        li = rng.integers(0, 2, (n, 4)).astype(np.int8)
+    for t, (ac, li) in enumerate(climate_uniform("climate", {}, n, T)):
         od, rd, ted, trd, _ = env.step((ac, li))
         oo, ro, teo, tro = o.step(ac, li)
         assert _close(_np(od), oo, 1e-6).all(), t
@@ -83,29 +82,28 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode):
     env.close()
 
 
-@pytest.mark.parametrize("max_occupancy,minutes", [(1, 77), (15, 200)])
+@pytest.mark.parametrize("max_occupancy,minutes", RUNS["climate_knobs"]["cases"])
 def test_constructor_knobs_match_oracle(cge, oracle, max_occupancy, minutes):
     """max_occupancy / episode_minutes (smartclimate/env.py:16-28) against the oracle built with the same values: step() through
     several episodes, then the fused rollout; occupancy reaches its bound."""
-    n = 300
-    env = cge.ClimateVectorEnv(n, autoreset_mode="SameStep", env_index0=2, max_occupancy=max_occupancy, episode_minutes=minutes)
+    R = RUNS["climate_knobs"]
+    n = R["n"]
+    env = cge.ClimateVectorEnv(n, autoreset_mode="SameStep", env_index0=R["env0"], max_occupancy=max_occupancy, episode_minutes=minutes)
     o = oracle.ClimateOracle(n, oracle.SAME_STEP, max_steps=minutes, max_occupancy=max_occupancy)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(2 + 19))
-    od, _ = env.reset(seed=19)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert _close(_np(od), o.reset(), 1e-6).all()
-    rng = np.random.default_rng(3)
     top = 0
-    for t in range(2 * minutes + 5):
-        ac = rng.uniform(10, 38, (n, 1)).astype(np.float32)
-        li = rng.integers(0, 2, (n, 4)).astype(np.int8)
+    for t, (ac, li) in enumerate(climate_uniform("climate", dict(max_occupancy=max_occupancy), n, 2 * minutes + 5, seed=3)):
         od, rd, ted, _, _ = env.step((ac, li))
         oo, ro, teo, _ = o.step(ac, li)
         assert _close(_np(od), oo, 1e-6).all() and np.array_equal(_np(od)[:, 1], oo[:, 1]), t
         assert _close(_np(rd), ro, 1e-4).all() and np.array_equal(_np(ted), teo.astype(bool)), t
         top = max(top, int(oo[:, 1].max()))
     assert top == max_occupancy and int(o.info("episodes").min()) == 2
-    obs, rs, dc = env.rollout(150, action_seed=4, t0=1)
-    oo, ro, do = o.rollout(150, 4, t0=1, env0=2)
+    a_seed, t0, env0, k = R["rollout"]
+    obs, rs, dc = env.rollout(k, action_seed=a_seed, t0=t0)
+    oo, ro, do = o.rollout(k, a_seed, t0=t0, env0=env0)
     assert _close(_np(obs), oo, 1e-6).all() and np.array_equal(_np(dc), do) and np.allclose(_np(rs), ro, rtol=1e-9, atol=1e-6)
     env.close()
     with pytest.raises(Exception):
@@ -113,7 +111,7 @@ def test_constructor_knobs_match_oracle(cge, oracle, max_occupancy, minutes):
 
 
 def test_rollout_config5_size_and_sharding(cge, oracle):
-    n, T = 1 << 17, 300
+    n, T = 1 << 17, HASH_ROLLOUTS["config5"]["k"]["climate"]
     env = cge.ClimateVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     env.reset(seed=0)
     obs, rs, dc = env.rollout(T, action_seed=123)

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, CRYPTO_KNOBS, crypto_uniform
 
 pytestmark = pytest.mark.gpu
 OBS_RTOL, OBS_ATOL = 4e-7, 2e-6
@@ -83,16 +84,15 @@ def test_matches_reference_fixture(cge, name):
                                        ("continuous", "SameStep")])
 def test_step_matches_oracle(cge, oracle, kind, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 200, 1100
-    env = cge.CryptoVectorEnv(n, action_type=kind, autoreset_mode=mode, env_index0=3)
+    R = RUNS["crypto_step"]
+    n, T = R["n"], R["T"]
+    env = cge.CryptoVectorEnv(n, action_type=kind, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.CryptoOracle(n, kind, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(3 + 70))
-    od, _ = env.reset(seed=70)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert _close_obs(_np(od), o.reset()).all()
-    rng = np.random.default_rng(2)
     diverged = np.zeros(n, bool)
-    for t in range(T):
-        a = (rng.uniform(-1, 1, (n, 2)).astype(np.float32) if kind == "continuous" else rng.integers(0, 5, n).astype(np.int32))
+    for t, a in enumerate(crypto_uniform("crypto", dict(action_type=kind), n, T)):
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         od, rd, ted = _np(od), _np(rd), _np(ted)
@@ -115,19 +115,17 @@ def test_step_matches_oracle(cge, oracle, kind, mode):
 def test_config_knobs_step_and_rollout_match_oracle(cge, oracle):
     """every TradingConfig field the constructor forwards (crypto_trading_env.py:28-38) against the oracle built with the
     same config — step() in two autoreset modes, then the fused rollout (reward sums, done counts, final observation)."""
-    config = dict(initial_balance=400.0, trading_fee_rate=0.004, slippage_rate=0.002, min_price=5000.0, max_price=80000.0,
-                  volatility_base=0.05, market_psychology_factor=0.3)
-    n = 257
+    config = dict(CRYPTO_KNOBS)
+    R = RUNS["crypto_config_knobs"]
+    n = R["n"]
     for mode, code in [("SameStep", oracle.SAME_STEP), ("NextStep", oracle.NEXT_STEP)]:
-        env = cge.CryptoVectorEnv(n, autoreset_mode=mode, config=config, max_steps=120)
-        o = oracle.CryptoOracle(n, "discrete", code, max_steps=120, config=config)
-        o.seed(np.arange(n, dtype=np.uint64) + np.uint64(11))
-        od, _ = env.reset(seed=11)
+        env = cge.CryptoVectorEnv(n, autoreset_mode=mode, config=config, max_steps=R["limit"])
+        o = oracle.CryptoOracle(n, "discrete", code, max_steps=R["limit"], config=config)
+        o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["seed"]))
+        od, _ = env.reset(seed=R["seed"])
         assert _close_obs(_np(od), o.reset()).all()
-        rng = np.random.default_rng(5)
         diverged = np.zeros(n, bool)
-        for t in range(300):
-            a = rng.integers(0, 5, n).astype(np.int32)
+        for t, a in enumerate(crypto_uniform("crypto", dict(action_type="discrete"), n, R["T"], seed=5)):
             od, rd, ted, _, _ = env.step(a)
             oo, ro, teo, _ = o.step(a)
             diverged |= ~np.isclose(_np(env.info("current_price")), o.info("current_price"), rtol=1e-9, atol=0)
@@ -135,8 +133,9 @@ def test_config_knobs_step_and_rollout_match_oracle(cge, oracle):
             assert np.array_equal(_np(ted)[ok], teo.astype(bool)[ok]), (mode, t)
             assert _close_obs(_np(od)[ok], oo[ok]).all() and _close_rew(_np(rd)[ok], ro[ok]).all(), (mode, t)
         assert int(diverged.sum()) <= 1
-        obs, rs, dc = env.rollout(200, action_seed=9, t0=0)
-        oo, ro, do = o.rollout(200, 9, t0=0, env0=0)
+        a_seed, t0, env0, k = R["rollout"]
+        obs, rs, dc = env.rollout(k, action_seed=a_seed, t0=t0)
+        oo, ro, do = o.rollout(k, a_seed, t0=t0, env0=env0)
         ok = ~diverged
         assert np.array_equal(_np(dc)[ok], do[ok]) and int(do.sum()) > n          # several episodes per env
         assert np.allclose(_np(rs)[ok], ro[ok], rtol=1e-6, atol=1e-2)

@@ -12,13 +12,14 @@ import numpy as np
 import pytest
 import torch
 
+from _action_streams import RUNS, HASH_ROLLOUTS, final_obs_actions as _random_actions
 from _hash_actions import at, hash_actions
 from test_edges_gpu import _rows_ok
 from test_oracle_hash_rollout import make_oracle
 
 pytestmark = pytest.mark.gpu
 
-ENV0, SEED, A_SEED, T0 = 3, 19, 0x5EED, 777
+ENV0, SEED, A_SEED, T0 = RUNS["final_obs"]["env0"], RUNS["final_obs"]["seed"], HASH_ROLLOUTS["final_obs"]["a_seed"], HASH_ROLLOUTS["final_obs"]["t0"]
 VIEWS = ["trajectory", "last_obs", "no_obs"]
 
 # id: (env type, VectorEnv class, device kwargs, oracle class, oracle kwargs; the same short time limit on both sides, helper kwargs)
@@ -66,15 +67,6 @@ def _device_kwargs(dkw):
         from test_oracle_hash_rollout import crypto_config
         return dict(dkw, config=crypto_config())
     return dkw
-
-
-def _random_actions(name, hkw, k, n, rng):
-    if name == "climate":
-        return rng.uniform(10, 38, (k, n)).astype(np.float32), rng.integers(0, 2, (k, n, 4)).astype(np.int8)
-    if name == "crypto" and hkw.get("continuous"):
-        return rng.uniform(-1, 1, (k, n, 2)).astype(np.float32)
-    shape = {"traffic": (hkw.get("ni", 9),), "fleet": (3,)}.get(name, ())
-    return rng.integers(0, NACT[name], (k, n) + shape).astype(np.int32)
 
 
 def _dev(a):
@@ -221,7 +213,7 @@ def _run(s, actions, view, k, rows_per_env=None, per_step=None):
     return exp, out
 
 
-def _matrix(cge, oracle, case, actions, view, k=80):
+def _matrix(cge, oracle, case, actions, view, k=RUNS["final_obs"]["k"]):
     s = Setup(cge, oracle, case)
     what = (s.name, s.dkw, actions, view)
     acts = _random_actions(s.name, s.hkw, k, s.n, np.random.default_rng(k)) if actions == "explicit" else None

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, HASH_ROLLOUTS, fleet_uniform
 
 pytestmark = pytest.mark.gpu
 
@@ -52,17 +53,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 400, 900
-    env = cge.FleetVectorEnv(n, autoreset_mode=mode, env_index0=1)
+    R = RUNS["fleet_all_modes"]
+    n, T = R["n"], R["T"]
+    env = cge.FleetVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.FleetOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(1 + 30))
-    od, _ = env.reset(seed=30)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(3)
-    for t in range(T):
-        a = rng.integers(0, 8, (n, 3)).astype(np.int32)
-        if t % 11 == 0:
-            a[rng.random((n, 3)) < 0.02] = 9                      # invalid action: -10
+    for t, a in enumerate(fleet_uniform("fleet", {}, n, T)):         # uniform, with a few invalid actions (-10) every 11th step
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), t
@@ -74,7 +72,7 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode):
 
 
 def test_rollout_config5_size_and_sharding(cge, oracle):
-    n, T = 1 << 17, 300
+    n, T = 1 << 17, HASH_ROLLOUTS["config5"]["k"]["fleet"]
     env = cge.FleetVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     env.reset(seed=0)
     obs, rs, dc = env.rollout(T, action_seed=123)

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, HASH_ROLLOUTS, hospital_biased
 
 pytestmark = pytest.mark.gpu
 
@@ -55,21 +56,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 300, 1600 if mode != "Disabled" else 1300
-    env = cge.HospitalVectorEnv(n, autoreset_mode=mode, env_index0=1)
+    R = RUNS["hospital_all_modes"]
+    n, T = R["n"], R["T"] if mode != "Disabled" else R["T_disabled"]
+    env = cge.HospitalVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.HospitalOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(1 + 30))
-    od, _ = env.reset(seed=30)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(3)
-    bias = rng.integers(0, 3, n)                                   # a third each: uniform / mass-casualty heavy / staffing heavy
-    for t in range(T):
-        a = rng.integers(0, 35, n).astype(np.int32)
-        r = rng.random(n)
-        a = np.where((bias == 1) & (r < 0.5), 33, a)
-        a = np.where((bias == 2) & (r < 0.5), rng.integers(0, 12, n), a).astype(np.int32)
-        if t % 13 == 0:
-            a[rng.random(n) < 0.02] = 40                            # out of range: no-op
+    for t, a in enumerate(hospital_biased("hospital", {}, n, T)):    # a third of the envs each: uniform / mass-casualty heavy / staffing heavy
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), (t, np.argwhere(_np(od) != oo)[:8])
@@ -96,7 +90,7 @@ def test_reset_mask_returns_every_row(cge, oracle):
 
 
 def test_rollout_config5_size_and_sharding(cge, oracle):
-    n, T = 1 << 17, 200
+    n, T = 1 << 17, HASH_ROLLOUTS["config5"]["k"]["hospital"]
     env = cge.HospitalVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     env.reset(seed=0)
     obs, rs, dc = env.rollout(T, action_seed=123)

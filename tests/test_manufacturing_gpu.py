@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, HASH_ROLLOUTS, manufacturing_biased
 
 pytestmark = pytest.mark.gpu
 
@@ -56,22 +57,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 300, 1700 if mode != "Disabled" else 1400
-    env = cge.ManufacturingVectorEnv(n, autoreset_mode=mode, env_index0=1)
+    R = RUNS["manufacturing_all_modes"]
+    n, T = R["n"], R["T"] if mode != "Disabled" else R["T_disabled"]
+    env = cge.ManufacturingVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.ManufacturingOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(1 + 30))
-    od, _ = env.reset(seed=30)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(3)
-    bias = rng.integers(0, 4, n)                                   # a quarter of the envs each: uniform / type A heavy / start heavy / quality mode
-    for t in range(T):
-        a = rng.integers(0, 25, n).astype(np.int32)
-        r = rng.random(n)
-        a = np.where((bias == 1) & (r < 0.7), 0, a)
-        a = np.where((bias == 2) & (r < 0.6), rng.integers(0, 6, n), a)
-        a = np.where((bias == 3) & (r < 0.3), 23, a).astype(np.int32)
-        if t % 13 == 0:
-            a[rng.random(n) < 0.02] = 31                            # out of range: no branch taken
+    for t, a in enumerate(manufacturing_biased("manufacturing", {}, n, T)):   # a quarter each: uniform / type A heavy / start heavy / quality mode
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), (t, np.argwhere(_np(od) != oo)[:5])
@@ -82,7 +75,7 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode):
 
 
 def test_rollout_config5_size_and_sharding(cge, oracle):
-    n, T = 1 << 17, 300
+    n, T = 1 << 17, HASH_ROLLOUTS["config5"]["k"]["manufacturing"]
     env = cge.ManufacturingVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     env.reset(seed=0)
     obs, rs, dc = env.rollout(T, action_seed=123)

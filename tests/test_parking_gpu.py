@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, HASH_ROLLOUTS, parking_assign_biased
 
 pytestmark = pytest.mark.gpu
 
@@ -56,16 +57,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 300, 1600
-    env = cge.ParkingVectorEnv(n, autoreset_mode=mode, env_index0=4)
+    R = RUNS["parking_all_modes"]
+    n, T = R["n"], R["T"]
+    env = cge.ParkingVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.ParkingOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(4 + 60))
-    od, _ = env.reset(seed=60)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(6)
-    for t in range(T):
-        a = rng.integers(0, 8, n).astype(np.int32)
-        a[rng.random(n) < 0.5] = rng.integers(1, 4)            # bias toward assignments so the lot fills up
+    for t, a in enumerate(parking_assign_biased("parking", {}, n, T)):   # biased toward assignments so the lot fills up
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), t
@@ -79,7 +78,7 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode):
 
 def test_rollout_and_config5_size(cge, oracle):
     """BASELINE config 5 share: 131,072 envs; rollout bit-exact vs the oracle on slices, sharding invariant."""
-    n, T = 1 << 17, 400
+    n, T = 1 << 17, HASH_ROLLOUTS["config5"]["k"]["parking"]
     env = cge.ParkingVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     obs, _ = env.reset(seed=0)
     obs, rs, dc = env.rollout(T, action_seed=123)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, SNAKE_GRIDS, snake_uniform
 
 pytestmark = pytest.mark.gpu
 
@@ -54,19 +55,18 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 # every grid_size the library compiles (4..30): even and odd, below and above the 144-cell switch to 64-thread workgroups, grids whose
 # obs row is narrower than a digit ring (4, 5), the reference scripts' 15 (test_visualization.py:17) and the largest
-@pytest.mark.parametrize("grid,n", [(10, 1000), (6, 77), (16, 130), (20, 65), (15, 200), (4, 70), (5, 129), (7, 300), (13, 66), (23, 65), (30, 70)])
+@pytest.mark.parametrize("grid,n", SNAKE_GRIDS)
 def test_step_matches_oracle_all_modes(cge, oracle, mode, grid, n):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    env = cge.SnakeVectorEnv(n, grid_size=grid, autoreset_mode=mode, env_index0=5)
+    R = RUNS["snake_all_modes"]
+    env = cge.SnakeVectorEnv(n, grid_size=grid, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.SnakeOracle(n, grid, code)
-    seeds = np.arange(n, dtype=np.uint64) + np.uint64(5 + 900)
+    seeds = np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"])
     o.seed(seeds)
-    obs_d, _ = env.reset(seed=900)
+    obs_d, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(obs_d), o.reset())
-    rng = np.random.default_rng(1)
     same = mode == "SameStep"
-    for t in range(300):
-        a = rng.integers(0, 4, n).astype(np.int32)
+    for t, a in enumerate(snake_uniform("snake", dict(grid_size=grid), n, R["T"])):
         od, rd, ted, trd, info = env.step(a)
         res = o.step(a, want_final=same)
         oo, ro, teo, tro = res[:4]

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import golden
+from _action_streams import RUNS, TRAFFIC_LAYOUTS, traffic_sparse
 
 pytestmark = pytest.mark.gpu
 
@@ -60,17 +61,14 @@ def test_same_step_matches_reference_fixture(cge, name):
 @pytest.mark.parametrize("mode", ["NextStep", "SameStep", "Disabled"])
 def test_step_matches_oracle_all_modes(cge, oracle, mode):
     code = {"NextStep": oracle.NEXT_STEP, "SameStep": oracle.SAME_STEP, "Disabled": oracle.DISABLED}[mode]
-    n, T = 333, 1100
-    env = cge.TrafficVectorEnv(n, autoreset_mode=mode, env_index0=2)
+    R = RUNS["traffic_all_modes"]
+    n, T = R["n"], R["T"]
+    env = cge.TrafficVectorEnv(n, autoreset_mode=mode, env_index0=R["env0"])
     o = oracle.TrafficOracle(n, code)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(2 + 40))
-    od, _ = env.reset(seed=40)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(4)
-    for t in range(T):
-        a = rng.integers(0, 3, (n, 9)).astype(np.int32)
-        if t % 3:
-            a[rng.random((n, 9)) < 0.8] = 0            # long stretches on the lights' own random timers
+    for t, a in enumerate(traffic_sparse("traffic", {}, n, T)):      # long stretches on the lights' own random timers
         od, rd, ted, trd, _ = env.step(a)
         oo, ro, teo, tro = o.step(a)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), t
@@ -84,21 +82,7 @@ def test_step_matches_oracle_all_modes(cge, oracle, mode):
     env.close()
 
 
-LAYOUTS = [dict(grid_size=(3, 3), num_intersections=4, max_vehicles=20, spawn_rate=0.4),          # simple_test.py:71-76
-           dict(grid_size=(6, 6), num_intersections=16, max_vehicles=80, spawn_rate=0.5),         # USAGE_EXAMPLES.md:32-38
-           dict(grid_size=(2, 7), num_intersections=9, max_vehicles=5, spawn_rate=0.9),           # a non-square grid, a tight vehicle cap
-           dict(grid_size=(2, 2), num_intersections=9, max_vehicles=127, spawn_rate=1.0),         # clamped to 4 intersections; always spawns
-           dict(grid_size=(5, 5), num_intersections=9, max_vehicles=50, spawn_rate=0.0),          # never spawns
-           # intersection counts none of the reference's scripts use (run-time-NI kernels, one per slot count): np.var's pairwise order
-           # below 8 terms, at 8, and with a remainder after the 8-accumulator block; route lengths 2, 2..3, 2..5
-           dict(grid_size=(1, 2), num_intersections=2, max_vehicles=30, spawn_rate=0.6),
-           dict(grid_size=(2, 3), num_intersections=3, max_vehicles=30, spawn_rate=0.5),
-           dict(grid_size=(4, 4), num_intersections=5, max_vehicles=40, spawn_rate=0.5),
-           dict(grid_size=(3, 3), num_intersections=7, max_vehicles=40, spawn_rate=0.5),
-           dict(grid_size=(3, 3), num_intersections=8, max_vehicles=40, spawn_rate=0.5),
-           dict(grid_size=(5, 4), num_intersections=12, max_vehicles=60, spawn_rate=0.5),
-           dict(grid_size=(4, 5), num_intersections=13, max_vehicles=60, spawn_rate=0.5),
-           dict(grid_size=(5, 5), num_intersections=15, max_vehicles=60, spawn_rate=0.5)]
+LAYOUTS = TRAFFIC_LAYOUTS
 
 
 @pytest.mark.parametrize("ctor", LAYOUTS, ids=lambda c: f"{c['grid_size'][0]}x{c['grid_size'][1]}_{c['num_intersections']}_{c['max_vehicles']}_{c['spawn_rate']}")
@@ -106,28 +90,27 @@ def test_layouts_and_knobs_match_oracle(cge, oracle, ctor):
     """Every constructor argument the reference takes (environment.py:62-83) against the oracle built with the same ones:
     step() with explicit actions in SameStep mode through a short time limit, then the fused rollout on top, a state round
     trip through the oracle, and the rollout's trajectory against step() on a twin."""
-    n, limit = 200, 90
-    env = cge.TrafficVectorEnv(n, autoreset_mode="SameStep", env_index0=5, max_steps=limit, **ctor)
+    R = RUNS["traffic_layouts"]
+    n, limit = R["n"], R["limit"]
+    env = cge.TrafficVectorEnv(n, autoreset_mode="SameStep", env_index0=R["env0"], max_steps=limit, **ctor)
     o = oracle.TrafficOracle(n, oracle.SAME_STEP, max_steps=limit, **ctor)
     ni = env.num_intersections
     assert ni == o.ni and env.obs_dim == o.obs_dim == 14 * ni + 4
     assert env.single_action_space.nvec.shape == (ni,) and env.single_observation_space.shape == (env.obs_dim,)
-    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(5 + 21))
-    od, _ = env.reset(seed=21)
+    o.seed(np.arange(n, dtype=np.uint64) + np.uint64(R["env0"] + R["seed"]))
+    od, _ = env.reset(seed=R["seed"])
     assert np.array_equal(_np(od), o.reset())
-    rng = np.random.default_rng(8)
-    for t in range(2 * limit + 10):
-        a = rng.integers(0, 3, (n, ni)).astype(np.int32)
-        if t % 3:
-            a[rng.random((n, ni)) < 0.8] = 0
+    for t, a in enumerate(traffic_sparse("traffic", ctor, n, 2 * limit + 10, seed=8)):
+        assert a.shape == (n, ni)
         od, rd, ted, _, info = env.step(a)
         oo, ro, teo, _, fo = o.step(a, want_final=True)
         assert np.array_equal(_np(od).view(np.uint32), oo.view(np.uint32)), t
         assert np.array_equal(_np(rd), ro) and np.array_equal(_np(ted), teo.astype(bool)), t
         done = teo.astype(bool)
         assert np.array_equal(_np(info["final_obs"])[done], fo[done]), t
-    obs, rs, dc = env.rollout(150, action_seed=9, t0=3)
-    oo, ro, do = o.rollout(150, 9, t0=3, env0=5)
+    a_seed, t0, env0, k = R["rollout"]
+    obs, rs, dc = env.rollout(k, action_seed=a_seed, t0=t0)
+    oo, ro, do = o.rollout(k, a_seed, t0=t0, env0=env0)
     assert np.array_equal(_np(obs), oo) and np.array_equal(_np(rs), ro) and np.array_equal(_np(dc), do) and do.min() >= 1
     assert np.array_equal(_np(env.total_reward()), o.total_reward())
     for q in range(4 * ni):
@@ -138,7 +121,7 @@ def test_layouts_and_knobs_match_oracle(cge, oracle, ctor):
         assert int(env.info("num_vehicles").max()) == 0
     o2 = oracle.TrafficOracle(n, oracle.SAME_STEP, max_steps=limit, **ctor)
     o2.set_state(env.get_state())
-    twin = cge.TrafficVectorEnv(n, autoreset_mode="SameStep", env_index0=5, max_steps=limit, **ctor)
+    twin = cge.TrafficVectorEnv(n, autoreset_mode="SameStep", env_index0=R["env0"], max_steps=limit, **ctor)
     twin.set_state(o2.get_state())
     assert np.array_equal(twin.get_state(), env.get_state())
     acts = torch.randint(0, 3, (40, n, ni), dtype=torch.int32, device="cuda")
