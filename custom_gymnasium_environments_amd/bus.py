@@ -4,7 +4,8 @@ import torch
 
 from . import _native
 from ._spaces import Box, Dict, Discrete, MultiBinary, MultiDiscrete
-from .vector_env import TRUNCATED, DeviceVectorEnv
+from ._slab import SlabVectorEnv, packed_planes
+from .vector_env import TRUNCATED
 
 INFO_FIELDS = {"timestep": 0, "total_delivered": 1, "total_waiting": 2, "total_onboard": 3, "bus_position": 4, "bus_stopped": 5,
                "bus_capacity": 6, "stop_waiting": 7, "needs_reset": 8}
@@ -34,7 +35,7 @@ def make_spaces(max_timesteps=500):
     return observation, MultiDiscrete([MAX_DWELL_TIME + 1] * NUM_BUSES)
 
 
-class BusVectorEnv(DeviceVectorEnv):
+class BusVectorEnv(SlabVectorEnv):
     """N independent BusSystemEnv instances (4 buses on a ring of 4 stops, 50..150 passengers per episode, 500 steps) stepped by one
     HIP kernel launch.  Spaces as the reference: `MultiDiscrete([11] * 4)` actions (the dwell time each bus takes when it next
     arrives at a stop, :82) and the `Dict` observation of :94-123 with its eleven keys and bounds.  Bit-exact with the reference.
@@ -56,10 +57,11 @@ class BusVectorEnv(DeviceVectorEnv):
 
     _abi = "cge_bus"
     INFO_FIELDS = INFO_FIELDS
-    _obs_dtype = torch.int32
     _action_shape = (NUM_BUSES,)
     _flags = TRUNCATED
     _info_dtype, _info_indexed = torch.int32, True
+    # an env-step refused for a dwell time outside 0..10 (reference: ValueError, :160-161)
+    _invalid_action_text = f"Invalid action in {{n}} env-step(s): must be {NUM_BUSES} integers 0-{MAX_DWELL_TIME}"
     metadata = {"render_modes": []}
 
     def __init__(self, num_envs, device="cuda:0", autoreset_mode="NextStep", env_index0=0, max_timesteps=500, reuse_buffers=False,
@@ -67,34 +69,8 @@ class BusVectorEnv(DeviceVectorEnv):
         self._init_common(num_envs, device, autoreset_mode, env_index0, reuse_buffers)
         self.max_timesteps = int(max_timesteps)
         self.single_observation_space, self.single_action_space = make_spaces(self.max_timesteps)
-        self._slab = self.num_envs * OBS_INTS
-        self._obs_shape = (self._slab,)                                  # one flat slab per step, not [N, ...]
-        self._views = {}
+        self._init_slab(*packed_planes(PLANES, self.num_envs), torch.int32)   # int32 [56 * N] per step
         self._create(_native.BusConfig(self.max_timesteps, self._mode_code), info_fields, record_episode_statistics, reference_info)
-
-    # ------------------------------------------------------------------ the slab and its per-key views
-    def _dict(self, slab):
-        """slab int32 [56 * N] or [k, 56 * N] -> {key: view [N, ...] or [k, N, ...]}.  The dict of a persistent buffer is built once."""
-        key = (slab.data_ptr(), tuple(slab.shape)) if self._reuse else None
-        d = self._views.get(key) if key is not None else None
-        if d is None:
-            n, d, o = self.num_envs, {}, 0
-            for name, shape in PLANES:
-                w = n * int(np.prod(shape))
-                d[name] = slab[..., o:o + w].view(slab.shape[:-1] + (n,) + shape)
-                o += w
-            if key is not None:
-                self._views = {k: v for k, v in self._views.items() if k[0] != key[0]}       # a regrown buffer drops its old views
-                self._views[key] = d
-        return dict(d)
-
-    _wrap_obs = _dict
-
-    def obs_slab(self, obs):
-        """The flat int32 slab ([56 * N], or [k, 56 * N] for a trajectory) behind an observation dict of this env."""
-        first = obs["bus_stops"]
-        lead = first.shape[:-2]
-        return torch.as_strided(first, lead + (self._slab,), tuple(first.stride()[:len(lead)]) + (1,), first.storage_offset())
 
     # ------------------------------------------------------------------ extras
     def reference_info(self):
@@ -108,12 +84,3 @@ class BusVectorEnv(DeviceVectorEnv):
                 "total_waiting": self.info("total_waiting"), "total_onboard": self.info("total_onboard"),
                 "bus_positions": per("bus_position"), "bus_states": per("bus_stopped"), "bus_capacities": per("bus_capacity"),
                 "stop_waiting": per("stop_waiting")}
-
-    def invalid_action_count(self):
-        """Synchronises; number of env-steps refused for a dwell time outside 0..10 since the last call (reference: ValueError)."""
-        return int(self._lib.cge_bus_error_count(self._h, self._stream()))
-
-    def check_actions(self):
-        n = self.invalid_action_count()
-        if n:
-            raise ValueError(f"Invalid action in {n} env-step(s): must be {NUM_BUSES} integers 0-{MAX_DWELL_TIME}")   # :160-161

@@ -26,8 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "cge_device.hpp"
-#include "cge_host.hpp"
+#include "cge_lane.hpp"
 
 namespace cge {
 namespace bus {
@@ -46,25 +45,11 @@ constexpr int DRAW_RUN = 16;     // ready words fetched per round of the reset's
 constexpr int P_STOPS = 0, P_STATES = 4, P_REMAINING = 8, P_CAPACITIES = 12, P_BUS_DEST = 16, P_WAITING = 32, P_STOP_DEST = 36,
               P_TIMESTEP = 52, P_DELIVERED = 53, P_TOTAL_WAITING = 54, P_TOTAL_ONBOARD = 55;
 
-struct Params {
-    uint4 *state;
-    uint32_t *mt;
-    int64_t n, env0;
+struct Params : LaneParams<int32_t> {
     int32_t max_t;
-    const int32_t *actions;
-    const uint8_t *mask;
-    int32_t *obs, *final_obs;
-    float *reward;
-    uint8_t *terminated, *truncated;
-    int32_t k_steps;
-    uint64_t a_seed;
-    int64_t t0, obs_step_stride;
-    double *reward_sum;
-    int32_t *done_count;
-    double *ep_ret;       // episode statistics (cge_bus_episode_stats), nullable
-    int32_t *ep_len;
-    unsigned long long *err_count;
+    static constexpr bool terminates = false;                       // truncated after max_t steps; terminated is never set (:156)
 };
+static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
 
 __device__ __forceinline__ uint32_t bsum(uint32_t x) { return (x & 255u) + ((x >> 8) & 255u) + ((x >> 16) & 255u) + (x >> 24); }
 // a[i] for a runtime i in 0..3, mask form (a ternary over array elements becomes "select the address, then load": scratch)
@@ -263,12 +248,7 @@ __device__ __forceinline__ void run(const Params &p) {
                 } else {
                     trunc = env_step(e, p.max_t, a, r2);
                     e.ret2 += r2;
-                    if (trunc) {
-                        if (p.ep_ret) p.ep_ret[i] = 0.5 * (double)e.ret2;
-                        if (p.ep_len) p.ep_len[i] = (int32_t)e.t;
-                        if (MODE == CGE_AUTORESET_SAME_STEP) reset_now = true;
-                        else if (MODE == CGE_AUTORESET_NEXT_STEP) e.needs_reset = 1;
-                    }
+                    if (trunc) lane_episode_end<MODE>(p, i, 0.5 * (double)e.ret2, (int32_t)e.t, reset_now, e.needs_reset);
                 }
             }
         }
@@ -279,7 +259,7 @@ __device__ __forceinline__ void run(const Params &p) {
             if (__ballot(reset_now)) env_reset(e, blk, reset_now);
         }
         if (live) {
-            if (p.obs && (!ROLLOUT || p.obs_step_stride != 0 || t == ksteps - 1)) observe(e, p.obs + (int64_t)t * p.obs_step_stride, p.n, i);
+            if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, p.obs + (int64_t)t * p.obs_step_stride, p.n, i);
             const float reward = 0.5f * (float)r2;                  // multiples of 0.5 below 2^24: exact
             if (ROLLOUT) {
                 rsum += (double)reward;
@@ -287,18 +267,13 @@ __device__ __forceinline__ void run(const Params &p) {
                 if (p.reward) p.reward[(int64_t)t * p.n + i] = reward;
                 if (p.truncated) p.truncated[(int64_t)t * p.n + i] = trunc ? 1 : 0;
             } else {
-                p.reward[i] = reward;
-                p.terminated[i] = 0;                                // :156, never set
-                p.truncated[i] = trunc ? 1 : 0;
+                lane_step_outputs(p, i, reward, trunc);
             }
         }
     }
     if (live) {
         e.store(p.state, p.n, i);
-        if (ROLLOUT) {
-            if (p.reward_sum) p.reward_sum[i] = rsum;
-            if (p.done_count) p.done_count[i] = dcount;
-        }
+        if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
 }
 
@@ -355,19 +330,24 @@ __global__ __launch_bounds__(256) void info_kernel(const uint4 *__restrict__ sta
 
 using namespace cge;
 
-struct cge_bus : HandleBase {
+struct cge_bus : LaneHandle {
+    using Params = bus::Params;
     cge_bus_config cfg{};
-    uint4 *state = nullptr;
-    uint32_t *mt = nullptr;
-    unsigned long long *err = nullptr;
     static constexpr uint32_t snap_tag = 6u;
-    bus::Params params() const {
-        bus::Params p{};
-        p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.max_t = cfg.max_timesteps; p.err_count = err;
-        p.ep_ret = ep_ret; p.ep_len = ep_len;
+    static constexpr const char *abi = "cge_bus", *kernel_ns = "cge::bus::";
+    static constexpr int block = bus::BLOCK, seed_kind = 0;
+    Params params() const {
+        Params p{};
+        fill(p);
+        p.max_t = cfg.max_timesteps;
         return p;
     }
-    unsigned blocks() const { return (unsigned)((n + bus::BLOCK - 1) / bus::BLOCK); }
+    int64_t step_elems() const { return n * bus::OBS; }
+    auto reset_kernel() const { return bus::reset_kernel; }
+    template <int MODE>
+    auto kernel(LaneKind kind) const {
+        return kind == LANE_STEP ? bus::step_kernel<MODE> : kind == LANE_ROLLOUT_GIVEN ? bus::rollout_kernel<MODE, true> : bus::rollout_kernel<MODE, false>;
+    }
     static int check(const cge_bus_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 0 || c.max_timesteps > 60000 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
@@ -377,71 +357,32 @@ struct cge_bus : HandleBase {
         CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
         CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
         CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
-        hipLaunchKernelGGL(bus::reset_kernel, dim3(blocks()), dim3(bus::BLOCK), 0, nullptr, params(), 1, 0);
+        lane_launch_reset(this, params(), 1, 0, nullptr);
         return hipGetLastError();
     }
 };
-
-template <int MODE>
-static void launch_bus(cge_bus *h, const bus::Params &p, int kind, hipStream_t s) {
-    const dim3 grid(h->blocks()), block(bus::BLOCK);
-    if (kind == 0) hipLaunchKernelGGL(bus::step_kernel<MODE>, grid, block, 0, s, p);
-    else if (kind == 1) hipLaunchKernelGGL((bus::rollout_kernel<MODE, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((bus::rollout_kernel<MODE, false>), grid, block, 0, s, p);
-}
-static void launch_bus(cge_bus *h, const bus::Params &p, int kind, hipStream_t s) {
-    if (h->cfg.autoreset_mode == CGE_AUTORESET_NEXT_STEP) launch_bus<CGE_AUTORESET_NEXT_STEP>(h, p, kind, s);
-    else if (h->cfg.autoreset_mode == CGE_AUTORESET_SAME_STEP) launch_bus<CGE_AUTORESET_SAME_STEP>(h, p, kind, s);
-    else launch_bus<CGE_AUTORESET_DISABLED>(h, p, kind, s);
-}
 
 extern "C" {
 
 CGE_DEFINE_LIFECYCLE(bus)
 
-int cge_bus_seed(cge_bus *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, as_stream(stream), h->params(), 0, 1);   // rewind cursors
-    return launched(h);
-}
+int cge_bus_seed(cge_bus *h, const uint64_t *seeds, uint64_t base_seed, void *stream) { return lane_seed(h, seeds, base_seed, stream); }
 
-int cge_bus_reset(cge_bus *h, const uint8_t *mask, int32_t *obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    bus::Params p = h->params();
-    p.mask = mask; p.obs = obs_out;
-    hipLaunchKernelGGL(bus::reset_kernel, dim3(h->blocks()), dim3(bus::BLOCK), 0, as_stream(stream), p, 0, 0);
-    return launched(h);
-}
+int cge_bus_reset(cge_bus *h, const uint8_t *mask, int32_t *obs_out, void *stream) { return lane_reset(h, mask, obs_out, stream); }
 
 int cge_bus_step(cge_bus *h, const int32_t *actions, int32_t *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
                  int32_t *final_obs_out, void *stream) {
-    bus::Params p;
-    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
-                             "cge_bus_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out, truncated_out,
-                             final_obs_out)) return st;
-    DeviceGuard g(h->device);
-    p.actions = actions;
-    launch_bus(h, p, 0, as_stream(stream));
-    h->last_kernel = "cge::bus::step_kernel<" + std::to_string(h->cfg.autoreset_mode) + ">";
-    return launched(h);
+    return lane_step(h, actions && obs_out && reward_out && terminated_out && truncated_out,
+                     "cge_bus_step: null actions/obs/reward/terminated/truncated pointer", actions, obs_out, reward_out, terminated_out, truncated_out,
+                     final_obs_out, stream);
 }
 
 int cge_bus_rollout(cge_bus *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
                     int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
                     int32_t *done_count_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    bus::Params p;
-    const int st = rollout_params_nofin(h, p, obs_step_stride % 4 == 0, h->n * bus::OBS, "cge_bus_rollout: bad k_steps / obs_step_stride", k_steps,
-                                        action_seed, t0, obs_out, obs_step_stride, reward_traj_out, reward_sum_out, done_count_out);
-    if (st != CGE_OK || k_steps == 0) return st;
-    DeviceGuard g(h->device);
-    p.actions = actions; p.truncated = truncated_traj_out;
-    launch_bus(h, p, actions ? 1 : 2, as_stream(stream));
-    h->last_kernel = "cge::bus::rollout_kernel<" + std::to_string(h->cfg.autoreset_mode) + (actions ? ", true>" : ", false>");
-    return launched(h);
+    // observations are stored as 16-byte pieces: a trajectory step starts at a multiple of four ints
+    return lane_rollout(h, obs_step_stride % 4 == 0, "cge_bus_rollout: bad k_steps / obs_step_stride", k_steps, actions, action_seed, t0, obs_out,
+                        obs_step_stride, reward_traj_out, truncated_traj_out, reward_sum_out, done_count_out, stream);
 }
 
 int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void *stream) {

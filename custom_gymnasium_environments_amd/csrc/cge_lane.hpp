@@ -1,0 +1,183 @@
+// cge_lane.hpp — what the lane-per-env types (bus, world builder, restaurant) share that is not dynamics.
+//
+// Such a type steps one env per lane with the record in registers for the whole launch, and has step_kernel<MODE...>,
+// rollout_kernel<MODE..., ACTIONS> and reset_kernel(p, init, rewind), an error counter and a key-major observation slab.  Here are
+// the fields its Params shares, the parts of its step loop that read the same in every type, and the host side of its
+// seed / reset / step / rollout entry points.  The step loops themselves stay with their types: they differ in where the wave
+// acts together (bus resets by drawing under a ballot, world builder's env_step is called by every lane with a `go` flag,
+// restaurant prefetches actions and keeps a run of generator words in registers), and a shared loop would branch on its caller.
+//
+// A new lane-per-env type supplies
+//   device  struct Params : LaneParams<Obs> with its own fields and `static constexpr bool terminates` (the flag it raises:
+//           terminated, or truncated), its run() loop calling the lane_* helpers below, and the three __global__ kernels;
+//   host    a handle derived from LaneHandle with Params, abi, kernel_ns, block, seed_kind, params(), step_elems(), reset_kernel(),
+//           kernel<MODE>(kind), and whichever of layout_arg() / actions_refusal() differ from the defaults;
+//   C ABI   entry points that are one lane_seed / lane_reset / lane_step / lane_rollout call each, with the type's own pointer and
+//           stride predicates and error texts as arguments.
+// Parking's seed / reset have the same shape and use lane_seed / lane_reset (and lane_blocks for its grid); the rest of parking is its own.
+#pragma once
+#include <string>
+#include <type_traits>
+
+#include "cge_device.hpp"
+#include "cge_host.hpp"
+
+namespace cge {
+
+// The kernel arguments every lane-per-env type has (passed by value: a type's Params must stay trivially copyable).
+template <class Obs>
+struct LaneParams {
+    uint4 *state;                  // the record's SoA columns; first, with mt / n / env0 behind it, as every type's kernels load them
+    uint32_t *mt;
+    int64_t n, env0;
+    const int32_t *actions;
+    const uint8_t *mask;
+    Obs *obs, *final_obs;
+    float *reward;
+    uint8_t *terminated, *truncated;
+    int32_t k_steps;
+    uint64_t a_seed;
+    int64_t t0, obs_step_stride;   // stride in elements of the observation layout
+    double *reward_sum;
+    int32_t *done_count;
+    double *ep_ret;                // episode statistics (cge_<env>_episode_stats), nullable
+    int32_t *ep_len;
+    unsigned long long *err_count;
+};
+
+// ---------------------------------------------------------------------------------------------------------------- device
+// Env i's episode has just ended with return `ret` after `len` steps: the registered statistics, then what the autoreset mode asks.
+template <int MODE, class P, class F>
+__device__ __forceinline__ void lane_episode_end(const P &p, int64_t i, double ret, int32_t len, bool &reset_now, F &needs_reset) {
+    if (p.ep_ret) p.ep_ret[i] = ret;
+    if (p.ep_len) p.ep_len[i] = len;
+    if (MODE == CGE_AUTORESET_SAME_STEP) reset_now = true;
+    else if (MODE == CGE_AUTORESET_NEXT_STEP) needs_reset = 1;
+}
+
+// Is an observation due at step t?  Always for step(); a rollout without a trajectory (stride 0) writes its last step only.
+template <bool ROLLOUT, class P>
+__device__ __forceinline__ bool lane_obs_due(const P &p, int t, int ksteps) {
+    return p.obs && (!ROLLOUT || p.obs_step_stride != 0 || t == ksteps - 1);
+}
+
+// step()'s outputs of env i; `done` is the flag the type raises (P::terminates), the one the reference never sets is written 0 (for a
+// type that only terminates `truncated` is nullable).  A rollout's per-step outputs — the sums and the nullable trajectories — are
+// four lines in each run() loop and stay there: written as a function, in any of the forms tried (accumulators by reference or at the
+// call site, the [t, env] index computed inside or passed in), they cost bus's fused rollout 3-4 % at 131,072 envs with the same
+// registers (profiles/lane_refactor_ab.txt).
+template <class P>
+__device__ __forceinline__ void lane_step_outputs(const P &p, int64_t i, float reward, bool done) {
+    p.reward[i] = reward;
+    if (P::terminates) {
+        p.terminated[i] = done ? 1 : 0;
+        if (p.truncated) p.truncated[i] = 0;
+    } else {
+        p.terminated[i] = 0;
+        p.truncated[i] = done ? 1 : 0;
+    }
+}
+
+// a rollout's per-env sums, after the last step
+template <class P>
+__device__ __forceinline__ void lane_sums(const P &p, int64_t i, double rsum, int32_t dcount) {
+    if (p.reward_sum) p.reward_sum[i] = rsum;
+    if (p.done_count) p.done_count[i] = dcount;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host
+enum LaneKind { LANE_STEP, LANE_ROLLOUT_GIVEN, LANE_ROLLOUT_HASHED };   // the kernel of a launch: step(), rollout() with / without actions
+
+// f(std::integral_constant<int, mode>): the one place an autoreset mode becomes the MODE template argument
+template <class F>
+void for_mode(int mode, F &&f) {
+    if (mode == CGE_AUTORESET_NEXT_STEP) f(std::integral_constant<int, CGE_AUTORESET_NEXT_STEP>{});
+    else if (mode == CGE_AUTORESET_SAME_STEP) f(std::integral_constant<int, CGE_AUTORESET_SAME_STEP>{});
+    else f(std::integral_constant<int, CGE_AUTORESET_DISABLED>{});
+}
+
+struct LaneHandle : HandleBase {
+    uint4 *state = nullptr;
+    uint32_t *mt = nullptr;
+    unsigned long long *err = nullptr;
+    // the shared fields a handle knows; the per-call ones are filled in by the drivers below
+    template <class P>
+    void fill(P &p) const { p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.err_count = err; p.ep_ret = ep_ret; p.ep_len = ep_len; }
+    const char *layout_arg() const { return ""; }                                   // template arguments between MODE and ACTIONS, as text
+    static const char *actions_refusal(const int32_t *) { return nullptr; }         // why the type cannot read these actions, or nullptr
+};
+
+template <class H>
+unsigned lane_blocks(const H *h) { return (unsigned)((h->n + H::block - 1) / H::block); }
+
+template <class H, class P>
+void lane_launch_reset(const H *h, const P &p, int init, int rewind, hipStream_t s) {
+    hipLaunchKernelGGL(h->reset_kernel(), dim3(lane_blocks(h)), dim3(H::block), 0, s, p, init, rewind);
+}
+
+template <class H>
+void lane_launch(H *h, LaneKind kind, const typename H::Params &p, const char *which, const char *tail, hipStream_t s) {
+    for_mode(h->cfg.autoreset_mode, [&](auto mode) {
+        hipLaunchKernelGGL(h->template kernel<decltype(mode)::value>(kind), dim3(lane_blocks(h)), dim3(H::block), 0, s, p);
+    });
+    h->last_kernel = std::string(H::kernel_ns) + which + "<" + std::to_string(h->cfg.autoreset_mode) + h->layout_arg() + tail + ">";
+}
+
+template <class H>
+int lane_refuse_actions(H *h, const char *fn, const char *why) {
+    return h->fail(CGE_ERR_INVALID_ARG, (std::string(H::abi) + "_" + fn + ": " + why).c_str());
+}
+
+// cge_<env>_seed: re-seed the streams (H::seed_kind: 0 CPython, 1 NumPy legacy), then rewind the cursors
+template <class H>
+int lane_seed(H *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, H::seed_kind, as_stream(stream)));
+    lane_launch_reset(h, h->params(), 0, 1, as_stream(stream));
+    return launched(h);
+}
+
+// cge_<env>_reset
+template <class H, class O>
+int lane_reset(H *h, const uint8_t *mask, O *obs, void *stream) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    DeviceGuard g(h->device);
+    auto p = h->params();
+    p.mask = mask; p.obs = obs;
+    lane_launch_reset(h, p, 0, 0, as_stream(stream));
+    return launched(h);
+}
+
+// cge_<env>_step.  `have` / `what`: as step_params (cge_host.hpp).
+template <class H, class O>
+int lane_step(H *h, bool have, const char *what, const int32_t *actions, O *obs, float *reward, uint8_t *terminated, uint8_t *truncated,
+              O *final_obs, void *stream) {
+    typename H::Params p;
+    if (int st = step_params(h, p, have, what, obs, reward, terminated, truncated, final_obs)) return st;
+    if (const char *why = H::actions_refusal(actions)) return lane_refuse_actions(h, "step", why);
+    DeviceGuard g(h->device);
+    p.actions = actions;
+    lane_launch(h, LANE_STEP, p, "step_kernel", "", as_stream(stream));
+    return launched(h);
+}
+
+// cge_<env>_rollout.  `env_ok` / `what`: as rollout_params_nofin (cge_host.hpp); `flags`: the per-step trajectory of the flag the
+// type raises.  k_steps == 0 launches nothing.
+template <class H, class O>
+int lane_rollout(H *h, bool env_ok, const char *what, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, O *obs,
+                 int64_t obs_step_stride, float *reward, uint8_t *flags, double *reward_sum, int32_t *done_count, void *stream) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    typename H::Params p;
+    const int st = rollout_params_nofin(h, p, env_ok, h->step_elems(), what, k_steps, action_seed, t0, obs, obs_step_stride, reward, reward_sum,
+                                        done_count);
+    if (st != CGE_OK || k_steps == 0) return st;
+    if (const char *why = H::actions_refusal(actions)) return lane_refuse_actions(h, "rollout", why);
+    DeviceGuard g(h->device);
+    p.actions = actions;
+    (H::Params::terminates ? p.terminated : p.truncated) = flags;
+    lane_launch(h, actions ? LANE_ROLLOUT_GIVEN : LANE_ROLLOUT_HASHED, p, "rollout_kernel", actions ? ", true" : ", false", as_stream(stream));
+    return launched(h);
+}
+
+}  // namespace cge

@@ -22,8 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cge_device.hpp"
-#include "cge_host.hpp"
+#include "cge_lane.hpp"
 
 namespace cge {
 namespace parking {
@@ -456,7 +455,9 @@ struct cge_parking : HandleBase {
         p.ep_ret = ep_ret; p.ep_len = ep_len;
         return p;
     }
-    unsigned blocks() const { return (unsigned)((n + parking::BLOCK - 1) / parking::BLOCK); }
+    // what lane_seed / lane_reset (cge_lane.hpp) ask of a handle
+    static constexpr int block = parking::BLOCK, seed_kind = 0;
+    auto reset_kernel() const { return parking::reset_kernel; }
     static int check(const cge_parking_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 0 || c.max_steps > 60000 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
@@ -465,7 +466,7 @@ struct cge_parking : HandleBase {
         CGE_HIP(alloc(state, (size_t)parking::COLS * n * sizeof(uint4), true, true));
         CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
         CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
-        hipLaunchKernelGGL(parking::reset_kernel, dim3(blocks()), dim3(parking::BLOCK), 0, nullptr, params(), 1, 0);
+        lane_launch_reset(this, params(), 1, 0, nullptr);
         return hipGetLastError();
     }
 };
@@ -474,22 +475,9 @@ extern "C" {
 
 CGE_DEFINE_LIFECYCLE(parking)
 
-int cge_parking_seed(cge_parking *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), h->params(), 0, 1);   // rewind cursors
-    return launched(h);
-}
+int cge_parking_seed(cge_parking *h, const uint64_t *seeds, uint64_t base_seed, void *stream) { return lane_seed(h, seeds, base_seed, stream); }
 
-int cge_parking_reset(cge_parking *h, const uint8_t *mask, float *obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    parking::Params p = h->params();
-    p.mask = mask; p.obs = obs_out;
-    hipLaunchKernelGGL(parking::reset_kernel, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p, 0, 0);
-    return launched(h);
-}
+int cge_parking_reset(cge_parking *h, const uint8_t *mask, float *obs_out, void *stream) { return lane_reset(h, mask, obs_out, stream); }
 
 int cge_parking_step(cge_parking *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
                      uint8_t *truncated_out, float *final_obs_out, void *stream) {
@@ -498,7 +486,7 @@ int cge_parking_step(cge_parking *h, const int32_t *actions, float *obs_out, flo
                              obs_out, reward_out, terminated_out, truncated_out, final_obs_out)) return st;
     DeviceGuard g(h->device);
     p.actions = actions;
-    hipLaunchKernelGGL(parking::step_kernel<false>, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(parking::step_kernel<false>, dim3(lane_blocks(h)), dim3(parking::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::parking::step_kernel<false>";
     return launched(h);
 }
@@ -513,7 +501,7 @@ int cge_parking_rollout(cge_parking *h, int32_t k_steps, const int32_t *actions,
     if (st != CGE_OK || k_steps == 0) return st;
     DeviceGuard g(h->device);
     p.actions = actions;
-    hipLaunchKernelGGL(parking::step_kernel<true>, dim3(h->blocks()), dim3(parking::BLOCK), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(parking::step_kernel<true>, dim3(lane_blocks(h)), dim3(parking::BLOCK), 0, as_stream(stream), p);
     h->last_kernel = "cge::parking::step_kernel<true>";
     return launched(h);
 }

@@ -19,8 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "cge_device.hpp"
-#include "cge_host.hpp"
+#include "cge_lane.hpp"
 #include "restaurant_env.hpp"
 
 namespace cge {
@@ -34,25 +33,11 @@ constexpr int P_WAITING = 0, P_WAITERS = 100, P_OCC = 130, P_DIRTY = 140, P_COOK
 constexpr int N_WAITING = 100, N_WAITERS = 30, N_TABLES = 10, N_COOKING = 150, N_READY = 40;
 static_assert(P_TIMESTEP + 1 == OBS, "planes");
 
-struct Params {
-    uint4 *state;
-    uint32_t *mt;
-    int64_t n, env0;
+struct Params : LaneParams<int32_t> {
     int32_t max_t;
-    const int32_t *actions;
-    const uint8_t *mask;
-    int32_t *obs, *final_obs;
-    float *reward;
-    uint8_t *terminated, *truncated;
-    int32_t k_steps;
-    uint64_t a_seed;
-    int64_t t0, obs_step_stride;
-    double *reward_sum;
-    int32_t *done_count;
-    double *ep_ret;       // episode statistics (cge_restaurant_episode_stats), nullable
-    int32_t *ep_len;
-    unsigned long long *err_count;
+    static constexpr bool terminates = false;                        // truncated after max_t steps; terminated is never set (:100)
 };
+static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
 
 __device__ __forceinline__ void load_env(Env &e, const uint4 *__restrict__ s, int64_t n, int64_t i) {
     uint32_t w[REC_WORDS];
@@ -167,19 +152,14 @@ __device__ __forceinline__ void run(const Params &p) {
                 if (invalid) atomicAdd(p.err_count, 1ull);           // the action had no effect (a negative component: none at all)
                 e.ret += (double)reward;
                 trunc = e.t >= (uint32_t)p.max_t;                    // :171
-                if (trunc) {
-                    if (p.ep_ret) p.ep_ret[i] = e.ret;
-                    if (p.ep_len) p.ep_len[i] = (int32_t)e.t;
-                    if (MODE == CGE_AUTORESET_SAME_STEP) reset_now = true;
-                    else if (MODE == CGE_AUTORESET_NEXT_STEP) e.needs_reset = 1;
-                }
+                if (trunc) lane_episode_end<MODE>(p, i, e.ret, (int32_t)e.t, reset_now, e.needs_reset);
             }
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal slab: every env of a wave with a truncated one
             if (p.final_obs && __ballot(trunc)) observe(e, stg, p.final_obs, p.n, i, live);
         }
         if (MODE != CGE_AUTORESET_DISABLED && reset_now) e.clear();
-        if (p.obs && (!ROLLOUT || p.obs_step_stride != 0 || t == ksteps - 1)) observe(e, stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, i, live);
+        if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, i, live);
         if (live) {
             if (ROLLOUT) {
                 rsum += (double)reward;
@@ -187,19 +167,14 @@ __device__ __forceinline__ void run(const Params &p) {
                 if (p.reward) p.reward[(int64_t)t * p.n + i] = reward;
                 if (p.truncated) p.truncated[(int64_t)t * p.n + i] = trunc ? 1 : 0;
             } else {
-                p.reward[i] = reward;
-                p.terminated[i] = 0;                                 // :100, never set
-                p.truncated[i] = trunc ? 1 : 0;
+                lane_step_outputs(p, i, reward, trunc);
             }
         }
     }
     if (live) {
         e.mt_pos = pos; e.mt_enc = pretw > pos ? mt_ready_encode(pretw) : 0u;
         store_env(e, p.state, p.n, i);
-        if (ROLLOUT) {
-            if (p.reward_sum) p.reward_sum[i] = rsum;
-            if (p.done_count) p.done_count[i] = dcount;
-        }
+        if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
 }
 
@@ -255,19 +230,29 @@ __global__ __launch_bounds__(256) void info_kernel(const uint4 *__restrict__ sta
 
 using namespace cge;
 
-struct cge_restaurant : HandleBase {
+struct cge_restaurant : LaneHandle {
+    using Params = restaurant::Params;
     cge_restaurant_config cfg{};
-    uint4 *state = nullptr;
-    uint32_t *mt = nullptr;
-    unsigned long long *err = nullptr;
     static constexpr uint32_t snap_tag = 7u;
-    restaurant::Params params() const {
-        restaurant::Params p{};
-        p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.max_t = cfg.max_episode_steps; p.err_count = err;
-        p.ep_ret = ep_ret; p.ep_len = ep_len;
+    static constexpr const char *abi = "cge_restaurant", *kernel_ns = "cge::restaurant::";
+    static constexpr int block = restaurant::BLOCK, seed_kind = 0;
+    Params params() const {
+        Params p{};
+        fill(p);
+        p.max_t = cfg.max_episode_steps;
         return p;
     }
-    unsigned blocks() const { return (unsigned)((n + restaurant::BLOCK - 1) / restaurant::BLOCK); }
+    int64_t step_elems() const { return n * restaurant::OBS; }
+    auto reset_kernel() const { return restaurant::reset_kernel; }
+    template <int MODE>
+    auto kernel(LaneKind kind) const {
+        return kind == LANE_STEP ? restaurant::step_kernel<MODE>
+               : kind == LANE_ROLLOUT_GIVEN ? restaurant::rollout_kernel<MODE, true> : restaurant::rollout_kernel<MODE, false>;
+    }
+    // an env's four action components are fetched as one 16-byte load
+    static const char *actions_refusal(const int32_t *actions) {
+        return (reinterpret_cast<uintptr_t>(actions) & 15u) != 0 ? "actions must be 16-byte aligned" : nullptr;
+    }
     static int check(const cge_restaurant_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_episode_steps < 1 || c.max_episode_steps > 1000 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
@@ -276,76 +261,31 @@ struct cge_restaurant : HandleBase {
         CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
         CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
         CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
-        hipLaunchKernelGGL(restaurant::reset_kernel, dim3(blocks()), dim3(restaurant::BLOCK), 0, nullptr, params(), 1, 0);
+        lane_launch_reset(this, params(), 1, 0, nullptr);
         return hipGetLastError();
     }
 };
-
-template <int MODE>
-static void launch_restaurant(cge_restaurant *h, const restaurant::Params &p, int kind, hipStream_t s) {
-    const dim3 grid(h->blocks()), block(restaurant::BLOCK);
-    if (kind == 0) hipLaunchKernelGGL(restaurant::step_kernel<MODE>, grid, block, 0, s, p);
-    else if (kind == 1) hipLaunchKernelGGL((restaurant::rollout_kernel<MODE, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((restaurant::rollout_kernel<MODE, false>), grid, block, 0, s, p);
-}
-static void launch_restaurant(cge_restaurant *h, const restaurant::Params &p, int kind, hipStream_t s) {
-    if (h->cfg.autoreset_mode == CGE_AUTORESET_NEXT_STEP) launch_restaurant<CGE_AUTORESET_NEXT_STEP>(h, p, kind, s);
-    else if (h->cfg.autoreset_mode == CGE_AUTORESET_SAME_STEP) launch_restaurant<CGE_AUTORESET_SAME_STEP>(h, p, kind, s);
-    else launch_restaurant<CGE_AUTORESET_DISABLED>(h, p, kind, s);
-}
-
-// an env's four action components are fetched as one 16-byte load
-static bool misaligned(const int32_t *actions) { return (reinterpret_cast<uintptr_t>(actions) & 15u) != 0; }
 
 extern "C" {
 
 CGE_DEFINE_LIFECYCLE(restaurant)
 
-int cge_restaurant_seed(cge_restaurant *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
-    hipLaunchKernelGGL(restaurant::reset_kernel, dim3(h->blocks()), dim3(restaurant::BLOCK), 0, as_stream(stream), h->params(), 0, 1);   // rewind cursors
-    return launched(h);
-}
+int cge_restaurant_seed(cge_restaurant *h, const uint64_t *seeds, uint64_t base_seed, void *stream) { return lane_seed(h, seeds, base_seed, stream); }
 
-int cge_restaurant_reset(cge_restaurant *h, const uint8_t *mask, int32_t *obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    restaurant::Params p = h->params();
-    p.mask = mask; p.obs = obs_out;
-    hipLaunchKernelGGL(restaurant::reset_kernel, dim3(h->blocks()), dim3(restaurant::BLOCK), 0, as_stream(stream), p, 0, 0);
-    return launched(h);
-}
+int cge_restaurant_reset(cge_restaurant *h, const uint8_t *mask, int32_t *obs_out, void *stream) { return lane_reset(h, mask, obs_out, stream); }
 
 int cge_restaurant_step(cge_restaurant *h, const int32_t *actions, int32_t *obs_out, float *reward_out, uint8_t *terminated_out,
                         uint8_t *truncated_out, int32_t *final_obs_out, void *stream) {
-    restaurant::Params p;
-    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && truncated_out,
-                             "cge_restaurant_step: null actions/obs/reward/terminated/truncated pointer", obs_out, reward_out, terminated_out,
-                             truncated_out, final_obs_out)) return st;
-    if (misaligned(actions)) return h->fail(CGE_ERR_INVALID_ARG, "cge_restaurant_step: actions must be 16-byte aligned");
-    DeviceGuard g(h->device);
-    p.actions = actions;
-    launch_restaurant(h, p, 0, as_stream(stream));
-    h->last_kernel = "cge::restaurant::step_kernel<" + std::to_string(h->cfg.autoreset_mode) + ">";
-    return launched(h);
+    return lane_step(h, actions && obs_out && reward_out && terminated_out && truncated_out,
+                     "cge_restaurant_step: null actions/obs/reward/terminated/truncated pointer", actions, obs_out, reward_out, terminated_out,
+                     truncated_out, final_obs_out, stream);
 }
 
 int cge_restaurant_rollout(cge_restaurant *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
                            int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
                            int32_t *done_count_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    restaurant::Params p;
-    const int st = rollout_params_nofin(h, p, true, h->n * restaurant::OBS, "cge_restaurant_rollout: bad k_steps / obs_step_stride", k_steps,
-                                        action_seed, t0, obs_out, obs_step_stride, reward_traj_out, reward_sum_out, done_count_out);
-    if (st != CGE_OK || k_steps == 0) return st;
-    if (misaligned(actions)) return h->fail(CGE_ERR_INVALID_ARG, "cge_restaurant_rollout: actions must be 16-byte aligned");
-    DeviceGuard g(h->device);
-    p.actions = actions; p.truncated = truncated_traj_out;
-    launch_restaurant(h, p, actions ? 1 : 2, as_stream(stream));
-    h->last_kernel = "cge::restaurant::rollout_kernel<" + std::to_string(h->cfg.autoreset_mode) + (actions ? ", true>" : ", false>");
-    return launched(h);
+    return lane_rollout(h, true, "cge_restaurant_rollout: bad k_steps / obs_step_stride", k_steps, actions, action_seed, t0, obs_out, obs_step_stride,
+                        reward_traj_out, truncated_traj_out, reward_sum_out, done_count_out, stream);
 }
 
 int cge_restaurant_info(cge_restaurant *h, int32_t field_id, double *out, void *stream) {

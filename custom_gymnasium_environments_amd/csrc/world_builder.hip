@@ -30,8 +30,7 @@
 #include <string>
 #include <vector>
 
-#include "cge_device.hpp"
-#include "cge_host.hpp"
+#include "cge_lane.hpp"
 
 namespace cge {
 namespace wb {
@@ -44,28 +43,14 @@ constexpr int MAX_RS = 25;             // dwords per env in the LDS byte tile (1
 constexpr int NEXTRA = 6;              // food, wood, stone, population, population_capacity, win_steps
 constexpr uint32_t MAX_POPULATION = 20, WIN_STEPS = 50;   // world_builder_env.py:45-46
 
-struct Params {
-    uint4 *state;
+struct Params : LaneParams<void> {     // obs_step_stride in elements of the layout: bytes (Dict) or floats (FLAT)
     int32_t *ret;
-    uint32_t *mt;
-    int64_t n, env0;
     int32_t G, GG, W, RS;              // grid size, cells, floats per flat row, dwords per env in the LDS tile
     uint32_t magic_gg, magic_w;        // ceil(2^32 / GG), ceil(2^32 / W): x / d == umulhi(x, magic) for the x < 2^16 used here
     int64_t off_res, off_cap, off_win; // byte offsets of the Dict slab's planes after the grid
-    const int32_t *actions;
-    const uint8_t *mask;
-    void *obs, *final_obs;
-    float *reward;
-    uint8_t *terminated, *truncated;
-    int32_t k_steps;
-    uint64_t a_seed;
-    int64_t t0, obs_step_stride;       // stride in elements of the layout: bytes (Dict) or floats (FLAT)
-    double *reward_sum;
-    int32_t *done_count;
-    double *ep_ret;
-    int32_t *ep_len;
-    unsigned long long *err_count;
+    static constexpr bool terminates = true;   // terminated only: the reference never truncates (world_builder_env.py:150)
 };
+static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
 
 // bit j = nibble j of w is non-zero
 __device__ __forceinline__ uint32_t nonzero_nibbles(uint32_t w) {
@@ -302,18 +287,13 @@ __device__ __forceinline__ void run(const Params &p) {
         const bool term = env_step(e, blk, a, go, p.GG, r);
         if (go) {
             e.ret += r;
-            if (term) {
-                if (p.ep_ret) p.ep_ret[i] = (double)e.ret;
-                if (p.ep_len) p.ep_len[i] = (int32_t)e.steps;
-                if (MODE == CGE_AUTORESET_SAME_STEP) reset_now = true;
-                else if (MODE == CGE_AUTORESET_NEXT_STEP) e.needs_reset = 1;
-            }
+            if (term) lane_episode_end<MODE>(p, i, (double)e.ret, (int32_t)e.steps, reset_now, e.needs_reset);
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {          // the terminal rows; a wave with none writes nothing
             if (p.final_obs && __ballot(term)) write_obs<FLAT>(e, p, p.final_obs, row0, nrows, lane, live, tile, ex);
         }
         if (MODE != CGE_AUTORESET_DISABLED && reset_now) e.clear();
-        if (p.obs && (!ROLLOUT || p.obs_step_stride != 0 || t == ksteps - 1))
+        if (lane_obs_due<ROLLOUT>(p, t, ksteps))
             write_obs<FLAT>(e, p, static_cast<char *>(p.obs) + (int64_t)t * step_bytes, row0, nrows, lane, live, tile, ex);
         if (live) {
             const float reward = (float)r;                          // small integers: exact
@@ -323,18 +303,13 @@ __device__ __forceinline__ void run(const Params &p) {
                 if (p.reward) p.reward[(int64_t)t * p.n + i] = reward;
                 if (p.terminated) p.terminated[(int64_t)t * p.n + i] = term ? 1 : 0;
             } else {
-                p.reward[i] = reward;
-                p.terminated[i] = term ? 1 : 0;
-                if (p.truncated) p.truncated[i] = 0;                // the reference never truncates (:150)
+                lane_step_outputs(p, i, reward, term);
             }
         }
     }
     if (live) {
         e.store(p.state, p.ret, p.n, i);
-        if (ROLLOUT) {
-            if (p.reward_sum) p.reward_sum[i] = rsum;
-            if (p.done_count) p.done_count[i] = dcount;
-        }
+        if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
 }
 
@@ -393,12 +368,12 @@ using namespace cge;
 
 static inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
-struct cge_world_builder : HandleBase {
+struct cge_world_builder : LaneHandle {
+    using Params = wb::Params;
     cge_world_builder_config cfg{};
-    uint4 *state = nullptr;
     int32_t *ret = nullptr;
-    uint32_t *mt = nullptr;
-    unsigned long long *err = nullptr;
+    static constexpr const char *kernel_ns = "cge::wb::";
+    static constexpr int block = wb::BLOCK, seed_kind = 1;
     int64_t cells() const { return (int64_t)cfg.grid_size * cfg.grid_size; }
     int64_t off_res() const { return align16(n * cells()); }
     int64_t off_cap() const { return off_res() + 16 * n; }
@@ -406,32 +381,38 @@ struct cge_world_builder : HandleBase {
     int64_t slab_bytes() const { return align16(off_win() + 4 * n); }
     int64_t step_elems() const { return cfg.flatten_obs ? n * (cells() + wb::NEXTRA) : slab_bytes(); }
     size_t record_bytes() const { return 64 + (size_t)((cells() + 3) / 4 * 4) + 4 * MT_N; }
-    wb::Params params() const {
-        wb::Params p{};
-        p.state = state; p.ret = ret; p.mt = mt; p.n = n; p.env0 = env0; p.err_count = err; p.ep_ret = ep_ret; p.ep_len = ep_len;
+    Params params() const {
+        Params p{};
+        fill(p);
+        p.ret = ret;
         p.G = cfg.grid_size; p.GG = (int32_t)cells(); p.W = p.GG + wb::NEXTRA; p.RS = (p.GG + 3) / 4;
         p.magic_gg = (uint32_t)(((1ull << 32) + (uint64_t)p.GG - 1) / (uint64_t)p.GG);
         p.magic_w = (uint32_t)(((1ull << 32) + (uint64_t)p.W - 1) / (uint64_t)p.W);
         p.off_res = off_res(); p.off_cap = off_cap(); p.off_win = off_win();
         return p;
     }
-    unsigned blocks() const { return (unsigned)((n + wb::BLOCK - 1) / wb::BLOCK); }
     // Dict slabs are written in 16-byte pieces, FLAT rows in dwords
     bool aligned(const void *ptr) const { return (reinterpret_cast<uintptr_t>(ptr) & (cfg.flatten_obs ? 3u : 15u)) == 0; }
     static int check(const cge_world_builder_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.grid_size < 2 || c.grid_size > 10 || c.flatten_obs < 0 || c.flatten_obs > 1 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
-    void launch_reset(const wb::Params &p, int init, int rewind, hipStream_t s) const {
-        if (cfg.flatten_obs) hipLaunchKernelGGL(wb::reset_kernel<true>, dim3(blocks()), dim3(wb::BLOCK), 0, s, p, init, rewind);
-        else hipLaunchKernelGGL(wb::reset_kernel<false>, dim3(blocks()), dim3(wb::BLOCK), 0, s, p, init, rewind);
+    // the FLAT axis sits on top of the mode: kernels and their names
+    auto reset_kernel() const { return cfg.flatten_obs ? wb::reset_kernel<true> : wb::reset_kernel<false>; }
+    template <int MODE, bool FLAT>
+    static auto kernel_of(LaneKind kind) {
+        return kind == LANE_STEP ? wb::step_kernel<MODE, FLAT>
+               : kind == LANE_ROLLOUT_GIVEN ? wb::rollout_kernel<MODE, FLAT, true> : wb::rollout_kernel<MODE, FLAT, false>;
     }
+    template <int MODE>
+    auto kernel(LaneKind kind) const { return cfg.flatten_obs ? kernel_of<MODE, true>(kind) : kernel_of<MODE, false>(kind); }
+    const char *layout_arg() const { return cfg.flatten_obs ? ", true" : ", false"; }
     hipError_t init() {
         CGE_HIP(alloc(state, (size_t)wb::COLS * n * sizeof(uint4), true, true));
         CGE_HIP(alloc(ret, (size_t)n * sizeof(int32_t), true, true));
         CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
         CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
         CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 1, nullptr));
-        launch_reset(params(), 1, 0, nullptr);
+        lane_launch_reset(this, params(), 1, 0, nullptr);
         return hipGetLastError();
     }
 
@@ -494,77 +475,31 @@ struct cge_world_builder : HandleBase {
     }
 };
 
-template <int MODE, bool FLAT>
-static void launch_wb(cge_world_builder *h, const wb::Params &p, int kind, hipStream_t s) {
-    const dim3 grid(h->blocks()), block(wb::BLOCK);
-    if (kind == 0) hipLaunchKernelGGL((wb::step_kernel<MODE, FLAT>), grid, block, 0, s, p);
-    else if (kind == 1) hipLaunchKernelGGL((wb::rollout_kernel<MODE, FLAT, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((wb::rollout_kernel<MODE, FLAT, false>), grid, block, 0, s, p);
-}
-template <bool FLAT>
-static void launch_wb(cge_world_builder *h, const wb::Params &p, int kind, hipStream_t s) {
-    if (h->cfg.autoreset_mode == CGE_AUTORESET_NEXT_STEP) launch_wb<CGE_AUTORESET_NEXT_STEP, FLAT>(h, p, kind, s);
-    else if (h->cfg.autoreset_mode == CGE_AUTORESET_SAME_STEP) launch_wb<CGE_AUTORESET_SAME_STEP, FLAT>(h, p, kind, s);
-    else launch_wb<CGE_AUTORESET_DISABLED, FLAT>(h, p, kind, s);
-}
-static void launch_wb(cge_world_builder *h, const wb::Params &p, int kind, hipStream_t s) {
-    if (h->cfg.flatten_obs) launch_wb<true>(h, p, kind, s);
-    else launch_wb<false>(h, p, kind, s);
-}
-static std::string kernel_name(const cge_world_builder *h, const char *which, const char *tail) {
-    return std::string("cge::wb::") + which + "<" + std::to_string(h->cfg.autoreset_mode) + (h->cfg.flatten_obs ? ", true" : ", false") + tail + ">";
-}
-
 extern "C" {
 
 CGE_DEFINE_LIFECYCLE(world_builder)
 
-int cge_world_builder_seed(cge_world_builder *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    DeviceGuard g(h->device);
-    CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 1, as_stream(stream)));
-    h->launch_reset(h->params(), 0, 1, as_stream(stream));          // rewind the cursors
-    return launched(h);
-}
+int cge_world_builder_seed(cge_world_builder *h, const uint64_t *seeds, uint64_t base_seed, void *stream) { return lane_seed(h, seeds, base_seed, stream); }
 
 int cge_world_builder_reset(cge_world_builder *h, const uint8_t *mask, void *obs_out, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
     if (obs_out && !h->aligned(obs_out)) return h->fail(CGE_ERR_INVALID_ARG, "cge_world_builder_reset: obs_out must be 16-byte (Dict) / 4-byte (flat) aligned");
-    DeviceGuard g(h->device);
-    wb::Params p = h->params();
-    p.mask = mask; p.obs = obs_out;
-    h->launch_reset(p, 0, 0, as_stream(stream));
-    return launched(h);
+    return lane_reset(h, mask, obs_out, stream);
 }
 
 int cge_world_builder_step(cge_world_builder *h, const int32_t *actions, void *obs_out, float *reward_out, uint8_t *terminated_out,
                            uint8_t *truncated_out, void *final_obs_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    wb::Params p;
-    if (int st = step_params(h, p, actions && obs_out && reward_out && terminated_out && h->aligned(obs_out) && h->aligned(final_obs_out),
-                             "cge_world_builder_step: null actions/obs/reward/terminated pointer, or a misaligned observation buffer", obs_out,
-                             reward_out, terminated_out, truncated_out, final_obs_out)) return st;
-    DeviceGuard g(h->device);
-    p.actions = actions;
-    launch_wb(h, p, 0, as_stream(stream));
-    h->last_kernel = kernel_name(h, "step_kernel", "");
-    return launched(h);
+    return lane_step(h, h && actions && obs_out && reward_out && terminated_out && h->aligned(obs_out) && h->aligned(final_obs_out),
+                     "cge_world_builder_step: null actions/obs/reward/terminated pointer, or a misaligned observation buffer", actions, obs_out,
+                     reward_out, terminated_out, truncated_out, final_obs_out, stream);
 }
 
 int cge_world_builder_rollout(cge_world_builder *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, void *obs_out,
                               int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                               int32_t *done_count_out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    wb::Params p;
-    const bool ok = h->aligned(obs_out) && (h->cfg.flatten_obs || obs_step_stride % 16 == 0);
-    const int st = rollout_params_nofin(h, p, ok, h->step_elems(), "cge_world_builder_rollout: bad k_steps / obs_step_stride / observation alignment",
-                                        k_steps, action_seed, t0, obs_out, obs_step_stride, reward_traj_out, reward_sum_out, done_count_out);
-    if (st != CGE_OK || k_steps == 0) return st;
-    DeviceGuard g(h->device);
-    p.actions = actions; p.terminated = terminated_traj_out;
-    launch_wb(h, p, actions ? 1 : 2, as_stream(stream));
-    h->last_kernel = kernel_name(h, "rollout_kernel", actions ? ", true" : ", false");
-    return launched(h);
+    const bool ok = h && h->aligned(obs_out) && (h->cfg.flatten_obs || obs_step_stride % 16 == 0);
+    return lane_rollout(h, ok, "cge_world_builder_rollout: bad k_steps / obs_step_stride / observation alignment", k_steps, actions, action_seed, t0,
+                        obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out, stream);
 }
 
 int cge_world_builder_info(cge_world_builder *h, int32_t field_id, int32_t index, int32_t *out, void *stream) {

@@ -6,7 +6,8 @@ import torch
 
 from . import _native
 from ._spaces import Box, Dict, Discrete
-from .vector_env import TRUNCATED, DeviceVectorEnv
+from ._slab import SlabVectorEnv, packed_planes
+from .vector_env import TRUNCATED
 
 INFO_FIELDS = {"timestep": 0, "waiting_customers": 1, "idle_waiters": 2, "kitchen_queue_length": 3, "ready_orders": 4, "dirty_tables": 5,
                "customers_served": 6, "customers_left": 7, "tables_cleaned": 8, "orders_served": 9, "wait_time_sum": 10, "num_customers": 11,
@@ -31,7 +32,7 @@ def make_spaces():
     return observation, Dict({k: Discrete(n) for k, n in zip(ACTION_KEYS, ACTION_NVEC)})
 
 
-class RestaurantVectorEnv(DeviceVectorEnv):
+class RestaurantVectorEnv(SlabVectorEnv):
     """N independent RestaurantEnv instances (10 tables, 10 waiters, a waiting line and a kitchen, 500 steps) stepped by one HIP
     kernel launch.  Spaces as the reference: the `Dict` action {type: Discrete(4), waiter_id: Discrete(10), customer_id: Discrete(50),
     table_id: Discrete(10)} (:41-46) and the `Dict` observation of :47-55 with its seven int32 keys.
@@ -67,9 +68,10 @@ class RestaurantVectorEnv(DeviceVectorEnv):
 
     _abi = "cge_restaurant"
     INFO_FIELDS = INFO_FIELDS
-    _obs_dtype = torch.int32
     _action_shape = (4,)
     _flags = TRUNCATED
+    # an env-step whose action had a component that was negative or not below its bound (it had no effect; the step itself ran)
+    _invalid_action_text = f"Invalid action in {{n}} env-step(s): (type, waiter_id, customer_id, table_id) must lie below {ACTION_NVEC}"
     metadata = {"render_modes": []}
 
     def __init__(self, num_envs, device="cuda:0", autoreset_mode="NextStep", env_index0=0, max_episode_steps=500, reuse_buffers=False,
@@ -77,9 +79,7 @@ class RestaurantVectorEnv(DeviceVectorEnv):
         self._init_common(num_envs, device, autoreset_mode, env_index0, reuse_buffers)
         self.max_episode_steps = int(max_episode_steps)
         self.single_observation_space, self.single_action_space = make_spaces()
-        self._slab = self.num_envs * OBS_INTS
-        self._obs_shape = (self._slab,)                                  # one flat slab per step, not [N, ...]
-        self._views = {}
+        self._init_slab(*packed_planes(PLANES, self.num_envs), torch.int32)   # int32 [341 * N] per step
         self._create(_native.RestaurantConfig(self.max_episode_steps, self._mode_code), info_fields, record_episode_statistics, reference_info)
 
     def _create_error(self, status):
@@ -105,30 +105,6 @@ class RestaurantVectorEnv(DeviceVectorEnv):
         """A DeviceSpaceSampler over the batched Dict action space; its samples are int32, the form step() stacks with no conversion."""
         return super().action_sampler(seed, {key: torch.int32 for key in ACTION_KEYS} if dtype is None else dtype)
 
-    # ------------------------------------------------------------------ the slab and its per-key views
-    def _dict(self, slab):
-        """slab int32 [341 * N] or [k, 341 * N] -> {key: view [N, ...] or [k, N, ...]}.  The dict of a persistent buffer is built once."""
-        key = (slab.data_ptr(), tuple(slab.shape)) if self._reuse else None
-        d = self._views.get(key) if key is not None else None
-        if d is None:
-            n, d, o = self.num_envs, {}, 0
-            for name, shape in PLANES:
-                w = n * int(np.prod(shape))
-                d[name] = slab[..., o:o + w].view(slab.shape[:-1] + (n,) + shape)
-                o += w
-            if key is not None:
-                self._views = {k: v for k, v in self._views.items() if k[0] != key[0]}       # a regrown buffer drops its old views
-                self._views[key] = d
-        return dict(d)
-
-    _wrap_obs = _dict
-
-    def obs_slab(self, obs):
-        """The flat int32 slab ([341 * N], or [k, 341 * N] for a trajectory) behind an observation dict of this env."""
-        first = obs["waiting_customers"]
-        lead = first.shape[:-3]
-        return torch.as_strided(first, lead + (self._slab,), tuple(first.stride()[:len(lead)]) + (1,), first.storage_offset())
-
     # ------------------------------------------------------------------ extras
     def reference_info(self):
         """The reference's `info` dict under ITS keys (_get_info, :478-494), one float64 tensor [N] per value; `episode_stats` is the
@@ -144,13 +120,3 @@ class RestaurantVectorEnv(DeviceVectorEnv):
                                   "tables_cleaned": self.info("tables_cleaned"), "orders_served": self.info("orders_served"),
                                   "total_wait_time": zero, "average_wait_time": zero.clone()},
                 "average_wait_time": self.info("wait_time_sum") / self.info("num_customers").clamp(min=1.0)}
-
-    def invalid_action_count(self):
-        """Synchronises; number of env-steps since the last call whose action had a component that was negative or not below its
-        bound (the action then had no effect; the step itself ran)."""
-        return int(self._lib.cge_restaurant_error_count(self._h, self._stream()))
-
-    def check_actions(self):
-        n = self.invalid_action_count()
-        if n:
-            raise ValueError(f"Invalid action in {n} env-step(s): (type, waiter_id, customer_id, table_id) must lie below {ACTION_NVEC}")

@@ -38,6 +38,7 @@ class SnakeVectorEnv(DeviceVectorEnv):
     _obs_dtype = torch.int8
     _reward_sum_dtype = torch.float32
     _info_dtype = torch.int32
+    _invalid_action_text = "Invalid action in {n} env-step(s)"   # an action outside 0..3 (reference: ValueError, snake_env.py:69-70)
     metadata = {"render_modes": ["rgb_array"]}
 
     def __init__(self, num_envs, grid_size=20, device="cuda:0", autoreset_mode="NextStep", env_index0=0,
@@ -78,12 +79,3 @@ class SnakeVectorEnv(DeviceVectorEnv):
         auto-reset that is the fresh episode's (the finished episode's score is what `record_episode_statistics` reports:
         return = 10 * score - 10 on a crash).  `reference_info=True` merges it into every `infos`."""
         return {"score": self.info("score"), "snake_length": self.info("snake_length")}
-
-    def invalid_action_count(self):
-        """Synchronises; number of out-of-range actions since the last call (reference: ValueError)."""
-        return int(self._lib.cge_snake_error_count(self._h, self._stream()))
-
-    def check_actions(self):
-        n = self.invalid_action_count()
-        if n:
-            raise ValueError(f"Invalid action in {n} env-step(s)")  # snake_env.py:69-70

@@ -65,6 +65,7 @@ class DeviceVectorEnv(VectorEnvBase):
     _flags = TERMINATED
     _reward_sum_dtype = torch.float64
     _info_dtype, _info_indexed = torch.float64, False
+    _invalid_action_text = None   # check_actions(): the ValueError text of a type with an error counter, with {n} = the count
 
     def _init_common(self, num_envs, device, autoreset_mode, env_index0, reuse_buffers):
         if int(num_envs) <= 0:
@@ -189,6 +190,19 @@ class DeviceVectorEnv(VectorEnvBase):
             dtype = torch.int32
         return DeviceSpaceSampler(space, self.device, seed=seed, env_index0=self.env_index0,
                                   global_num_envs=getattr(self, "global_num_envs", None), dtype=dtype)
+
+    def invalid_action_count(self):
+        """Synchronises; number of env-steps since the last call whose action the kernel reported instead of acting on (what counts
+        is the type's: see its `_invalid_action_text`).  Reading clears the counter.  Only the types that export
+        `<abi>_error_count` have one (snake, bus, world builder, restaurant); for the others this is an AttributeError."""
+        return int(self._fn("error_count")(self._h, self._stream()))
+
+    def check_actions(self):
+        """Raises the reference's ValueError if `invalid_action_count()` is not zero."""
+        n = self.invalid_action_count()
+        assert self._invalid_action_text is not None, f"{type(self).__name__} has an error counter but no _invalid_action_text"
+        if n:
+            raise ValueError(self._invalid_action_text.format(n=n))
 
     def last_kernel(self):
         """Name(s) of the kernel(s) the last step() / rollout() launched, as rocprofv3 prints them ("" before the first call)."""

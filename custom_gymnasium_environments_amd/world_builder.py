@@ -4,7 +4,8 @@ import torch
 
 from . import _native
 from ._spaces import Box, Dict, Discrete
-from .vector_env import TERMINATED, DeviceVectorEnv
+from ._slab import SlabVectorEnv
+from .vector_env import TERMINATED
 
 INFO_FIELDS = {"steps": 0, "win_steps": 1, "reached_win_population": 2, "food": 3, "wood": 4, "stone": 5, "population": 6,
                "population_capacity": 7, "building_count": 8, "needs_reset": 9}
@@ -28,6 +29,12 @@ def slab_layout(num_envs, grid_size):
     return offs, o
 
 
+def plane_table(num_envs, grid_size):
+    """(the planes as _slab takes them: key, per-env shape, torch dtype, byte offset in the uint8 slab; slab bytes)."""
+    offs, total = slab_layout(num_envs, grid_size)
+    return tuple((key, shape, _TORCH[dtype], offs[key]) for key, shape, dtype in planes(grid_size)), total
+
+
 def make_spaces(grid_size=10, flatten_obs=False):
     """(observation_space, action_space) of ONE WorldBuilderEnv (:57, :69-86)."""
     g = int(grid_size)
@@ -42,7 +49,7 @@ def make_spaces(grid_size=10, flatten_obs=False):
     return observation, Discrete(5)
 
 
-class WorldBuilderVectorEnv(DeviceVectorEnv):
+class WorldBuilderVectorEnv(SlabVectorEnv):
     """N independent WorldBuilderEnv instances (a `grid_size` x `grid_size` grid, food / wood / stone, a population that must reach 20
     and hold for 50 steps) stepped by one HIP kernel launch.  Spaces as the reference: `Discrete(5)` actions (pass, farm, lumberyard,
     quarry, house) and either the `Dict` observation of :79-86 — int8 `grid`, float32 `resources` (food, wood, stone, population) and
@@ -67,6 +74,8 @@ class WorldBuilderVectorEnv(DeviceVectorEnv):
     _action_shape = ()
     _flags = TERMINATED
     _info_dtype, _info_indexed = torch.int32, True
+    # an env-step refused for an action outside 0..4 (reference: ValueError, :133-134)
+    _invalid_action_text = "Invalid action in {n} env-step(s). Action space is Discrete(5)"
     metadata = {"render_modes": []}
 
     def __init__(self, num_envs, device="cuda:0", autoreset_mode="NextStep", env_index0=0, grid_size=10, flatten_obs=False,
@@ -74,14 +83,11 @@ class WorldBuilderVectorEnv(DeviceVectorEnv):
         self._init_common(num_envs, device, autoreset_mode, env_index0, reuse_buffers)
         self.grid_size, self.flatten_obs = int(grid_size), bool(flatten_obs)
         self.single_observation_space, self.single_action_space = make_spaces(self.grid_size, self.flatten_obs)
-        cells = self.grid_size * self.grid_size
-        self._offsets, self._slab = slab_layout(self.num_envs, self.grid_size)
-        if self.flatten_obs:
-            self._obs_dtype, self._obs_shape = torch.float32, (self.num_envs, cells + 6)
+        self._offsets = slab_layout(self.num_envs, self.grid_size)[0]          # read by tests/test_world_builder_gpu.py only
+        if self.flatten_obs:                                                    # plain float32 rows: no slab, no dict of views
+            self._obs_dtype, self._obs_shape, self._wrap_obs = torch.float32, (self.num_envs, self.grid_size * self.grid_size + 6), None
         else:
-            self._obs_dtype, self._obs_shape = torch.uint8, (self._slab,)       # one flat slab per step, not [N, ...]
-            self._wrap_obs = self._dict
-        self._views = {}
+            self._init_slab(*plane_table(self.num_envs, self.grid_size), torch.uint8)
         self._create(_native.WorldBuilderConfig(self.grid_size, int(self.flatten_obs), self._mode_code, 0), info_fields,
                      record_episode_statistics, reference_info)
 
@@ -89,28 +95,6 @@ class WorldBuilderVectorEnv(DeviceVectorEnv):
         if status == -1 and not MIN_GRID <= self.grid_size <= MAX_GRID:
             return ValueError(f"grid_size must be in {MIN_GRID}..{MAX_GRID}, got {self.grid_size}")
         return None
-
-    # ------------------------------------------------------------------ the slab and its per-key views
-    def _dict(self, slab):
-        """slab uint8 [slab_bytes] or [k, slab_bytes] -> {key: typed view [N, ...] or [k, N, ...]}.  The dict of a persistent buffer is
-        built once."""
-        key = (slab.data_ptr(), tuple(slab.shape)) if self._reuse else None
-        d = self._views.get(key) if key is not None else None
-        if d is None:
-            n, d = self.num_envs, {}
-            for name, shape, dtype in planes(self.grid_size):
-                o, w = self._offsets[name], n * int(np.prod(shape)) * np.dtype(dtype).itemsize
-                d[name] = slab[..., o:o + w].view(_TORCH[dtype]).view(slab.shape[:-1] + (n,) + shape)
-            if key is not None:
-                self._views = {k: v for k, v in self._views.items() if k[0] != key[0]}       # a regrown buffer drops its old views
-                self._views[key] = d
-        return dict(d)
-
-    def obs_slab(self, obs):
-        """The uint8 slab ([slab_bytes], or [k, slab_bytes] for a trajectory) behind a Dict observation of this env."""
-        first = obs["grid"].view(torch.uint8)
-        lead = first.shape[:-3]
-        return torch.as_strided(first, lead + (self._slab,), tuple(first.stride()[:len(lead)]) + (1,), first.storage_offset())
 
     # ------------------------------------------------------------------ extras
     def reference_info(self):
@@ -122,12 +106,3 @@ class WorldBuilderVectorEnv(DeviceVectorEnv):
                 "resources": {k: self.info(k) for k in ("food", "wood", "stone")},
                 "population": self.info("population"), "population_capacity": self.info("population_capacity"),
                 "building_counts": {k: self.info("building_count", j) for j, k in enumerate(BUILDINGS)}}
-
-    def invalid_action_count(self):
-        """Synchronises; number of env-steps refused for an action outside 0..4 since the last call (reference: ValueError)."""
-        return int(self._lib.cge_world_builder_error_count(self._h, self._stream()))
-
-    def check_actions(self):
-        n = self.invalid_action_count()
-        if n:
-            raise ValueError(f"Invalid action in {n} env-step(s). Action space is Discrete(5)")   # :133-134

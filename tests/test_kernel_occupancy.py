@@ -55,16 +55,25 @@ def _kernels(tmp):
     return out
 
 
+def waves_per_simd(vgpr, agpr):
+    total = -(-vgpr // 8) * 8 + -(-agpr // 8) * 8
+    return min(8, 512 // max(total, 8))
+
+
+def check_floors(ks, floors):
+    """Every kernel of `ks` (_kernels) whose name holds a fragment of `floors` keeps that many waves per SIMD, and every fragment is found."""
+    seen = set()
+    for name, (vgpr, agpr) in ks.items():
+        for frag, floor in floors.items():
+            if frag in name:
+                seen.add(frag)
+                waves = waves_per_simd(vgpr, agpr)
+                assert waves >= floor, f"{name}: {vgpr} + {agpr} registers = {waves} waves per SIMD, the floor is {floor}"
+    assert seen == set(floors), f"kernels not found in the library: {sorted(set(floors) - seen)}"
+
+
 @pytest.mark.skipif(not (os.path.exists(LIB) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))), reason="needs the built library and the ROCm LLVM tools")
 def test_hot_kernels_keep_their_waves_per_simd(tmp_path):
     ks = _kernels(str(tmp_path))
     assert len(ks) > 50, "no kernel notes found in the library"
-    seen = set()
-    for name, (vgpr, agpr) in ks.items():
-        for frag, floor in FLOORS.items():
-            if frag in name:
-                seen.add(frag)
-                total = -(-vgpr // 8) * 8 + -(-agpr // 8) * 8
-                waves = min(8, 512 // max(total, 8))
-                assert waves >= floor, f"{name}: {vgpr} + {agpr} registers = {waves} waves per SIMD, the floor is {floor}"
-    assert seen == set(FLOORS), f"kernels not found in the library: {sorted(set(FLOORS) - seen)}"
+    check_floors(ks, FLOORS)

@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from test_kernel_occupancy import LIB, LLVM, _kernels
+from test_kernel_occupancy import LIB, LLVM, _kernels, check_floors
 
 # mangled-name fragment -> minimum waves per SIMD; template arguments: autoreset mode (0 NextStep, 1 SameStep, 2 Disabled), caller's actions
 FLOORS = {
@@ -24,13 +24,4 @@ FLOORS = {
 
 @pytest.mark.skipif(not (os.path.exists(LIB) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))), reason="needs the built library and the ROCm LLVM tools")
 def test_restaurant_kernels_keep_their_waves_per_simd(tmp_path):
-    ks = _kernels(str(tmp_path))
-    seen = set()
-    for name, (vgpr, agpr) in ks.items():
-        for frag, floor in FLOORS.items():
-            if frag in name:
-                seen.add(frag)
-                total = -(-vgpr // 8) * 8 + -(-agpr // 8) * 8
-                waves = min(8, 512 // max(total, 8))
-                assert waves >= floor, f"{name}: {vgpr} + {agpr} registers = {waves} waves per SIMD, the floor is {floor}"
-    assert seen == set(FLOORS), f"kernels not found in the library: {sorted(set(FLOORS) - seen)}"
+    check_floors(_kernels(str(tmp_path)), FLOORS)
