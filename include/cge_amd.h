@@ -728,6 +728,78 @@ const char *cge_restaurant_last_error(const cge_restaurant *h);
 const char *cge_restaurant_last_kernel(const cge_restaurant *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Airline operations  (airline_operations_env/airline_env.py: AirlineOperationsEnv)             */
+/*   25 aircraft, 15 airports, 150 flights, 40 crew sets, up to 3 weather systems; a step is a    */
+/*   quarter of an hour from 6.0; terminated only: the clock reaches 23.75 (71 steps) or          */
+/*   passenger_satisfaction < 0.6.  action int32 0..44 (Discrete(45), :445-511).                  */
+/*   obs float32 [n_envs, 160] row-major (:354-396), 16-byte aligned.                             */
+/*   Bit-exact: observations, the integer-valued reward, flags and the float64 info values, with  */
+/*   ONE stated departure: a weather system's distance is sqrt(dx*dx + dy*dy) where the reference */
+/*   evaluates dx**2 through libm pow (a last-place difference in 0.07 % of its evaluations,      */
+/*   seen only through the float32 weather_severity: no recorded observation differs).           */
+/*   Generator: the process-global CPython `random` (randint, uniform, choice); the env never     */
+/*   seeds it.  The NETWORK (aircraft bases, the flight schedule, crews) is drawn once, by the    */
+/*   constructor, and survives every reset; aircraft positions carry across episodes too.         */
+/*   cge_airline_seed is `random.seed(s_i); AirlineOperationsEnv()` for env i: it seeds the       */
+/*   stream, draws the network and the constructor's own discarded reset (:190); the reset that   */
+/*   follows draws the visible one.  cge_airline_create does the same with base seed 0.           */
+/*   Device memory: 1,656 B of record + 2,560 B of generator per env (+ 8 B).                     */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_airline cge_airline;
+
+typedef struct {
+    int32_t autoreset_mode;      /* CGE_AUTORESET_* */
+    int32_t reserved;            /* 0 */
+} cge_airline_config;
+
+enum { CGE_AIRLINE_OBS_FLOATS = 160, CGE_AIRLINE_RECORD_BYTES = 1656 };
+
+enum { /* cge_airline_info float64 fields: the reference's five info values (:435-441), then what else the record knows */
+    CGE_AIRLINE_INFO_ON_TIME_PERFORMANCE = 0,
+    CGE_AIRLINE_INFO_PASSENGER_SATISFACTION = 1,
+    CGE_AIRLINE_INFO_DAILY_REVENUE = 2,        /* 0.0 for ever: passengers_onboard is zeroed before it is paid (:562, :569) */
+    CGE_AIRLINE_INFO_DAILY_COSTS = 3,
+    CGE_AIRLINE_INFO_CURRENT_HOUR = 4,
+    CGE_AIRLINE_INFO_TIMESTEP = 5,             /* steps since the episode's reset */
+    CGE_AIRLINE_INFO_NEEDS_RESET = 6,
+    CGE_AIRLINE_INFO_FLIGHTS_IN_AIR = 7,       /* aircraft with in_flight set */
+    CGE_AIRLINE_INFO_DELAY_COMPENSATION = 8,
+    CGE_AIRLINE_INFO_FUEL_COSTS = 9
+};
+
+/* AirlineOperationsEnv.__init__ :132-190 on the stream random.seed(env_index0 + i) */
+int cge_airline_create(const cge_airline_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_airline **out);
+int cge_airline_destroy(cge_airline *h);
+/* random.seed(s_i); AirlineOperationsEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+int cge_airline_seed(cge_airline *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :274-336 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
+int cge_airline_reset(cge_airline *h, const uint8_t *mask, float *obs_out, void *stream);
+/* step :398-443.  actions int32 [n_envs].  An action outside 0..44 skips _process_action — the rest of the step runs — and bumps a
+ * device-side counter (cge_airline_error_count); the reference would index its aircraft list from the back for -25..-1 and do
+ * nothing for anything else.  truncated_out is nullable (always 0).  final_obs_out (nullable): SAME_STEP writes the rows of every
+ * wave of 64 envs that holds an env terminated in this step; valid where terminated. */
+int cge_airline_step(cge_airline *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
+                     uint8_t *truncated_out, float *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs], or NULL: env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 45, 0).
+ * obs_out: k batches obs_step_stride floats apart (>= 160 * n_envs, a multiple of 4), or with stride 0 the last step's.
+ * terminated_traj_out [k, n_envs]; done_count counts terminated steps.  Terminal rows of a SAME_STEP rollout are not delivered. */
+int cge_airline_rollout(cge_airline *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
+                        int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
+                        int32_t *done_count_out, void *stream);
+int cge_airline_info(cge_airline *h, int32_t field_id, double *out, void *stream);
+/* env-steps whose action was outside 0..44 since the last call; synchronises */
+int64_t cge_airline_error_count(cge_airline *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_airline_snapshot_bytes(const cge_airline *h);
+int cge_airline_snapshot_get(cge_airline *h, void *host_buf, void *stream);
+int cge_airline_snapshot_set(cge_airline *h, const void *host_buf, void *stream);
+size_t cge_airline_device_bytes(const cge_airline *h);
+int cge_airline_episode_stats(cge_airline *h, double *return_out, int32_t *length_out);
+const char *cge_airline_last_error(const cge_airline *h);
+const char *cge_airline_last_kernel(const cge_airline *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
 /*   game_logic.py: GameLogic)                                                                    */
 /*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */
