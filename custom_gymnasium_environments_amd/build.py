@@ -34,6 +34,7 @@ def is_stale():
 # work-list indices of the hospital and fleet kernels (cge_device.hpp: CGE_GX); the first violation is recorded instead of dereferenced (`python -m custom_gymnasium_environments_amd.build --guard` writes libcge_amd_guard.so next to
 # the release library; tools/probes/guard_run.py replays the reference fixtures through it).  -DCGE_<ENV>_TIMING: on-device phase clocks.
 # -DCGE_AIRLINE_LDS_ROWS: the airline observation through an LDS tile, the store pass measured and dropped (profiles/airline_timing.txt).
+# -DCGE_EMERGENCY_LDS_ROWS: the same for the emergency observation (profiles/emergency_timing.txt).
 GUARD_FLAGS = ("-DCGE_MFG_GUARD", "-DCGE_GUARD")
 
 

@@ -800,6 +800,80 @@ const char *cge_airline_last_error(const cge_airline *h);
 const char *cge_airline_last_kernel(const cge_airline *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Emergency response  (emergency_response_env/emergency_env.py: EmergencyResponseEnv)           */
+/*   A 30 x 30 city, up to 20 incidents, 40 response units of which actions 0..19 dispatch the    */
+/*   twelve fire trucks and eight police cars, 8 hospitals, weather, 25 traffic segments; a step  */
+/*   is a minute.  terminated only (:808-827): no incident after minute 60 (success), more than   */
+/*   50 casualties, a mean response time above 45, or max_timesteps reached.                      */
+/*   action int32 0..49 (Discrete(50), :648-690).                                                 */
+/*   obs float32 [n_envs, 276] row-major (:524-587), 16-byte aligned.                             */
+/*   Bit-exact: observations, the integer-valued reward, flags and the float64 info values.       */
+/*   Generator: the process-global CPython `random` (random, uniform, randint); the env never     */
+/*   seeds it.  The constructor draws population densities, the stations of units 30..39 and the  */
+/*   hospitals' capacities (952 randint) and does NOT reset.  cge_emergency_seed is               */
+/*   `random.seed(s_i); EmergencyResponseEnv()` for env i and leaves it without an incident; the   */
+/*   reset that follows draws the first episode.  cge_emergency_create does the same with base    */
+/*   seed 0.  Every later reset continues the stream and keeps the network and the reward's       */
+/*   _prev_ counters, as the reference does.                                                      */
+/*   Device memory: 808 B of record + 2,560 B of generator per env (+ 8 B).                       */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_emergency cge_emergency;
+
+typedef struct {
+    int32_t autoreset_mode;      /* CGE_AUTORESET_* */
+    int32_t max_timesteps;       /* 1..65535; the reference's attribute of the same name, 1440 */
+} cge_emergency_config;
+
+enum { CGE_EMERGENCY_OBS_FLOATS = 276, CGE_EMERGENCY_RECORD_BYTES = 808, CGE_EMERGENCY_ACTIONS = 50 };
+
+enum { /* cge_emergency_info float64 fields: the reference's six info values (:913-920), then what else the record knows */
+    CGE_EMERGENCY_INFO_ACTIVE_EMERGENCIES = 0,
+    CGE_EMERGENCY_INFO_TOTAL_CASUALTIES = 1,
+    CGE_EMERGENCY_INFO_LIVES_SAVED = 2,
+    CGE_EMERGENCY_INFO_EMERGENCIES_RESOLVED = 3,
+    CGE_EMERGENCY_INFO_AVG_RESPONSE_TIME = 4,
+    CGE_EMERGENCY_INFO_TERMINATION_REASON = 5,   /* of the last step: 0 none, 1 success, 2 casualties, 3 overwhelmed, 4 timeout */
+    CGE_EMERGENCY_INFO_TIMESTEP = 6,             /* steps since the episode's reset */
+    CGE_EMERGENCY_INFO_NEEDS_RESET = 7,
+    CGE_EMERGENCY_INFO_BUSY_UNITS = 8,
+    CGE_EMERGENCY_INFO_MUTUAL_AID_REQUESTED = 9,
+    CGE_EMERGENCY_INFO_NATIONAL_GUARD_ACTIVE = 10,
+    CGE_EMERGENCY_INFO_STATE_OF_EMERGENCY = 11
+};
+
+/* EmergencyResponseEnv.__init__ :116-157 on the stream random.seed(env_index0 + i) */
+int cge_emergency_create(const cge_emergency_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_emergency **out);
+int cge_emergency_destroy(cge_emergency *h);
+/* random.seed(s_i); EmergencyResponseEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+int cge_emergency_seed(cge_emergency *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :829-881 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
+int cge_emergency_reset(cge_emergency *h, const uint8_t *mask, float *obs_out, void *stream);
+/* step :883-922.  actions int32 [n_envs].  An action outside 0..49 falls through every branch of _execute_action, as it does in
+ * the reference — the rest of the step runs — and bumps a device-side counter (cge_emergency_error_count).  truncated_out is
+ * nullable (always 0).  final_obs_out (nullable): SAME_STEP writes the rows of every wave of 64 envs that holds an env terminated
+ * in this step; valid where terminated. */
+int cge_emergency_step(cge_emergency *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
+                       uint8_t *truncated_out, float *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs], or NULL: env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 50, 0).
+ * obs_out: k batches obs_step_stride floats apart (>= 276 * n_envs, a multiple of 4), or with stride 0 the last step's.
+ * terminated_traj_out [k, n_envs]; done_count counts terminated steps.  Terminal rows of a SAME_STEP rollout are not delivered. */
+int cge_emergency_rollout(cge_emergency *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
+                          int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
+                          int32_t *done_count_out, void *stream);
+int cge_emergency_info(cge_emergency *h, int32_t field_id, double *out, void *stream);
+/* env-steps whose action was outside 0..49 since the last call; synchronises */
+int64_t cge_emergency_error_count(cge_emergency *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_emergency_snapshot_bytes(const cge_emergency *h);
+int cge_emergency_snapshot_get(cge_emergency *h, void *host_buf, void *stream);
+int cge_emergency_snapshot_set(cge_emergency *h, const void *host_buf, void *stream);
+size_t cge_emergency_device_bytes(const cge_emergency *h);
+int cge_emergency_episode_stats(cge_emergency *h, double *return_out, int32_t *length_out);
+const char *cge_emergency_last_error(const cge_emergency *h);
+const char *cge_emergency_last_kernel(const cge_emergency *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
 /*   game_logic.py: GameLogic)                                                                    */
 /*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */
