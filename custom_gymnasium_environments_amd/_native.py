@@ -78,6 +78,10 @@ class EmergencyConfig(C.Structure):
     _fields_ = [("autoreset_mode", C.c_int32), ("max_timesteps", C.c_int32)]
 
 
+class SpaceStationConfig(C.Structure):
+    _fields_ = [("autoreset_mode", C.c_int32), ("max_steps", C.c_int32)]
+
+
 class Pcg64State(C.Structure):
     """cge_pcg64_state: NumPy's PCG64 bit_generator.state as 40 bytes."""
     _fields_ = [("state_lo", C.c_uint64), ("state_hi", C.c_uint64), ("inc_lo", C.c_uint64), ("inc_hi", C.c_uint64),
@@ -133,6 +137,7 @@ _ENV_TYPES = {
     "restaurant": (RestaurantConfig, "info error_count snapshot"),
     "airline": (AirlineConfig, "info error_count snapshot"),
     "emergency": (EmergencyConfig, "info error_count snapshot"),
+    "space_station": (SpaceStationConfig, "info error_count snapshot"),
 }
 _HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
 

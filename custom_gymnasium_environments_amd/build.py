@@ -35,6 +35,8 @@ def is_stale():
 # the release library; tools/probes/guard_run.py replays the reference fixtures through it).  -DCGE_<ENV>_TIMING: on-device phase clocks.
 # -DCGE_AIRLINE_LDS_ROWS: the airline observation through an LDS tile, the store pass measured and dropped (profiles/airline_timing.txt).
 # -DCGE_EMERGENCY_LDS_ROWS: the same for the emergency observation (profiles/emergency_timing.txt).
+# -DCGE_STATION_LANE_ROWS: the space-station observation as per-lane row stores; there the LDS tile is the faster form and is built
+# (profiles/space_station_timing.txt).
 GUARD_FLAGS = ("-DCGE_MFG_GUARD", "-DCGE_GUARD")
 
 

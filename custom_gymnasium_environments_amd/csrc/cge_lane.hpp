@@ -1,4 +1,4 @@
-// cge_lane.hpp — what the lane-per-env types (bus, world builder, restaurant, airline, emergency) share that is not dynamics.
+// cge_lane.hpp — what the lane-per-env types (bus, world builder, restaurant, airline, emergency, space station) share that is not dynamics.
 //
 // Such a type steps one env per lane with the record in registers for the whole launch, and has step_kernel<MODE...>,
 // rollout_kernel<MODE..., ACTIONS> and reset_kernel(p, init, rewind), an error counter and a key-major observation slab.  Here are

@@ -45,7 +45,7 @@ def _batch(space, n):
     return {k: batch_space(v, n) for k, v in space.items()} if isinstance(space, dict) else batch_space(space, n)
 
 
-TERMINATED, TRUNCATED, BOTH = "terminated", "truncated", "both"
+TERMINATED, TRUNCATED, BOTH, TERMINATED_AT_LIMIT = "terminated", "truncated", "both", "terminated_at_limit"
 
 
 class DeviceVectorEnv(VectorEnvBase):
@@ -54,8 +54,9 @@ class DeviceVectorEnv(VectorEnvBase):
     `_obs_shape` (the shape of one observation buffer, set in __init__), and writes none of them; DESIGN.md §1 "One façade" has the
     table of variants.  `_flags` names the flag the type raises and with it the tensor that means "done": TERMINATED (`truncated` is
     NULL for the kernel and one shared all-False tensor for the caller; done = terminated), TRUNCATED (bus: both written,
-    done = truncated) or BOTH (done = the `done_mask` buffer the step kernel fills; a rollout's per-step flags are uint8
-    terminated | truncated << 1 instead of bool)."""
+    done = truncated), BOTH (done = the `done_mask` buffer the step kernel fills; a rollout's per-step flags are uint8
+    terminated | truncated << 1 instead of bool) or TERMINATED_AT_LIMIT (space station: both written, `truncated` only ever together
+    with `terminated`, so done = terminated and a rollout's per-step flags are the bool `terminated`)."""
 
     _abi = None  # e.g. "cge_snake"
     INFO_FIELDS = {}
@@ -194,7 +195,7 @@ class DeviceVectorEnv(VectorEnvBase):
     def invalid_action_count(self):
         """Synchronises; number of env-steps since the last call whose action the kernel reported instead of acting on (what counts
         is the type's: see its `_invalid_action_text`).  Reading clears the counter.  Only the types that export
-        `<abi>_error_count` have one (snake, bus, world builder, restaurant, airline, emergency); for the others this is an AttributeError."""
+        `<abi>_error_count` have one (snake, bus, world builder, restaurant, airline, emergency, space station); for the others this is an AttributeError."""
         return int(self._fn("error_count")(self._h, self._stream()))
 
     def check_actions(self):
@@ -242,7 +243,9 @@ class DeviceVectorEnv(VectorEnvBase):
         else:
             trunc = done = self._out("truncated", (self.num_envs,), torch.bool)
             trunc_ptr = trunc.data_ptr()
-            if self._flags == BOTH:
+            if self._flags == TERMINATED_AT_LIMIT:
+                done = term
+            elif self._flags == BOTH:
                 done = None
                 if same or self._ep_ret is not None:               # terminated | truncated, written by the step kernel itself
                     done = self._out("done", (self.num_envs,), torch.bool)

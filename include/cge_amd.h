@@ -874,6 +874,86 @@ const char *cge_emergency_last_error(const cge_emergency *h);
 const char *cge_emergency_last_kernel(const cge_emergency *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Space station  (space_station_env/station_env.py: SpaceStationEnv)                           */
+/*   Six crew members, twelve systems and eight modules in orbit; a step is five minutes.        */
+/*   terminated (:714-737): all six healths <= 0, three critical systems below 10 % efficiency,  */
+/*   mean oxygen < 15 or mean pressure < 80, or max_steps reached — which raises truncated too   */
+/*   (:343-344) and sets mission_success.                                                         */
+/*   action int32 0..39 (Discrete(40), :351-398).                                                 */
+/*   obs float32 [n_envs, 120] row-major (:739-783; the reference declares 110 and returns 120),  */
+/*   16-byte aligned.                                                                             */
+/*   Bit-exact: observations, the integer-valued reward, flags and the float64 info values, with  */
+/*   one caveat: the 32 Gaussian draws of a reset go through log(), and where the device's log    */
+/*   differs from glibc's in the last place the float64 module state after that reset does too.   */
+/*   Generator: the process-global NumPy legacy stream (normal, uniform, random, choice); the env */
+/*   never seeds it and its constructor draws nothing.  cge_space_station_seed is                 */
+/*   `np.random.seed(s_i); SpaceStationEnv()` for env i; the reset that follows draws the first   */
+/*   episode.  cge_space_station_create does the same with base seed 0.  Every later reset        */
+/*   continues the stream and keeps what the reference's reset() does not touch: episode_reward,  */
+/*   last_emergency_time, the crew's modules, solar_angle, radiation_level and                    */
+/*   total_power_consumption.                                                                     */
+/*   Device memory: 752 B of record + 2,560 B of generator per env (+ 8 B).                       */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_space_station cge_space_station;
+
+typedef struct {
+    int32_t autoreset_mode;      /* CGE_AUTORESET_* */
+    int32_t max_steps;           /* 1..65535; the reference's attribute of the same name, 8640 */
+} cge_space_station_config;
+
+enum { CGE_SPACE_STATION_OBS_FLOATS = 120, CGE_SPACE_STATION_RECORD_BYTES = 752, CGE_SPACE_STATION_ACTIONS = 40 };
+
+enum { /* cge_space_station_info float64 fields: the reference's nine info values (:785-797), then what else the record knows */
+    CGE_SPACE_STATION_INFO_TIME_STEP = 0,
+    CGE_SPACE_STATION_INFO_DAY = 1,
+    CGE_SPACE_STATION_INFO_CREW_ALIVE = 2,
+    CGE_SPACE_STATION_INFO_SYSTEM_FAILURES = 3,       /* the length of the reference's list of names */
+    CGE_SPACE_STATION_INFO_EMERGENCY_COUNT = 4,
+    CGE_SPACE_STATION_INFO_MISSION_SUCCESS = 5,
+    CGE_SPACE_STATION_INFO_EPISODE_REWARD = 6,        /* never reset by the reference: the sum over every episode since the seed */
+    CGE_SPACE_STATION_INFO_BATTERY_LEVEL = 7,
+    CGE_SPACE_STATION_INFO_AVG_CREW_HEALTH = 8,
+    CGE_SPACE_STATION_INFO_SYSTEM_FAILURE_MASK = 9,   /* bit s: system s is named in the list */
+    CGE_SPACE_STATION_INFO_NEEDS_RESET = 10,
+    CGE_SPACE_STATION_INFO_CREW_CASUALTIES = 11,      /* grows by one per dead member per step, as in the reference */
+    CGE_SPACE_STATION_INFO_EVACUATED = 12             /* action 38 was taken since the seed: everybody is in Docking */
+};
+
+/* SpaceStationEnv.__init__ :56-135 on the stream np.random.seed(env_index0 + i) */
+int cge_space_station_create(const cge_space_station_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_space_station **out);
+int cge_space_station_destroy(cge_space_station *h);
+/* np.random.seed(s_i); SpaceStationEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+int cge_space_station_seed(cge_space_station *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :247-308 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
+int cge_space_station_reset(cge_space_station *h, const uint8_t *mask, float *obs_out, void *stream);
+/* step :310-349.  actions int32 [n_envs].  An action outside 0..39 skips _process_action — 40 and above fall through every branch
+ * of it in the reference, a negative one would index its list of systems from the back — the rest of the step runs, and a
+ * device-side counter is bumped (cge_space_station_error_count).  truncated_out (nullable) is 1 where max_steps ended the episode,
+ * which sets terminated too.  final_obs_out (nullable): SAME_STEP writes the rows of every wave of 64 envs that holds an env
+ * terminated in this step; valid where terminated. */
+int cge_space_station_step(cge_space_station *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out,
+                           uint8_t *truncated_out, float *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs], or NULL: env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 40, 0).
+ * obs_out: k batches obs_step_stride floats apart (>= 120 * n_envs, a multiple of 4), or with stride 0 the last step's.
+ * terminated_traj_out [k, n_envs]; done_count counts terminated steps.  Terminal rows of a SAME_STEP rollout and the per-step
+ * truncated flag (terminated at time_step == max_steps) are not delivered. */
+int cge_space_station_rollout(cge_space_station *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
+                              int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
+                              int32_t *done_count_out, void *stream);
+int cge_space_station_info(cge_space_station *h, int32_t field_id, double *out, void *stream);
+/* env-steps whose action was outside 0..39 since the last call; synchronises */
+int64_t cge_space_station_error_count(cge_space_station *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_space_station_snapshot_bytes(const cge_space_station *h);
+int cge_space_station_snapshot_get(cge_space_station *h, void *host_buf, void *stream);
+int cge_space_station_snapshot_set(cge_space_station *h, const void *host_buf, void *stream);
+size_t cge_space_station_device_bytes(const cge_space_station *h);
+int cge_space_station_episode_stats(cge_space_station *h, double *return_out, int32_t *length_out);
+const char *cge_space_station_last_error(const cge_space_station *h);
+const char *cge_space_station_last_kernel(const cge_space_station *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
 /*   game_logic.py: GameLogic)                                                                    */
 /*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */
