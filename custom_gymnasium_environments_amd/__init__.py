@@ -17,11 +17,12 @@ from .restaurant import RestaurantVectorEnv  # noqa: F401
 from .airline import AirlineVectorEnv  # noqa: F401
 from .emergency import EmergencyVectorEnv  # noqa: F401
 from .space_station import SpaceStationVectorEnv  # noqa: F401
+from .farm import AgriculturalFarmVectorEnv  # noqa: F401
 from . import sharding  # noqa: F401
 from .sharding import gather_obs, make_sharded, shard_range  # noqa: F401
 from .registry import NumpyVectorEnv, make_vec, registered_ids  # noqa: F401
 from .sampling import DeviceSpaceSampler  # noqa: F401
 from ._spaces import Dict, MultiBinary  # noqa: F401
 
-__all__ = ["SnakeVectorEnv", "CryptoVectorEnv", "TrafficVectorEnv", "ParkingVectorEnv", "ClimateVectorEnv", "FleetVectorEnv", "ManufacturingVectorEnv", "HospitalVectorEnv", "BusVectorEnv", "WorldBuilderVectorEnv", "RestaurantVectorEnv", "AirlineVectorEnv", "EmergencyVectorEnv", "SpaceStationVectorEnv", "sharding", "make_sharded", "gather_obs", "shard_range", "make_vec", "registered_ids", "NumpyVectorEnv", "AutoresetMode", "DeviceVectorEnv", "NativeLibraryError", "native_lib", "DeviceSpaceSampler", "Dict", "MultiBinary"]
+__all__ = ["SnakeVectorEnv", "CryptoVectorEnv", "TrafficVectorEnv", "ParkingVectorEnv", "ClimateVectorEnv", "FleetVectorEnv", "ManufacturingVectorEnv", "HospitalVectorEnv", "BusVectorEnv", "WorldBuilderVectorEnv", "RestaurantVectorEnv", "AirlineVectorEnv", "EmergencyVectorEnv", "SpaceStationVectorEnv", "AgriculturalFarmVectorEnv", "sharding", "make_sharded", "gather_obs", "shard_range", "make_vec", "registered_ids", "NumpyVectorEnv", "AutoresetMode", "DeviceVectorEnv", "NativeLibraryError", "native_lib", "DeviceSpaceSampler", "Dict", "MultiBinary"]
 __version__ = "0.1.0"

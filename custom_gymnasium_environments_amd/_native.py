@@ -82,6 +82,10 @@ class SpaceStationConfig(C.Structure):
     _fields_ = [("autoreset_mode", C.c_int32), ("max_steps", C.c_int32)]
 
 
+class FarmConfig(C.Structure):
+    _fields_ = [("autoreset_mode", C.c_int32), ("max_years", C.c_int32), ("compact_obs", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Pcg64State(C.Structure):
     """cge_pcg64_state: NumPy's PCG64 bit_generator.state as 40 bytes."""
     _fields_ = [("state_lo", C.c_uint64), ("state_hi", C.c_uint64), ("inc_lo", C.c_uint64), ("inc_hi", C.c_uint64),
@@ -138,6 +142,7 @@ _ENV_TYPES = {
     "airline": (AirlineConfig, "info error_count snapshot"),
     "emergency": (EmergencyConfig, "info error_count snapshot"),
     "space_station": (SpaceStationConfig, "info error_count snapshot"),
+    "farm": (FarmConfig, "info error_count snapshot"),
 }
 _HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
 

@@ -195,7 +195,7 @@ class DeviceVectorEnv(VectorEnvBase):
     def invalid_action_count(self):
         """Synchronises; number of env-steps since the last call whose action the kernel reported instead of acting on (what counts
         is the type's: see its `_invalid_action_text`).  Reading clears the counter.  Only the types that export
-        `<abi>_error_count` have one (snake, bus, world builder, restaurant, airline, emergency, space station); for the others this is an AttributeError."""
+        `<abi>_error_count` have one (snake, bus, world builder, restaurant, airline, emergency, space station, farm); for the others this is an AttributeError."""
         return int(self._fn("error_count")(self._h, self._stream()))
 
     def check_actions(self):

@@ -954,6 +954,93 @@ const char *cge_space_station_last_error(const cge_space_station *h);
 const char *cge_space_station_last_kernel(const cge_space_station *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Agricultural farm  (agricultural_farm_env/farm_env.py: AgriculturalFarmEnv,                  */
+/*   crops/crop_data.py)                                                                          */
+/*   Four fields, eight machines, a market of five crops, weather by season; a step is a day, a  */
+/*   season 90 days.  terminated only (:612-621): year > max_years (in the step that makes the   */
+/*   day a multiple of 360), or cash_flow < -50000 (-5000); the soil termination cannot fire.    */
+/*   action int32 0..44 (Discrete(45), :629-800).                                                 */
+/*   obs float32 [n_envs, 620] row-major (:435-518): 134 live values and 486 zeros, as the        */
+/*   reference pads them; 16-byte aligned.  compact_obs: [n_envs, 134], 8-byte aligned.           */
+/*   Bit-exact: observations, the integer-valued reward, the flag and the float64 info values,   */
+/*   with one caveat: the five Gaussians of a step's prices go through log(), and where the      */
+/*   device's log differs from glibc's in the last place a float64 price does too.  The number   */
+/*   of draws never depends on a price.                                                           */
+/*   Generators: TWO streams per env, both process-global in the reference and seeded by none of */
+/*   its code: NumPy's legacy one (uniform, random, randint, normal) and CPython's `random`      */
+/*   (random.choice of the crop to plant).  cge_farm_seed is `random.seed(s_i);                   */
+/*   np.random.seed(s_i); AgriculturalFarmEnv()` for env i — the constructor draws the fields,   */
+/*   the equipment and the market — and the reset that follows draws them again.                  */
+/*   cge_farm_create does the same with base seed 0.  Every later reset continues both streams,  */
+/*   the legacy Gaussian's cached second value included, and keeps what the reference's reset()  */
+/*   does not touch: water_quality.                                                               */
+/*   Device memory: 832 B of record + 2 x 2,560 B of generators per env (+ 8 B).                  */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct cge_farm cge_farm;
+
+typedef struct {
+    int32_t autoreset_mode;      /* CGE_AUTORESET_* */
+    int32_t max_years;           /* 1..255; the reference's attribute of the same name (:139), 1 */
+    int32_t compact_obs;         /* 0: rows of 620 floats as the reference returns them; 1: their 134 leading values only */
+    int32_t reserved;
+} cge_farm_config;
+
+enum { CGE_FARM_OBS_FLOATS = 620, CGE_FARM_COMPACT_OBS_FLOATS = 134, CGE_FARM_RECORD_BYTES = 832, CGE_FARM_ACTIONS = 45 };
+
+enum { /* cge_farm_info float64 fields: the reference's eleven scalar info values (:911-924), field_status (:925-934), then what else the record knows */
+    CGE_FARM_INFO_DAY = 0,
+    CGE_FARM_INFO_SEASON = 1,                     /* 0 spring .. 3 winter; the reference gives the name */
+    CGE_FARM_INFO_YEAR = 2,
+    CGE_FARM_INFO_CASH_FLOW = 3,
+    CGE_FARM_INFO_TOTAL_REVENUE = 4,
+    CGE_FARM_INFO_TOTAL_EXPENSES = 5,
+    CGE_FARM_INFO_PROFIT_MARGIN = 6,
+    CGE_FARM_INFO_CARBON_SEQUESTERED = 7,
+    CGE_FARM_INFO_WATER_CONSERVATION_SCORE = 8,
+    CGE_FARM_INFO_BIODIVERSITY_INDEX = 9,
+    CGE_FARM_INFO_SOIL_HEALTH_TREND = 10,
+    CGE_FARM_INFO_FIELD_CROP = 11,                /* + field 0..3: the crop's index, -1 where the reference prints "None" (wheat too) */
+    CGE_FARM_INFO_FIELD_STAGE = 15,               /* + field 0..3: CropStage 0..7 */
+    CGE_FARM_INFO_FIELD_HEALTH = 19,              /* + field 0..3 */
+    CGE_FARM_INFO_FIELD_YIELD_POTENTIAL = 23,     /* + field 0..3 */
+    CGE_FARM_INFO_NEEDS_RESET = 27,
+    CGE_FARM_INFO_WATER_QUALITY = 28              /* not reset by the reference */
+};
+
+/* AgriculturalFarmEnv.__init__ :127-192 on the streams random.seed / np.random.seed(env_index0 + i) */
+int cge_farm_create(const cge_farm_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_farm **out);
+int cge_farm_destroy(cge_farm *h);
+/* random.seed(s_i); np.random.seed(s_i); AgriculturalFarmEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).
+ * Call reset next. */
+int cge_farm_seed(cge_farm *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
+/* reset :520-566 for envs with mask[i] != 0 (all if NULL), continuing each env's streams; writes every row if obs_out != NULL */
+int cge_farm_reset(cge_farm *h, const uint8_t *mask, float *obs_out, void *stream);
+/* step :568-627.  actions int32 [n_envs].  An action outside 0..44 falls through every branch of _process_action (:629-800), as in
+ * the reference; the rest of the step runs, and a device-side counter is bumped (cge_farm_error_count).  truncated_out (nullable)
+ * is written 0.  final_obs_out (nullable): SAME_STEP writes the rows of every wave of 64 envs that holds an env terminated in this
+ * step; valid where terminated. */
+int cge_farm_step(cge_farm *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
+                  float *final_obs_out, void *stream);
+/* k fused steps.  actions int32 [k, n_envs], or NULL: env i takes cge_hash_action(action_seed, env_index0 + i, t0 + t, 45, 0).
+ * obs_out: k batches obs_step_stride floats apart (>= the row width * n_envs; a multiple of 4, compact_obs: of 2), or with stride 0
+ * the last step's.  terminated_traj_out [k, n_envs]; done_count counts terminated steps.  Terminal rows of a SAME_STEP rollout are
+ * not delivered. */
+int cge_farm_rollout(cge_farm *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out, int64_t obs_step_stride,
+                     float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out, int32_t *done_count_out, void *stream);
+int cge_farm_info(cge_farm *h, int32_t field_id, double *out, void *stream);
+/* env-steps whose action was outside 0..44 since the last call; synchronises */
+int64_t cge_farm_error_count(cge_farm *h, void *stream);
+/* whole-handle checkpoint (host memory, opaque: 32-byte header + the device arrays in device layout); restores only
+ * into a handle created with the same n_envs and config; both calls synchronise `stream` */
+size_t cge_farm_snapshot_bytes(const cge_farm *h);
+int cge_farm_snapshot_get(cge_farm *h, void *host_buf, void *stream);
+int cge_farm_snapshot_set(cge_farm *h, const void *host_buf, void *stream);
+size_t cge_farm_device_bytes(const cge_farm *h);
+int cge_farm_episode_stats(cge_farm *h, double *return_out, int32_t *length_out);
+const char *cge_farm_last_error(const cge_farm *h);
+const char *cge_farm_last_kernel(const cge_farm *h);
+
+/* ------------------------------------------------------------------------------------------ */
 /* World builder  (world_builder_env/src/environment/world_builder_env.py: WorldBuilderEnv,      */
 /*   game_logic.py: GameLogic)                                                                    */
 /*   A G x G grid (G = 2..10, default 10, :39), food / wood / stone, a population; five actions:  */

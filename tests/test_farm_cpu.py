@@ -1,0 +1,265 @@
+"""CPU-side checks of the agricultural-farm env: the model (tests/farm_model.py) reproduces, bit for bit, what the unmodified reference
+recorded (tests/golden/farm_*.npz, written by tests/golden/gen/gen_farm.py), the autoreset observations and the stepping past
+termination included; the kernels' own dynamics code, built for the host, does too, sums its means in NumPy's order, carries Python's
+stage durations and draws the two streams as NumPy and CPython do; the C ABI is declared, exported and bound; there is no CPU path;
+the spaces are the reference's; no kernel of the type uses scratch."""
+import ctypes
+import json
+import os
+import random
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import farm_model as fm
+from conftest import ROOT, golden
+
+FIXTURES = ["farm_hash.npz", "farm_bankrupt.npz", "farm_orchard.npz", "farm_chores.npz", "farm_overrun.npz", "farm_two_years.npz"]
+ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
+       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
+HOST_CHECK = os.path.join(ROOT, "tools", "probes", "farm_host_check.py")
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+def bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view(np.uint32 if x.dtype == np.float32 else np.uint64)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_model_reproduces_the_reference(name):
+    z = golden(name)
+    n, T = z["reward"].shape
+    obs_ref = fm.fixture_obs(z)
+    assert obs_ref.shape == (n, T, fm.LIVE) and obs_ref.dtype == np.float32
+    assert json.loads(str(z["info_keys"])) == list(fm.INFO) + [f"{k}_{f}" for k in fm.FIELD_INFO for f in range(4)]
+    autoreset = bool(int(z["autoreset"]))
+    m = fm.FarmModel(int(z["seed0"]) + np.arange(n), fm.SAME_STEP if autoreset else fm.DISABLED, int(z["max_years"]), width=fm.LIVE)
+    assert np.array_equal(bits(m.reset()), bits(z["obs0"])) and np.array_equal(bits(m.info()), bits(z["info0"]))
+    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
+    seen = 0
+    for t in range(T):
+        obs, reward, terminated, final, info = m.step(z["actions"][:, t])
+        assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
+        assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)), t
+        assert np.array_equal(bits(final), bits(obs_ref[:, t])), t                         # the reference's step() returns the terminal observation
+        assert np.array_equal(bits(info), bits(z["info"][:, t])), t                        # the eleven values and field_status
+        for i in np.flatnonzero(terminated & autoreset):                                   # then reset() continues the env's streams
+            seen += 1
+            assert np.array_equal(bits(obs[i]), bits(z["reset_obs"][where[(int(i), t)]])), (t, i)
+    assert seen == len(where) and m.invalid == 0
+    if not autoreset:
+        assert z["terminated"].any() and len(where) == 0                                   # stepped on past termination
+
+
+def test_model_pads_the_row_with_zeros():
+    m = fm.FarmModel([3, 4])
+    row = m.reset()
+    assert row.shape == (2, 620) and row.dtype == np.float32 and not row[:, 134:].any() and row[:, :134].any()
+    assert np.array_equal(bits(row[:, :134]), bits(fm.FarmModel([3, 4], width=134).reset()))
+
+
+def test_fixtures_cover_what_they_are_for():
+    h, b, o, c, ov, ty = (golden(f) for f in FIXTURES)
+    ev = {f: json.loads(str(z["events"])) for f, z in zip(FIXTURES, (h, b, o, c, ov, ty))}
+    assert h["reward"].shape == (8, 400) and b["reward"].shape == (8, 100) and o["reward"].shape == (4, 400) and c["reward"].shape == (4, 400)
+    assert ov["reward"].shape == (4, 400) and ty["reward"].shape == (4, 730)
+    assert h["actions"].min() == 0 and h["actions"].max() == 44 and (b["actions"] == 40).all()
+    assert int(ty["max_years"]) == 2 and all(int(z["max_years"]) == 1 for z in (h, b, o, c, ov))
+    # farm_hash: an end at day 360 followed by an autoreset, a random.choice in every planting season, frost, a long drought, a
+    # negative observed health, a reset observation that carries a changed water_quality
+    hv = ev["farm_hash.npz"]
+    assert hv["year_end"] >= 1 and min(hv["choice_spring"], hv["choice_summer"], hv["choice_fall"]) >= 1 and hv["plant_winter"] >= 1
+    assert hv["frost_high"] >= 1 and hv["drought_long"] >= 1 and hv["negative_health"] >= 1 and hv["invalid_fifth_field"] >= 1
+    assert hv["year_end"] + hv["bankrupt"] == len(h["reset_index"]) == int(h["terminated"].sum()) and hv["soil_end"] == 0
+    ends = h["info"][h["terminated"].astype(bool)]
+    assert (ends[ends[:, 2] == 2][:, 0] == 360).all() and (ends[:, 2] == 2).sum() == hv["year_end"]      # year 2 begins at day 360
+    hobs = fm.fixture_obs(h)
+    assert (hobs[..., 2:60:15] < 0).any() and (hobs[..., 65] > 0.5).any() and (hobs[..., 66] > np.float32(20 / 30.0)).any()
+    assert (h["reset_obs"][:, 122] != np.float32(0.9)).sum() == hv["carried_water_quality"] >= 1
+    assert (h["reset_obs"][:, 69] == 0).all() and (h["reset_obs"][:, 125] == 0.5).all()    # day 0, cash 50000 / 100000
+    # farm_bankrupt: action 40 only; every env bankrupt at day 80 or 81 with -5000 and reset once; water_quality, which action 40
+    # never changes, is the constructor's in the reset observation
+    bv = ev["farm_bankrupt.npz"]
+    assert bv["bankrupt"] == 8 == len(b["reset_index"]) and sorted(set(b["reset_index"][:, 0])) == list(range(8))
+    assert set(b["reset_index"][:, 1]) <= {79, 80}                                         # the step that makes the day 80 or 81
+    at = b["terminated"].astype(bool)
+    assert (b["reward"][at] <= -5000).all() and (b["info"][at][:, 3] < -50000).all() and (b["reset_obs"][:, 122] == np.float32(0.9)).all()
+    # farm_orchard: field 3 planted and harvested by hand and by the automatic harvest, replanted with and without the rotation bonus
+    ov_ = ev["farm_orchard.npz"]
+    assert min(ov_["harvest_action"], ov_["harvest_auto"], ov_["replant_bonus"], ov_["replant_no_bonus"], ov_["replant_after_wheat"]) >= 1
+    assert set(np.unique(o["actions"])) == {3, 8} and (o["actions"][:, 0:100:2] == 3).all() and (o["actions"][:, 1:100:2] == 8).all() and (o["actions"][:, 100:200] == 3).all()
+    # farm_chores: refusals, over-fertilisation, a sale taken and one refused, action 43 with and without three truthy crop types.
+    # Nothing is ever repaired: maintenance_needed stays below 0.5 in the reference (0.2 at most, plus 0.02 for each of the at most
+    # ten operations a tank allows), so that branch of action 44 is the model's alone.
+    cv = ev["farm_chores.npz"]
+    assert min(cv["fert_refused"], cv["over_fertilised"], cv["pest_refused"], cv["equipment_refused"], cv["sale_taken"], cv["sale_refused"],
+               cv["rotation_three"], cv["rotation_fewer"]) >= 1 and cv["year_end"] >= 1 and cv["carried_water_quality"] >= 1
+    assert all(v["maintenance_repair"] == 0 and v["excessive_rain"] == 0 and v["soil_end"] == 0 for v in ev.values())
+    assert all((fm.fixture_obs(z)[..., 73:110:5] < 0.5).all() for z in (h, b, o, c, ov, ty))
+    chores = {10, 11, 12, 13, 15, 16, 17, 18, 20, 21, 22, 23, 25, 26, 27, 28, 29, 30, 31, 32, 33, 35, 36, 37, 38, 39, 41, 42, 43, 44}
+    assert set(np.unique(c["actions"])) == chores | {3} and (c["actions"][:, [31, 211]] == 3).all() and (c["actions"][:, 0:30:2] == np.array(sorted(chores))[:15]).all()
+    # farm_overrun: stepped on past termination
+    assert ov["terminated"].any() and len(ov["reset_index"]) == 0 and not ov["terminated"][:, 0].any() and (ov["terminated"].sum(1) >= 30).all()
+    # farm_two_years: the second year's climate shift, an end at day 720
+    tv = ev["farm_two_years.npz"]
+    assert tv["climate_temperature"] >= 1 and tv["year_end"] >= 1
+    ends = ty["info"][ty["terminated"].astype(bool)]
+    assert (ends[ends[:, 2] == 3][:, 0] == 720).all() and (ends[:, 2] == 3).sum() == tv["year_end"] and (ty["info"][..., 2] == 2).any()
+    for z in (h, b, o, c, ov, ty):
+        assert not z["terminated"][:, 0].any() and z["reward"].dtype == np.float64 and np.array_equal(z["reward"], np.round(z["reward"]))
+        assert np.abs(z["reward"]).max() < 2 ** 24                                         # integers a float32 holds exactly
+    for f in FIXTURES:
+        assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) < 1 << 20
+
+
+def test_hash_actions_equal_the_shared_hash():
+    from _hash_actions import common
+    a = fm.hash_actions(77, 5, 6, t0=40, env0=1000)
+    assert a.shape == (5, 6) and a.dtype == np.int32
+    for t in range(5):
+        for i in range(6):
+            assert int(a[t, i]) == common.hash_action(77, 1000 + i, 40 + t, 45, 0)
+    z = golden("farm_hash.npz")
+    assert np.array_equal(fm.hash_actions(int(z["a_seed"]), 30, 8).T, z["actions"][:, :30])
+
+
+def test_kernel_dynamics_replay_the_fixtures_on_the_host():
+    """csrc/farm_env.hpp — the record's packing, the draw order of both streams and the step logic the kernels run — compiled for the
+    CPU (with glibc's log) and replayed over every fixture: observations, rewards, the flag and the float64 info values bit for bit
+    (tools/probes/farm_host_check.py, which takes the PATH's host compiler or the clang++ behind hipcc: the test fails, it does not
+    skip, where neither is there)."""
+    out = subprocess.run([sys.executable, HOST_CHECK], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = [line for line in out.stdout.splitlines() if "mismatching" in line]
+    assert len(lines) == len(FIXTURES) and all(line.endswith(" 0 mismatching steps") for line in lines), out.stdout
+
+
+def test_mean_of_four_is_summed_in_numpys_order():
+    """np.mean over the four fields' organic matter and compaction: below eight values a plain loop.  The host build of mean4 and the
+    model's against np.mean on 5,000 random vectors, every one bit for bit."""
+    rng = np.random.default_rng(4)
+    v = 0.04 + rng.uniform(-0.03, 0.06, (5000, 4)) * rng.uniform(0.0, 1.0, (5000, 1))
+    v[:200] = 0.045 + rng.uniform(-1e-16, 1e-16, (200, 4))
+    want = np.array([np.mean(list(row)) for row in v])
+    tree = np.array([((row[0] + row[1]) + (row[2] + row[3])) / 4.0 for row in v])
+    assert (tree != want).sum() > 100                                                      # the order matters for these vectors
+    assert np.array_equal(bits(np.array([fm.mean4(list(row)) for row in v])), bits(want))
+    out = subprocess.run([sys.executable, HOST_CHECK, "--mean"], input=v.tobytes(), capture_output=True)
+    assert out.returncode == 0, out.stderr.decode()
+    got = np.frombuffer(out.stdout, np.float64)
+    assert got.shape == want.shape and np.array_equal(bits(got), bits(want))
+
+
+def test_stage_durations_equal_pythons_int():
+    """int(growth_cycle_days * percentage) for the five crops and the eight stages (0.1 where a stage is not listed), in Python's float
+    arithmetic: int(365 * 0.01) is 3, int(90 * 0.35) is 31"""
+    want = [[int(fm.CYCLE[c] * p) for p in fm.STAGE_PCT[c]] for c in range(5)]
+    assert want[3][0] == int(365 * 0.01) == 3 and want[0][2] == int(90 * 0.35) == 31 and want[3][7] == int(365 * 0.14) == 51 and want[0][7] == 9
+    assert [list(r) for r in fm.STAGE_DAYS] == want and min(min(r) for r in want) >= 3      # never a modulus of zero
+    out = subprocess.run([sys.executable, HOST_CHECK, "--stage-days"], capture_output=True)
+    assert out.returncode == 0, out.stderr.decode()
+    assert np.frombuffer(out.stdout, np.int32).reshape(5, 8).tolist() == want
+
+
+@pytest.mark.parametrize("seed", [0, 7, 123456])
+def test_draws_equal_numpy_and_cpython(seed):
+    """the legacy randint(0, 25) of the equipment's locations (one masked word per attempt) and random.choice's _randbelow(5 | 3 | 1)
+    (the top k bits of a word; _randbelow(1) draws until a zero bit), host build against NumPy and CPython"""
+    out = subprocess.run([sys.executable, HOST_CHECK, "--randint", str(seed), "2000"], capture_output=True)
+    assert out.returncode == 0, out.stderr.decode()
+    rs = np.random.RandomState(seed)
+    assert np.frombuffer(out.stdout, np.uint32).tolist() == [int(rs.randint(0, 25)) for _ in range(2000)]
+    for n in (5, 3, 1):
+        out = subprocess.run([sys.executable, HOST_CHECK, "--randbelow", str(seed), str(n), str(n.bit_length()), "1000"], capture_output=True)
+        assert out.returncode == 0, out.stderr.decode()
+        py = random.Random(seed)
+        want = [py.choice(range(n)) for _ in range(1000)]
+        assert np.frombuffer(out.stdout, np.uint32).tolist() == want
+        py2 = random.Random(seed)
+        assert [py2._randbelow(n) for _ in range(1000)] == want
+
+
+def test_host_record_equals_the_model():
+    """the float64 record after 64 hashed steps — the Gaussians of 320 prices, the one place libm's log enters — host build against
+    the model, which draws NumPy's own normal(), bit for bit"""
+    n, k = 16, 64
+    acts = fm.hash_actions(9, k, n, envs=np.arange(n))
+    out = subprocess.run([sys.executable, HOST_CHECK, "--record", "2000", str(n), str(k)], input=np.ascontiguousarray(acts, np.int32).tobytes(), capture_output=True)
+    assert out.returncode == 0, out.stderr.decode()
+    got = np.frombuffer(out.stdout, np.float64).reshape(n, 89)
+    m = fm.FarmModel(2000 + np.arange(n), fm.SAME_STEP)
+    m.reset()
+    for t in range(k):
+        m.step(acts[t])
+    for j, e in enumerate(m.envs):
+        want = [x for f in e.fields for x in (f.health, f.yp, f.moisture, f.ph, f.n, f.p, f.k, f.compaction, f.om, f.pest, f.disease)]
+        want += e.fuel + e.maint + [e.temp, e.hum, e.rain, e.wind, e.frost] + e.price + e.pred
+        want += [e.reservoir, e.water_quality, e.cash, e.costs, e.margin, e.revenue, e.expenses, e.carbon, e.wcs, e.bio, e.trend, e.climate]
+        assert np.array_equal(bits(got[j, :87]), bits(np.array(want, np.float64))), j
+        assert got[j, 88] == e.ep_ret
+
+
+def test_abi_is_declared_exported_and_bound():
+    from custom_gymnasium_environments_amd import _native, build
+    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(cge_farm_[a-z0-9_]+)\s*\(", src))
+    assert declared == {f"cge_farm_{fn}" for fn in ABI}
+    assert {n for n in _native.SIGNATURES if n.startswith("cge_farm_")} == declared
+    build.build_native()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    assert not [n for n in declared if not hasattr(L, n)]
+    assert ctypes.sizeof(_native.FarmConfig) == 16 and [f[0] for f in _native.FarmConfig._fields_] == ["autoreset_mode", "max_years", "compact_obs", "reserved"]
+
+
+def test_no_cpu_path():
+    import torch
+    import custom_gymnasium_environments_amd as cge
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(cge.NativeLibraryError):
+        cge.AgriculturalFarmVectorEnv(8)
+    with pytest.raises(cge.NativeLibraryError):
+        cge.AgriculturalFarmVectorEnv(8, device="cpu")
+
+
+def test_spaces_equal_the_reference():
+    rec = json.loads(str(golden("farm_hash.npz")["spaces"]))
+    from custom_gymnasium_environments_amd import farm
+    from custom_gymnasium_environments_amd._spaces import Box, Discrete, batch_space
+    assert rec["action"] == {"kind": "Discrete", "n": 45} and farm.NUM_ACTIONS == 45
+    o = rec["observation"]
+    assert o["kind"] == "Box" and o["dtype"] == "float32" and o["low"] == -np.inf and o["high"] == np.inf
+    assert o["shape"] == [620] == [farm.OBS_DIM] and o["live"] == 134 == farm.COMPACT_OBS_DIM
+    sp = Box(-np.inf, np.inf, (farm.OBS_DIM,), np.float32)
+    assert tuple(batch_space(sp, 6).shape) == (6, 620) and [int(v) for v in batch_space(Discrete(45), 6).nvec] == [45] * 6
+    assert tuple(farm.REFERENCE_INFO_KEYS) == fm.INFO and tuple(farm.FIELD_INFO_KEYS) == fm.FIELD_INFO
+    assert list(farm.INFO_FIELDS)[:11] == list(fm.INFO) and [farm.INFO_FIELDS[k] for k in fm.FIELD_INFO] == [11, 15, 19, 23]
+    assert farm.RECORD_BYTES == 832 and farm.GENERATOR_BYTES == 5120 and len(farm.CROPS) == 5 and len(farm.SEASONS) == 4
+
+
+def test_no_kernel_uses_scratch(tmp_path):
+    """the condition of DESIGN.md §3.18: the record stays in registers.  The private-segment size of every cge::farm kernel, read from
+    the built library's code-object notes as tests/test_kernel_occupancy.py reads the register counts"""
+    from custom_gymnasium_environments_amd import build
+    lib = os.path.join(str(tmp_path), "lib.so")
+    shutil.copy(build.build_native(), lib)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", lib], cwd=str(tmp_path), check=True, capture_output=True)
+    found = {}
+    for f in sorted(os.listdir(str(tmp_path))):
+        if "amdgcn" not in f:
+            continue
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(str(tmp_path), f)], capture_output=True, text=True).stdout
+        for blk in notes.split("  - .agpr_count:")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", blk)
+            private = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
+            if name and private and "3cge4farm" in name.group(1):
+                found[name.group(1)] = int(private.group(1))
+    kinds = {k: [n for n in found if k in n] for k in ("11step_kernel", "14rollout_kernel", "12reset_kernel")}
+    assert len(kinds["11step_kernel"]) == 3 and len(kinds["14rollout_kernel"]) == 6 and len(kinds["12reset_kernel"]) == 1, sorted(found)
+    assert all(v == 0 for v in found.values()), found
