@@ -6,12 +6,14 @@ an `np.random.RandomState` (the process-global NumPy legacy stream of the refere
 What reset() leaves alone is kept across episodes, as the reference keeps it: `water_quality` (`irrigation_capacity` and `water_costs`
 never change at all), and both streams with the legacy Gaussian's cached second value.  `operation_field` is never set, so an operating
 machine compacts nothing; `last_irrigated_day`, `debt_level`, `groundwater_level` and `solar_radiation` are never read or never change.
-The soil termination (:619-621) and the excessive-rain penalty (:879-881) are written as the reference writes them; no fixture reaches
-them.
+The soil termination (:619-621) is written as the reference writes it; the clip of :388 keeps every fixture out of it
+(tests/golden/lane_env_unreachable.json).  The excessive-rain penalty (:879-881) and the repair of action 44 are entered by
+farm_poked.npz, whose `pokes` table poke() applies.
 
 tests/test_farm_cpu.py pins the model to fixtures recorded from the unmodified reference; the GPU tests use it where the fixtures
 cannot reach.  Test infrastructure only: the product never imports it.
 """
+import json
 import random
 
 import numpy as np
@@ -422,6 +424,33 @@ class _Env:
         return ([self.day, self.season, self.year, self.cash, self.revenue, self.expenses, self.margin, self.carbon, self.wcs, self.bio, self.trend]
                 + [f.crop if f.crop > 0 else -1 for f in self.fields] + [f.stage for f in self.fields] + [f.health for f in self.fields]
                 + [f.yp for f in self.fields])
+
+
+def poke(env, name, value):
+    """set the plain state field that csrc/farm_env.hpp calls `name` (a fixture's `pokes` table; tools/probes/farm_host_check.cpp
+    --layout lists the names): f<k>.<member> of a field, fuel<q> / maint<q> of a machine, a scalar"""
+    head, _, member = name.partition(".")
+    if member:
+        assert head[0] == "f" and member in ("health", "yp", "moisture", "ph", "n", "p", "k", "compaction", "om", "pest", "disease"), name
+        setattr(env.fields[int(head[1:])], member, float(value))
+    elif name[:-1] in ("fuel", "maint"):
+        getattr(env, name[:-1])[int(name[-1])] = float(value)
+    elif name in ("day", "drought", "rain_days"):
+        setattr(env, name, int(value))
+    else:
+        attr = {"quality": "water_quality"}.get(name, name)
+        assert attr in ("temp", "hum", "rain", "wind", "frost", "reservoir", "water_quality", "cash", "bio", "trend", "climate"), name
+        setattr(env, attr, float(value))
+
+
+def fixture_pokes(z):
+    """{step: [(env, field name, value)]} of a fixture's `pokes` table (empty for a fixture without one)"""
+    out = {}
+    if "pokes" in z:
+        names = json.loads(str(z["poke_fields"]))
+        for i, t, k, value in z["pokes"]:
+            out.setdefault(int(t), []).append((int(i), names[int(k)], float(value)))
+    return out
 
 
 class FarmModel:

@@ -20,7 +20,9 @@ The event counters are taken by watching the env from outside: its methods are w
 `obs_xor` is the per-step observation as uint32 bit patterns [env, element, step], each step XORed with the step before it;
 emergency_model.fixture_obs() undoes it.  `info` holds the six info values, `termination_reason` as a code (0 none, 1 success,
 2 casualties, 3 overwhelmed, 4 timeout).
-Outputs: tests/golden/emergency_hash.npz, emergency_dispatch.npz, emergency_idle.npz, emergency_timeout.npz, emergency_overrun.npz.
+Outputs: tests/golden/emergency_hash.npz, emergency_dispatch.npz, emergency_idle.npz, emergency_timeout.npz, emergency_overrun.npz (RUNS)
+and emergency_day.npz (NEW_RUNS; `python gen_emergency.py --new` writes it alone and leaves the others' bytes as they are): like
+emergency_overrun it never resets, and it runs on to 22:10 on the env's clock, through every arm of the traffic's hour-of-day chain.
 """
 import json
 import os
@@ -41,6 +43,8 @@ INFO = ("active_emergencies", "total_casualties", "lives_saved", "emergencies_re
 REASONS = {None: 0, "success": 1, "casualties": 2, "overwhelmed": 3, "timeout": 4}
 EVENTS = ("success", "casualties", "overwhelmed", "timeout", "escalations", "cascades", "mutual_aid", "national_guard", "gridlock", "quick_response",
           "escalated_after_work", "full", "prev_carried", "resolved", "overallocated")
+# counted in the runs of NEW_RUNS only (the older files' `events` have the keys above): steps by the hour-of-day arm of :787-792
+NEW_EVENTS = ("hour_night_early", "hour_before_rush", "hour_rush_morning", "hour_midday", "hour_rush_evening", "hour_evening", "hour_night_late")
 OBS = 276
 
 
@@ -107,6 +111,10 @@ def run_env(seed, T, a_seed, i, policy, autoreset, ev, max_timesteps=None):
     for t in range(T):
         a = action(policy, a_seed, i, t)
         resolved = env.emergencies_resolved
+        if "hour_midday" in ev:
+            hour = (env.current_timestep // 60) % 24
+            ev["hour_night_early" if hour <= 5 else "hour_before_rush" if hour < 7 else "hour_rush_morning" if hour <= 9 else "hour_midday" if hour < 17
+               else "hour_rush_evening" if hour <= 19 else "hour_evening" if hour < 22 else "hour_night_late"] += 1
         obs, rew, term, trunc, info = env.step(a)
         assert not trunc and obs.dtype == np.float32 and rew == int(rew) and list(info) == list(INFO)
         ev["gridlock"] += bool(np.mean(env.traffic_congestion) > 0.8)
@@ -128,7 +136,7 @@ def run_env(seed, T, a_seed, i, policy, autoreset, ev, max_timesteps=None):
 
 
 def make(name, n_envs, T, seed0, a_seed, policy, autoreset=True, max_timesteps=None):
-    ev = dict.fromkeys(EVENTS, 0)
+    ev = dict.fromkeys(EVENTS + (NEW_EVENTS if name in NEW_RUNS else ()), 0)
     rows = [run_env(seed0 + i, T, a_seed, i, policy, autoreset, ev, max_timesteps) for i in range(n_envs)]
     env = rows[0][0]
     rows = [r[1] for r in rows]
@@ -159,6 +167,14 @@ RUNS = dict(emergency_hash=dict(n_envs=16, T=150, seed0=2944, a_seed=301, policy
             emergency_idle=dict(n_envs=16, T=200, seed0=2232, a_seed=303, policy="idle"),
             emergency_timeout=dict(n_envs=16, T=150, seed0=2636, a_seed=304, policy="dispatch", max_timesteps=90),
             emergency_overrun=dict(n_envs=8, T=300, seed0=2400, a_seed=305, policy="hash", autoreset=False))
+# recorded later than RUNS, for the branches of csrc/emergency_env.hpp that those leave unentered (tests/test_lane_env_branch_coverage.py)
+NEW_RUNS = dict(emergency_day=dict(n_envs=4, T=1330, seed0=3000, a_seed=306, policy="dispatch", autoreset=False))
+
+
+def check_new(name, ev):
+    if name == "emergency_day":
+        return min(ev[k] for k in NEW_EVENTS if k.startswith("hour_")) >= 4 * 10
+    return True
 
 
 def check(evs):
@@ -173,6 +189,13 @@ def check(evs):
 
 
 if __name__ == "__main__":
+    if "--new" in sys.argv[1:]:
+        made = {name: make(name, **kw) for name, kw in NEW_RUNS.items()}
+        for name, (_, ev) in made.items():
+            assert check_new(name, ev), (name, ev)
+        for name, (arrays, _) in made.items():
+            save(name, arrays)
+        sys.exit(0)
     made = {name: make(name, **kw) for name, kw in RUNS.items()}
     check({name: ev for name, (_, ev) in made.items()})                   # nothing is written unless the runs hold what they are for
     for name, (arrays, _) in made.items():

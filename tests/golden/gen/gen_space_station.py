@@ -17,11 +17,18 @@ The event counters are taken by watching the env from outside: its methods are w
 `obs_xor` is the per-step observation as uint32 bit patterns [env, element, step], each step XORed with the step before it;
 space_station_model.fixture_obs() undoes it.  `info` holds the nine info values in the reference's order, `system_failures` as the
 length of the list, and as a tenth column the 12-bit mask of the systems named in it.
+`station_poked` sets plain state attributes of the env object between steps, where the reference's own arithmetic keeps a state out
+of reach of any run a fixture can hold (water and food fall below 20 after some 8,000 steps, the oxygen tanks never rise above their
+initial 20, the pressure falls only by a micrometeorite of probability 0.00025 a step, the cascade of failed systems ends an unattended
+station long before the air does); the reference's code stays untouched.  Its `pokes` table holds (env, step, index into
+`poke_fields`, value): the field, named as csrc/space_station_env.hpp names it, is set to the value before the action of that step.
 Outputs: tests/golden/station_hash.npz, station_keep.npz, station_idle.npz, station_evacuate.npz, station_timeout.npz,
-station_overrun.npz.
+station_overrun.npz (RUNS) and station_poked.npz (NEW_RUNS; `python gen_space_station.py --new` writes it alone and leaves the others'
+bytes as they are).
 """
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -38,6 +45,9 @@ INFO = ("time_step", "day", "crew_alive", "system_failures", "emergency_count", 
 EVENTS = ("crew_dead", "cascade", "uninhabitable", "timeout", "carried_angle", "backup_used", "backup_gone", "no_spares", "thermal_drift",
           "micrometeorite", "system_failure", "medical", "solar_storm", "failure_critical", "failure_noncritical", "choice_rejected",
           "negative_health", "docking_after_reset", "both_flags", "mission_success", "power_failure_steps")
+# counted in the runs of NEW_RUNS only (the older files' `events` have the keys above)
+NEW_EVENTS = ("water_low", "food_low", "resources_bonus", "module_cold", "module_hot", "fatigued", "suffocated_alive", "air_thin", "air_alert",
+              "end_air", "end_pressure", "end_crew", "crew_lost_systems_fine", "oxygen_exactly_19", "water_short", "food_short", "waste_short")
 KINDS = ("micrometeorite", "system_failure", "medical", "solar_storm")
 OBS = 120
 
@@ -52,6 +62,69 @@ def action(policy, a_seed, i, t):
     if policy == "evacuate":
         return 38 if t == 3 else 39
     return common.hash_action(a_seed, i, t, 40)
+
+
+def set_field(env, name, value):
+    """a poke: the header's name of a plain state field -> the reference's attribute"""
+    m = re.fullmatch(r"(o2|co2|pres|temp|health|oxy|fatigue|eff)(\d+)", name)
+    if m:
+        kind, k = m.group(1), int(m.group(2))
+        if kind in ("o2", "co2", "pres", "temp"):
+            setattr(list(env.modules.values())[k], dict(o2="oxygen_percent", co2="co2_ppm", pres="pressure", temp="temperature")[kind], float(value))
+        elif kind == "eff":
+            list(env.systems.values())[k].efficiency = float(value)
+        else:
+            setattr(env.crew[k], dict(health="health", oxy="oxygen_level", fatigue="fatigue")[kind], float(value))
+    elif name in ("water", "food", "tanks", "waste"):
+        env.resources[dict(water="water", food="food", tanks="oxygen_tanks", waste="waste_capacity")[name]] = float(value)
+    else:
+        raise KeyError(name)
+
+
+O2_JUST_ABOVE_19 = 19.0 + 0.01                                            # minus the 0.01 one crew member breathes: 19.0 exactly (asserted)
+
+
+def plan_poked(i, t):
+    """-> the pokes [(field, value)] before step t of env i (every action is 39).  Step 1: the oxygen generator off and module 2 at
+    19.01 % oxygen, which one crew member's 0.01 makes 19.0 exactly (neither `< 19` nor `> 19`); env 3 loses crew member 0 there, with
+    the systems and the battery fine.  Steps 2 to 5: water at 15, food at 15, the tanks at 25, each alone.  Step 6: module 0 at 12
+    degrees, module 1 at 33.  Step 7: a fatigue of 85.  Step 8: crew member 1 at an oxygen level of 1 in a module at 18 %.  Step 9:
+    every module at 18.5 % (a mean at or below 19), step 10: at 17 % (the life-support alert).  Step 11: the ends: env 0 every module
+    at 14 % oxygen, env 1 every module at 75 kPa, env 2 every crew member at health 0.  Steps 12 to 15 (after the resets of envs 0 to
+    2): water at 5, food at 5, the waste capacity at 5, each alone: the terms of the shortage penalty (`< 10`, :702-705) that no
+    other run makes true (the tanks and the spare parts fall below 10 in the older files)."""
+    all_o2 = lambda v: [(f"o2{m}", v) for m in range(8)]
+    if t == 1:
+        return [("eff0", 20.0), ("o2" + "2", O2_JUST_ABOVE_19)] + ([("health0", 0.0)] if i == 3 else [])
+    if t == 2:
+        return [("eff0", 100.0), ("water", 15.0)]
+    if t == 3:
+        return [("water", 1000.0), ("food", 15.0)]
+    if t == 4:
+        return [("food", 500.0), ("tanks", 25.0)]
+    if t == 5:
+        return [("tanks", 20.0)]
+    if t == 6:
+        return [("temp0", 12.0), ("temp1", 33.0)]
+    if t == 7:
+        return [("fatigue2", 85.0)]
+    if t == 8:
+        return [("oxy1", 1.0), ("o2" + "1", 18.0)]
+    if t == 9:
+        return all_o2(18.5)
+    if t == 10:
+        return all_o2(17.0)
+    if t == 11:
+        return [all_o2(14.0), all_o2(21.0) + [(f"pres{m}", 75.0) for m in range(8)], all_o2(21.0) + [(f"health{c}", 0.0) for c in range(6)], all_o2(21.0)][i]
+    if t == 12:
+        return [("water", 5.0)]
+    if t == 13:
+        return [("water", 1000.0), ("food", 5.0)]
+    if t == 14:
+        return [("food", 500.0), ("waste", 5.0)]
+    if t == 15:
+        return [("waste", 100.0)]
+    return []
 
 
 def xor_time(obs):
@@ -113,10 +186,38 @@ def run_env(seed, T, a_seed, i, policy, autoreset, ev, max_steps=None):
     obs, info = env.reset(seed=seed)
     assert obs.shape == (OBS,) and obs.dtype == np.float32
     out = dict(obs0=obs, info0=info_row(env, info, names), A=np.zeros(T, np.int8), R=np.zeros(T, np.float64), TM=np.zeros(T, np.uint8),
-               TR=np.zeros(T, np.uint8), I=np.zeros((T, 10), np.float64), O=np.zeros((T, OBS), np.float32), resets=[])
+               TR=np.zeros(T, np.uint8), I=np.zeros((T, 10), np.float64), O=np.zeros((T, OBS), np.float32), resets=[], pokes=[])
     for t in range(T):
-        a = action(policy, a_seed, i, t)
+        a = action("idle" if policy == "poked" else policy, a_seed, i, t)
+        if policy == "poked":
+            for name, value in plan_poked(i, t):
+                set_field(env, name, value)
+                out["pokes"].append((i, t, name, value))
         obs, rew, term, trunc, info = env.step(a)
+        if "water_low" in ev:                                         # what the step saw, read off the state it left
+            res, mods, alive = env.resources, list(env.modules.values()), sum(1 for c in env.crew if c.health > 0)
+            avg_o2 = np.mean([m.oxygen_percent for m in mods])
+            avg_eff = np.mean([s.efficiency for s in env.systems.values()])
+            ev["water_low"] += int(not res["water"] > 20)
+            ev["food_low"] += int(res["water"] > 20 and not res["food"] > 20)
+            ev["water_short"] += int(res["water"] < 10)
+            ev["food_short"] += int(res["food"] < 10)
+            ev["waste_short"] += int(res["waste_capacity"] < 10)
+            ev["resources_bonus"] += int(res["water"] > 20 and res["food"] > 20 and res["oxygen_tanks"] > 20)
+            ev["module_cold"] += sum(1 for k in range(6) if mods[k].temperature < 15)
+            ev["module_hot"] += sum(1 for k in range(6) if mods[k].temperature > 30)
+            ev["fatigued"] += sum(1 for c in env.crew if c.fatigue > 80)
+            ev["suffocated_alive"] += sum(1 for c in env.crew if c.health > 0 and c.oxygen_level <= 0)
+            ev["air_thin"] += int(not 19 < avg_o2)
+            ev["air_alert"] += int(avg_o2 < 18)
+            ev["crew_lost_systems_fine"] += int(env.battery_level > 50 and avg_eff > 80 and alive < 6)
+            ev["oxygen_exactly_19"] += sum(1 for k in range(6) if mods[k].oxygen_percent == 19.0)
+            if term:
+                crit = sum(1 for s in env.systems.values() if s.is_critical and s.efficiency < 10)
+                dead = all(c.health <= 0 for c in env.crew)
+                ev["end_crew"] += int(dead)
+                ev["end_air"] += int(not dead and crit < 3 and avg_o2 < 15)
+                ev["end_pressure"] += int(not dead and crit < 3 and not avg_o2 < 15 and np.mean([m.pressure for m in mods]) < 80)
         assert obs.dtype == np.float32 and rew == int(rew) and (not trunc or term)
         ev["negative_health"] += int((obs[2:24:4] < 0).any())
         ev["power_failure_steps"] += int(env.emergency_alerts["power_failure"])
@@ -137,7 +238,7 @@ def run_env(seed, T, a_seed, i, policy, autoreset, ev, max_steps=None):
 
 
 def make(name, n_envs, T, seed0, a_seed, policy, autoreset=True, max_steps=None):
-    ev = dict.fromkeys(EVENTS, 0)
+    ev = dict.fromkeys(EVENTS + (NEW_EVENTS if name in NEW_RUNS else ()), 0)
     rows = [run_env(seed0 + i, T, a_seed, i, policy, autoreset, ev, max_steps) for i in range(n_envs)]
     env = rows[0][0]
     rows = [r[1] for r in rows]
@@ -154,6 +255,11 @@ def make(name, n_envs, T, seed0, a_seed, policy, autoreset=True, max_steps=None)
                   info_keys=np.array(json.dumps(INFO + ("system_failure_mask",))), reset_index=np.array(ridx, np.int32).reshape(-1, 2),
                   reset_obs=np.array([ob for r in rows for _, ob in r["resets"]], np.float32).reshape(-1, OBS),
                   spaces=np.array(json.dumps(sp)), events=np.array(json.dumps(ev)), versions=np.array(json.dumps(common.versions())))
+    if policy == "poked":
+        pokes = [p for r in rows for p in r["pokes"]]
+        names = sorted({p[2] for p in pokes})
+        arrays["poke_fields"] = np.array(json.dumps(names))
+        arrays["pokes"] = np.array([(i, t, names.index(name), value) for i, t, name, value in pokes], np.float64).reshape(-1, 4)
     return arrays, ev
 
 
@@ -171,6 +277,8 @@ RUNS = dict(station_hash=dict(n_envs=8, T=400, seed0=0, a_seed=401, policy="hash
             station_evacuate=dict(n_envs=8, T=80, seed0=400, a_seed=404, policy="evacuate"),
             station_timeout=dict(n_envs=8, T=70, seed0=500, a_seed=405, policy="keep", max_steps=20),
             station_overrun=dict(n_envs=8, T=400, seed0=600, a_seed=406, policy="hash", autoreset=False))
+# recorded later than RUNS, for the branches of csrc/space_station_env.hpp that those leave unentered (tests/test_lane_env_branch_coverage.py)
+NEW_RUNS = dict(station_poked=dict(n_envs=4, T=18, seed0=700, a_seed=407, policy="poked"))
 
 
 def check_one(name, ev):
@@ -183,6 +291,9 @@ def check_one(name, ev):
         return ev["cascade"] >= 16 and ev["thermal_drift"] >= 16
     if name == "station_evacuate":
         return ev["docking_after_reset"] >= 8
+    if name == "station_poked":
+        return (min(ev[k] for k in NEW_EVENTS) >= 1 and ev["end_air"] == ev["end_pressure"] == ev["end_crew"] == 1 and ev["oxygen_exactly_19"] == 4
+                and ev["uninhabitable"] == 2 and ev["crew_dead"] == 1 and ev["cascade"] == 0 and ev["water_short"] == ev["food_short"] == ev["waste_short"] == 4)
     if name == "station_timeout":
         return ev["timeout"] >= 8 and ev["both_flags"] == ev["timeout"] == ev["mission_success"]
     return True
@@ -198,7 +309,8 @@ if __name__ == "__main__":
                 print("found", name, seed0)
                 break
         sys.exit(0)
-    made = {name: make(name, **kw) for name, kw in RUNS.items()}
+    assert O2_JUST_ABOVE_19 - 1 * 0.01 == 19.0
+    made = {name: make(name, **kw) for name, kw in (NEW_RUNS if "--new" in sys.argv[1:] else RUNS).items()}
     for name, (_, ev) in made.items():                                    # nothing is written unless the runs hold what they are for
         assert check_one(name, ev), (name, ev)
     for name, (arrays, _) in made.items():

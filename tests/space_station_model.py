@@ -11,7 +11,9 @@ overwritten before the crew update of the next step) and is kept as written.
 tests/test_space_station_cpu.py pins the model to fixtures recorded from the unmodified reference; the GPU tests use it where the
 fixtures cannot reach.  Test infrastructure only: the product never imports it.
 """
+import json
 import math
+import re
 
 import numpy as np
 
@@ -315,6 +317,28 @@ class _Env:
         """the nine values in the reference's order (system_failures as its length), then the 12-bit mask of the failed systems"""
         return [self.t, (self.t * 5) // 1440, sum(1 for h in self.health if h > 0), self.failures, self.emergencies, float(self.success), self.ret,
                 self.battery, mean6(self.health), self.failure_mask]
+
+
+def poke(env, name, value):
+    """set the plain state field that csrc/space_station_env.hpp calls `name` (a fixture's `pokes` table;
+    tools/probes/space_station_host_check.cpp --layout lists the names): o2 / co2 / pres / temp of module m, health / oxy / fatigue of
+    crew member c, eff / maint of system s, a resource or the battery"""
+    m = re.fullmatch(r"(o2|co2|pres|temp|health|oxy|fatigue|eff|maint)(\d+)", name)
+    if m:
+        getattr(env, m.group(1))[int(m.group(2))] = float(value)
+    else:
+        assert name in ("water", "food", "tanks", "spare", "waste", "battery"), name
+        setattr(env, name, float(value))
+
+
+def fixture_pokes(z):
+    """{step: [(env, field name, value)]} of a fixture's `pokes` table (empty for a fixture without one)"""
+    out = {}
+    if "pokes" in z:
+        names = json.loads(str(z["poke_fields"]))
+        for i, t, k, value in z["pokes"]:
+            out.setdefault(int(t), []).append((int(i), names[int(k)], float(value)))
+    return out
 
 
 class SpaceStationModel:

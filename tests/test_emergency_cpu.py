@@ -15,7 +15,8 @@ import pytest
 import emergency_model as em
 from conftest import ROOT, golden
 
-FIXTURES = ["emergency_hash.npz", "emergency_dispatch.npz", "emergency_idle.npz", "emergency_timeout.npz", "emergency_overrun.npz"]
+OLD_FIXTURES = ["emergency_hash.npz", "emergency_dispatch.npz", "emergency_idle.npz", "emergency_timeout.npz", "emergency_overrun.npz"]
+FIXTURES = OLD_FIXTURES + ["emergency_day.npz"]
 ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
        "snapshot_set", "device_bytes", "last_error", "last_kernel"]
 
@@ -51,7 +52,7 @@ def test_model_reproduces_the_reference(name):
 
 
 def test_fixtures_cover_what_they_are_for():
-    h, d, i, to, o = (golden(f) for f in FIXTURES)
+    h, d, i, to, o = (golden(f) for f in OLD_FIXTURES)
     assert h["reward"].shape == d["reward"].shape == to["reward"].shape == (16, 150) and i["reward"].shape == (16, 200) and o["reward"].shape == (8, 300)
     assert h["actions"].min() == 0 and h["actions"].max() == 49 and (i["actions"] == 49).all()
     for z in (d, to):
@@ -72,7 +73,18 @@ def test_fixtures_cover_what_they_are_for():
     assert o["terminated"].any() and len(o["reset_index"]) == 0 and not o["terminated"][:, 0].any()   # stepped on past termination
     obs = em.fixture_obs(i)
     assert (obs[..., 272] == 1.0).any()                                                    # twenty active incidents in an observation
-    for z in (h, d, i, to, o):
+    # emergency_day: never reset, on past 22:00 on the env's clock: every arm of the hour-of-day chain of :787-792 for at least ten
+    # steps in every env (the hour of a step is that of the timestep before it, which the observation of the step before shows)
+    day = golden("emergency_day.npz")
+    dv = json.loads(str(day["events"]))
+    assert day["reward"].shape == (4, 1330) and not int(day["autoreset"]) and len(day["reset_index"]) == 0 and int(day["max_timesteps"]) == 1440
+    assert (day["actions"][:, 3::4] >= 20).all() and (day["actions"][:, 0::4] < 20).all()
+    hours = (np.arange(1330) // 60) % 24
+    want = dict(hour_night_early=hours <= 5, hour_before_rush=hours == 6, hour_rush_morning=(hours >= 7) & (hours <= 9), hour_midday=(hours >= 10) & (hours <= 16),
+                hour_rush_evening=(hours >= 17) & (hours <= 19), hour_evening=(hours >= 20) & (hours <= 21), hour_night_late=hours >= 22)
+    assert all(dv[k] == 4 * int(v.sum()) >= 40 for k, v in want.items()), dv
+    assert np.abs(day["reward"]).max() < 2 ** 24 and np.array_equal(day["reward"], np.round(day["reward"]))   # integers a float32 holds exactly
+    for z in (h, d, i, to, o, day):
         assert json.loads(str(z["versions"]))["python"].startswith("3.10")                # sum() of floats without compensation
     for f in FIXTURES:
         assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) < 1 << 20

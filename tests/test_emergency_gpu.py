@@ -149,6 +149,27 @@ def test_overrun_fixture_steps_on_past_termination(cge):
     env.close()
 
 
+def test_day_fixture_runs_through_every_hour(cge):
+    """emergency_day.npz: Disabled, never reset, on to 22:10 on the env's clock, so that the traffic's hour-of-day chain (:787-792) takes
+    every arm: the morning and the evening rush, the hours between and after them, the night on both sides of midnight.  Chunks of
+    fused steps, every step's row, reward and flag compared with the recorded reference."""
+    z = golden("emergency_day.npz")
+    n, T = z["reward"].shape
+    assert (n, T) == (4, 1330) and not int(z["autoreset"])
+    ref = em.fixture_obs(z)
+    env = cge.EmergencyVectorEnv(n, autoreset_mode="Disabled")
+    same(env.reset(seed=int(z["seed0"]))[0], z["obs0"], "reset")
+    acts = dev(z["actions"].T)
+    for t in range(0, T, 70):
+        k = min(70, T - t)
+        traj, rt, tt, rs, dc = env.rollout(k, actions=acts[t:t + k], trajectory=True, per_step=True)
+        same(traj, ref[:, t:t + k].transpose(1, 0, 2), t); same(rt, f32(z["reward"][:, t:t + k].T), t)
+        assert np.array_equal(tt.cpu().numpy(), z["terminated"][:, t:t + k].T.astype(bool)), t
+        same(info6(env), z["info"][:, t + k - 1], (t, "info"))
+    assert (env.info("timestep") == T).all()
+    env.close()
+
+
 def test_hash_fixture_next_step_against_the_model(cge):
     z = golden("emergency_hash.npz")
     n, T = z["reward"].shape

@@ -18,7 +18,8 @@ import pytest
 import space_station_model as sm
 from conftest import ROOT, golden
 
-FIXTURES = ["station_hash.npz", "station_keep.npz", "station_idle.npz", "station_evacuate.npz", "station_timeout.npz", "station_overrun.npz"]
+OLD_FIXTURES = ["station_hash.npz", "station_keep.npz", "station_idle.npz", "station_evacuate.npz", "station_timeout.npz", "station_overrun.npz"]
+FIXTURES = OLD_FIXTURES + ["station_poked.npz"]
 ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
        "snapshot_set", "device_bytes", "last_error", "last_kernel"]
 HOST_CHECK = os.path.join(ROOT, "tools", "probes", "space_station_host_check.py")
@@ -41,7 +42,11 @@ def test_model_reproduces_the_reference(name):
     assert np.array_equal(bits(m.reset()), bits(z["obs0"])) and np.array_equal(bits(m.info()), bits(z["info0"]))
     where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
     seen = 0
+    pokes = sm.fixture_pokes(z)
+    assert bool(pokes) == (name == "station_poked.npz")
     for t in range(T):
+        for i, field, value in pokes.get(t, ()):                                           # what the generator set on the reference's env object
+            sm.poke(m.envs[i], field, value)
         obs, reward, terminated, truncated, final, info = m.step(z["actions"][:, t])
         assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
         assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)) and np.array_equal(truncated, z["truncated"][:, t].astype(bool)), t
@@ -56,8 +61,8 @@ def test_model_reproduces_the_reference(name):
 
 
 def test_fixtures_cover_what_they_are_for():
-    h, k, i, e, to, o = (golden(f) for f in FIXTURES)
-    ev = {f: json.loads(str(z["events"])) for f, z in zip(FIXTURES, (h, k, i, e, to, o))}
+    h, k, i, e, to, o = (golden(f) for f in OLD_FIXTURES)
+    ev = {f: json.loads(str(z["events"])) for f, z in zip(OLD_FIXTURES, (h, k, i, e, to, o))}
     assert h["reward"].shape == (8, 400) and k["reward"].shape == (8, 600) and i["reward"].shape == (16, 100) and e["reward"].shape == (8, 80)
     assert to["reward"].shape == (8, 70) and o["reward"].shape == (8, 400)
     assert h["actions"].min() == 0 and h["actions"].max() == 39 and (i["actions"] == 39).all()
@@ -97,7 +102,27 @@ def test_fixtures_cover_what_they_are_for():
     assert not any(z["truncated"].any() for z in (h, k, i, e, o))
     # station_overrun: stepped on past termination
     assert o["terminated"].any() and len(o["reset_index"]) == 0 and not o["terminated"][:, 0].any() and (o["terminated"].sum(1) >= 50).sum() >= 2   # fifty steps and more past the end
-    for z in (h, k, i, e, to, o):
+    # station_poked: what no run a fixture can hold reaches, set on the reference's env object between steps: water, food and the
+    # tanks across 20, a cold and a hot module, a fatigue above 80, a crew member out of oxygen but alive, the mean oxygen at or below
+    # 19 and below 18, a module at 19.0 % exactly, a crew member lost with the systems fine, and the three ends that the cascade of
+    # failed systems otherwise comes before: the air, the pressure, the crew
+    pk = golden("station_poked.npz")
+    pv = json.loads(str(pk["events"]))
+    assert pk["reward"].shape == (4, 18) and pk["pokes"].shape[1] == 4 and (pk["actions"] == 39).all() and int(pk["autoreset"]) == 1
+    assert min(pv[key] for key in ("water_low", "food_low", "resources_bonus", "module_cold", "module_hot", "fatigued", "suffocated_alive", "air_thin",
+                                   "air_alert", "crew_lost_systems_fine")) >= 1 and pv["oxygen_exactly_19"] == 4
+    assert pv["end_air"] == pv["end_pressure"] == pv["end_crew"] == 1 and pv["uninhabitable"] == 2 and pv["crew_dead"] == 1 and pv["cascade"] == 0
+    assert pk["terminated"][:3, 11].all() and pk["terminated"].sum() == 3 == len(pk["reset_index"]) and not pk["truncated"].any()
+    # and the three terms of the shortage penalty (`< 10`) that no other file makes true: water, food and the waste capacity at 5, each
+    # alone for one step in every env (the tanks and the spare parts fall below 10 in the older files; the line has no branch, so
+    # tests/test_lane_env_branch_coverage.py cannot see it)
+    assert pv["water_short"] == pv["food_short"] == pv["waste_short"] == 4
+    late = sm.fixture_pokes(pk)
+    assert [sorted((i, f, v) for i, f, v in late[t] if v == 5.0) for t in (12, 13, 14)] == [[(i, f, 5.0) for i in range(4)] for f in ("water", "food", "waste")]
+    names = json.loads(str(pk["poke_fields"]))
+    assert {"water", "food", "tanks", "waste", "eff0", "fatigue2", "oxy1", "health0", "temp0", "temp1", "pres7", "o20"} <= set(names)
+    assert (pk["pokes"][:, 0] < 4).all() and (pk["pokes"][:, 1] < 18).all() and (pk["pokes"][:, 2] < len(names)).all()
+    for z in (h, k, i, e, to, o, pk):
         assert json.loads(str(z["versions"]))["python"].startswith("3.10")                # sum() of floats without compensation
     for f in FIXTURES:
         assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) < 1 << 20
@@ -173,6 +198,64 @@ def test_host_reset_state_equals_the_model():
         e = sm._Env(1000 + j)
         e.reset()
         assert np.array_equal(bits(got[j]), bits(np.array([e.o2, e.co2, e.pres, e.temp]))), j
+
+
+def _host_records(n, k, seed0=3000):
+    """the host build's float64 records of n envs after k hashed steps, and the model stepped alike"""
+    acts = sm.hash_actions(11, k, n, envs=np.arange(n))
+    out = subprocess.run([sys.executable, HOST_CHECK, "--record", str(seed0), str(n), str(k)], input=np.ascontiguousarray(acts, np.int32).tobytes(), capture_output=True)
+    assert out.returncode == 0, out.stderr.decode()
+    m = sm.SpaceStationModel(seed0 + np.arange(n), sm.SAME_STEP)
+    m.reset()
+    for t in range(k):
+        m.step(acts[t])
+    return np.frombuffer(out.stdout, np.float64).reshape(n, 89), m
+
+
+def _model_field(e, name):
+    """the model's value of the field csrc/space_station_env.hpp calls `name` (the reading side of space_station_model.poke)"""
+    m = re.fullmatch(r"(o2|co2|pres|temp|health|oxy|fatigue|eff|maint)(\d+)", name)
+    return getattr(e, m.group(1))[int(m.group(2))] if m else getattr(e, name)
+
+
+def test_layout_names_the_fields_the_model_holds():
+    """every name of the host build's `--layout` against the model, independently of the layout itself: after 40 hashed steps the
+    float64 at the word offset listed for a name, in the record the host packer wrote, is the value the model holds under that name,
+    bit for bit, for all 16 envs; the 74 values of an env are pairwise different where the fields are, so no two names can be swapped"""
+    import _lane_env_pokes as lp
+    rec, m = _host_records(16, 40)
+    table = lp.layout("space_station")
+    assert len(table) == 4 * 8 + 3 * 6 + 2 * 12 + 6 and len({w for w, _ in table.values()}) == len(table)
+    assert all(fmt == "f64" and 0 <= w < 178 and w % 2 == 0 for w, fmt in table.values())
+    for j, e in enumerate(m.envs):
+        want = {name: float(_model_field(e, name)) for name in table}
+        for name, (word, _) in table.items():
+            assert bits(rec[j, word // 2:word // 2 + 1])[0] == bits(np.array([want[name]]))[0], (j, name)
+    distinct = [len({float(_model_field(e, name)) for name in table}) for e in m.envs]
+    assert max(distinct) >= 60, distinct                                 # a few resources and clipped values coincide, no more
+
+
+def test_poke_helper_changes_exactly_the_named_field():
+    """tests/_lane_env_pokes.py, which the GPU test of station_poked.npz uses: on a snapshot-shaped blob (32-byte header, 32-bit
+    columns [word][env]) made from the host packer's records, a poke changes the named field of the named env and nothing else"""
+    import _lane_env_pokes as lp
+    n = 5
+    rec, _ = _host_records(n, 3)
+    table = lp.layout("space_station")
+    words = np.zeros((188, n), np.uint32)
+    words[:178] = rec.view(np.uint32).reshape(n, 178).T
+    blob = np.concatenate([np.zeros(32, np.uint8), words.reshape(-1).view(np.uint8)])
+    for name, env, value in (("o22", 0, 19.01), ("pres7", 3, 75.0), ("temp1", 4, 33.0), ("co25", 2, 1200.0), ("health0", 1, 12.5), ("water", 2, 5.0),
+                             ("eff0", 0, 20.0), ("fatigue2", 4, 85.0), ("tanks", 1, 25.0), ("waste", 3, 5.0), ("food", 0, 5.0), ("oxy1", 2, 1.0)):
+        poked = blob.copy()
+        lp.poke_blob(poked, n, table, env, name, value)
+        assert np.array_equal(poked[:32], blob[:32])
+        got = poked[32:].view(np.uint32).reshape(188, n)
+        assert np.array_equal(got[178:], words[178:])
+        after = np.ascontiguousarray(got[:178].T).view(np.float64).reshape(n, 89)
+        assert np.argwhere(bits(after) != bits(rec)).tolist() == [[env, table[name][0] // 2]] and after[env, table[name][0] // 2] == value, name
+    with pytest.raises(KeyError):
+        lp.poke_blob(blob.copy(), n, table, 0, "no_such_field", 1.0)
 
 
 def test_abi_is_declared_exported_and_bound():

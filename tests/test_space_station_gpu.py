@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import _lane_env_pokes as lane_pokes
 import space_station_model as sm
 from conftest import golden
 
@@ -71,8 +72,9 @@ def test_surface(cge):
     env.close()
 
 
-@pytest.mark.parametrize("name", ["station_hash.npz", "station_keep.npz", "station_idle.npz", "station_evacuate.npz", "station_timeout.npz"])
-def test_fixtures_same_step(cge, name):
+def replay_same_step(cge, name, pokes=None):
+    """the fixture on the device, every step against the recorded reference rows bit for bit; pokes = {step: [(env, field, value)]} are
+    written into the record before that step.  Returns the resets seen and recorded."""
     z = golden(name)
     n, T = z["reward"].shape
     ref = sm.fixture_obs(z)
@@ -84,6 +86,8 @@ def test_fixtures_same_step(cge, name):
     acts = dev(z["actions"].T)
     seen = 0
     for t in range(T):
+        if pokes and t in pokes:
+            lane_pokes.apply(env, n, "space_station", pokes[t])
         obs, rew, term, trunc, infos = env.step(acts[t])
         tm = term.cpu().numpy()
         same(rew, f32(z["reward"][:, t]), t)
@@ -97,8 +101,25 @@ def test_fixtures_same_step(cge, name):
         for i in np.flatnonzero(tm):                                      # and `obs` is what reset() then returned on the same stream
             seen += 1
             same(o[i], z["reset_obs"][where[(int(i), t)]], (t, i))
-    assert seen == len(where) > 0 and env.invalid_action_count() == 0
+    assert env.invalid_action_count() == 0
     env.close()
+    return seen, len(where)
+
+
+@pytest.mark.parametrize("name", ["station_hash.npz", "station_keep.npz", "station_idle.npz", "station_evacuate.npz", "station_timeout.npz"])
+def test_fixtures_same_step(cge, name):
+    seen, recorded = replay_same_step(cge, name)
+    assert seen == recorded > 0
+
+
+def test_poked_fixture_same_step(cge):
+    """station_poked.npz: the reference with resources, module air and temperature, crew values and a system's efficiency set from outside
+    between steps (states no run a fixture can hold reaches, the three ends behind the cascade of failed systems among them).  The
+    device gets the same pokes through snapshot() and restore(), at the word offsets the host build of csrc/space_station_env.hpp
+    reports, and is then compared like any other fixture, the three ends and their resets included."""
+    pokes = sm.fixture_pokes(golden("station_poked.npz"))
+    assert sorted(pokes) == list(range(1, 16))
+    assert replay_same_step(cge, "station_poked.npz", pokes) == (3, 3)
 
 
 def test_idle_fixture_disabled_with_masked_resets(cge):

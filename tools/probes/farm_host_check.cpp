@@ -1,8 +1,10 @@
 // Replays a farm fixture through csrc/farm_env.hpp on the CPU (the code the kernels run, compiled for the host) and compares every
 // step with what the reference recorded, bit for bit.  Driven by tools/probes/farm_host_check.py, which writes the input file:
-//   int32 n, T, autoreset, nresets, max_years; float reset_obs[nresets][134]; then per env: int32 seed, int32 actions[T],
+//   int32 n, T, autoreset, nresets, max_years, npokes; float reset_obs[nresets][134]; npokes x {int32 env, int32 step, char name[24],
+//   double value}: the named field of that env is set before that step; then per env: int32 seed, int32 actions[T],
 //   int32 reset_at[T] (row of reset_obs or -1), float obs0[134], double info0[27], float obs[T][134], double reward[T],
 //   uint8 terminated[T], double info[T][27].
+// `--layout`: prints `name word-offset f64|u32` for every field a poke can name, the offsets found through the record's own packer.
 // `--mean`: reads float64 vectors of 4 from stdin and writes mean4() of each to stdout (the order of NumPy's np.mean).
 // `--stage-days`: writes the 5 x 8 int32 entries of stage_days() to stdout.
 // `--randint S N`: writes N uint32 draws of randint25() after np.random.seed(S).  `--randbelow S n k N`: writes N uint32 draws of
@@ -78,12 +80,65 @@ static void repack(Env &e) {
     e = f;
 }
 
+// every field a poke can name, as the header names it: f(name, the double or nullptr, the whole-word integer or nullptr)
+template <class F>
+static void each_named(Env &e, F f) {
+    static const char *FD[] = {"health", "yp", "moisture", "ph", "n", "p", "k", "compaction", "om", "pest", "disease"};
+    char name[24];
+    for (int k = 0; k < NF; ++k) {
+        double *d[] = {&e.f[k].health, &e.f[k].yp, &e.f[k].moisture, &e.f[k].ph, &e.f[k].n, &e.f[k].p, &e.f[k].k, &e.f[k].compaction, &e.f[k].om, &e.f[k].pest, &e.f[k].disease};
+        for (int j = 0; j < FIELD_DOUBLES; ++j) { snprintf(name, sizeof name, "f%d.%s", k, FD[j]); f(name, d[j], (uint32_t *)nullptr); }
+    }
+    for (int q = 0; q < NE; ++q) {
+        snprintf(name, sizeof name, "fuel%d", q); f(name, &e.fuel[q], (uint32_t *)nullptr);
+        snprintf(name, sizeof name, "maint%d", q); f(name, &e.maint[q], (uint32_t *)nullptr);
+    }
+    const char *WD[] = {"temp", "hum", "rain", "wind", "frost", "reservoir", "quality", "cash", "bio", "trend", "climate"};
+    double *wd[] = {&e.temp, &e.hum, &e.rain, &e.wind, &e.frost, &e.reservoir, &e.quality, &e.cash, &e.bio, &e.trend, &e.climate};
+    for (int j = 0; j < 11; ++j) f(WD[j], wd[j], (uint32_t *)nullptr);
+    f("day", (double *)nullptr, &e.day); f("drought", (double *)nullptr, &e.drought); f("rain_days", (double *)nullptr, &e.rain_days);
+}
+
+static bool poke(Env &e, const char *name, double value) {
+    bool found = false;
+    each_named(e, [&](const char *nm, double *d, uint32_t *u) {
+        if (strcmp(nm, name)) return;
+        found = true;
+        if (d) *d = value; else *u = (uint32_t)value;
+    });
+    return found;
+}
+
+// the word of the record that holds each named field: a double by its address in each_double(), an integer by a marker through pack_ints()
+static int layout() {
+    Env e{};
+    int bad = 0;
+    each_named(e, [&](const char *nm, double *d, uint32_t *u) {
+        int at = -1;
+        if (d) {
+            Env::each_double(e, [&](int w, double &v) { if (&v == d) at = w; });
+        } else {
+            const uint32_t keep = *u;
+            *u = 0x5a5a5a5au;
+            e.pack_ints([&](int k, uint32_t v) { if (v == 0x5a5a5a5au) at = W_INT + k; });
+            *u = keep;
+        }
+        if (at < 0 || at >= REC_WORDS) { ++bad; return; }
+        printf("%s %d %s\n", nm, at, d ? "f64" : "u32");
+    });
+    return bad ? 1 : 0;
+}
+
+struct Poke { int32_t env, step; char name[24]; double value; };
+static_assert(sizeof(Poke) == 40, "as farm_host_check.py writes it");
+
 static void info_row(const Env &e, double *gi) {
     for (int k = 0; k < NINFO; ++k) gi[k] = info_value(e, k);
 }
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
+    if (!strcmp(argv[1], "--layout")) return layout();
     if (!strcmp(argv[1], "--mean")) {
         double v[4];
         while (fread(v, 8, 4, stdin) == 4) {
@@ -143,12 +198,14 @@ int main(int argc, char **argv) {
     }
     FILE *f = fopen(argv[1], "rb");
     if (!f) return 2;
-    int32_t hd[5];
-    if (fread(hd, 4, 5, f) != 5) return 2;
+    int32_t hd[6];
+    if (fread(hd, 4, 6, f) != 6) return 2;
     const int n = hd[0], T = hd[1], autoreset = hd[2], nres = hd[3];
     const uint32_t max_years = (uint32_t)hd[4];
     std::vector<float> robs((size_t)nres * LIVE);
     if (fread(robs.data(), 4, robs.size(), f) != robs.size()) return 2;
+    std::vector<Poke> pokes((size_t)hd[5]);
+    if (fread(pokes.data(), sizeof(Poke), pokes.size(), f) != pokes.size()) return 2;
     long bad = 0;
     for (int i = 0; i < n; ++i) {
         int32_t seed;
@@ -171,6 +228,10 @@ int main(int argc, char **argv) {
         info_row(e, gi);
         if ((memcmp(got, obs0.data(), sizeof got) || memcmp(gi, info0.data(), sizeof gi)) && bad++ < 5) printf("env %d: reset observation or info differs\n", i);
         for (int t = 0; t < T; ++t) {
+            for (Poke &p : pokes) {
+                p.name[sizeof p.name - 1] = 0;
+                if (p.env == i && p.step == t && !poke(e, p.name, p.value)) { printf("no field %s\n", p.name); return 2; }
+            }
             repack(e);
             bool term;
             const double rew = env_step(e, rng, py, a[t], a[t] >= 0 && a[t] < ACTIONS, max_years, term);

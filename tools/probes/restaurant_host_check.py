@@ -26,27 +26,42 @@ def host_compiler():
     raise RuntimeError("no host C++ compiler found (g++, c++, clang++, ROCm's clang++)")
 
 
+OPT = ["-O1"]
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+
+def build(outdir, flags=OPT, compiler=None):
+    """the host program, built into outdir with the given compiler flags; returns its path"""
+    exe = os.path.join(outdir, "check")
+    subprocess.run([compiler or host_compiler(), *flags, "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tools", "probes", "restaurant_host_check.cpp"), "-o", exe],
+                   check=True)
+    return exe
+
+
+def write_fixture(name, outdir):
+    """the fixture as the binary file that the host program reads; returns its path"""
+    with np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")) as z:
+        z = {k: z[k] for k in z.files}
+    n, T = z["reward"].shape
+    path = os.path.join(outdir, name + ".bin")
+    with open(path, "wb") as f:
+        f.write(np.array([n, T, int(z["max_episode_steps"])], np.int32).tobytes())
+        for i in range(n):
+            rng = random.Random(int(z["seed0"]) + i)
+            f.write(z["actions"][i].astype(np.int32).tobytes())
+            f.write(np.array([rng.random() for _ in range(T)], np.float64).tobytes())
+            f.write(z["reward"][i].tobytes())
+            f.write(z["total_reward"][i].tobytes())
+            f.write(z["info"][i].astype(np.int32).tobytes())
+            f.write(np.concatenate([z["obs_" + k][i].reshape(T, -1) for k in KEYS], 1).astype(np.int32).tobytes())
+    return path
+
+
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "check")
-        flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if "--sanitize" in sys.argv else []
-        subprocess.run([host_compiler(), "-O1", "-std=c++17", "-ffp-contract=off", *flags, os.path.join(ROOT, "tools", "probes", "restaurant_host_check.cpp"), "-o", exe], check=True)
+        exe = build(tmp, OPT + (SANITIZE if "--sanitize" in sys.argv else []))
         for name in FIXTURES:
-            with np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")) as z:
-                z = {k: z[k] for k in z.files}
-            n, T = z["reward"].shape
-            path = os.path.join(tmp, name + ".bin")
-            with open(path, "wb") as f:
-                f.write(np.array([n, T, int(z["max_episode_steps"])], np.int32).tobytes())
-                for i in range(n):
-                    rng = random.Random(int(z["seed0"]) + i)
-                    f.write(z["actions"][i].astype(np.int32).tobytes())
-                    f.write(np.array([rng.random() for _ in range(T)], np.float64).tobytes())
-                    f.write(z["reward"][i].tobytes())
-                    f.write(z["total_reward"][i].tobytes())
-                    f.write(z["info"][i].astype(np.int32).tobytes())
-                    f.write(np.concatenate([z["obs_" + k][i].reshape(T, -1) for k in KEYS], 1).astype(np.int32).tobytes())
-            subprocess.run([exe, path], check=True)
+            subprocess.run([exe, write_fixture(name, tmp)], check=True)
 
 
 if __name__ == "__main__":

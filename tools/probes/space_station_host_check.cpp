@@ -1,13 +1,18 @@
 // Replays a space-station fixture through csrc/space_station_env.hpp on the CPU (the code the kernels run, compiled for the host) and
 // compares every step with what the reference recorded, bit for bit.  Driven by tools/probes/space_station_host_check.py, which writes
 // the input file:
-//   int32 n, T, autoreset, nresets, max_steps; float reset_obs[nresets][120]; then per env: int32 seed, int32 actions[T],
+//   int32 n, T, autoreset, nresets, max_steps, npokes; float reset_obs[nresets][120]; npokes x {int32 env, int32 step, char name[24],
+//   double value}: the named field of that env is set before that step; then per env: int32 seed, int32 actions[T],
 //   int32 reset_at[T] (row of reset_obs or -1), float obs0[120], double info0[10], float obs[T][120], double reward[T],
 //   uint8 terminated[T], uint8 truncated[T], double info[T][10].
 // `--mean N`: reads float64 vectors of N (6, 8 or 12) from stdin and writes mean6() / mean8() / mean12() of each to stdout (the orders
 // of NumPy's np.mean).  `--tables`: writes the 3 x 18 float64 entries of cos_phase(), solar_eff() and radiation_of() to stdout.
 // `--reset S0 N`: writes the 32 float64 module values after np.random.seed(s); reset() for s = S0 .. S0 + N - 1 to stdout, in record
 // order (o2[8], co2[8], pressure[8], temperature[8]).
+// `--record S0 N K`: reads int32 actions [K][N] from stdin, runs env i = 0 .. N - 1 seeded S0 + i through reset and K steps with an
+// autoreset in the same step, and writes the 89 float64 slots of each record below W_SCAL in column order (the six slots of the
+// last_maintenance integers as zeros).
+// `--layout`: prints `name word-offset f64|u32` for every field a poke can name, the offsets found through the record's own packer.
 // The generator is MT19937 seeded as NumPy's legacy np.random.seed(int) does (init_genrand).
 #include <cstdio>
 #include <cstdlib>
@@ -63,12 +68,79 @@ static void repack(Env &e) {
     e = f;
 }
 
+// every field a poke can name, as the header names it: f(name, the double)
+template <class F>
+static void each_named(Env &e, F f) {
+    char name[24];
+    for (int m = 0; m < NM; ++m) {
+        snprintf(name, sizeof name, "o2%d", m); f(name, &e.o2[m]);
+        snprintf(name, sizeof name, "co2%d", m); f(name, &e.co2[m]);
+        snprintf(name, sizeof name, "pres%d", m); f(name, &e.pres[m]);
+        snprintf(name, sizeof name, "temp%d", m); f(name, &e.temp[m]);
+    }
+    for (int c = 0; c < NC; ++c) {
+        snprintf(name, sizeof name, "health%d", c); f(name, &e.health[c]);
+        snprintf(name, sizeof name, "oxy%d", c); f(name, &e.oxy[c]);
+        snprintf(name, sizeof name, "fatigue%d", c); f(name, &e.fatigue[c]);
+    }
+    for (int s = 0; s < NS; ++s) {
+        snprintf(name, sizeof name, "eff%d", s); f(name, &e.eff[s]);
+        snprintf(name, sizeof name, "maint%d", s); f(name, &e.maint[s]);
+    }
+    f("water", &e.water); f("food", &e.food); f("tanks", &e.tanks); f("spare", &e.spare); f("waste", &e.waste); f("battery", &e.battery);
+}
+
+static bool poke(Env &e, const char *name, double value) {
+    bool found = false;
+    each_named(e, [&](const char *nm, double *d) { if (!strcmp(nm, name)) { found = true; *d = value; } });
+    return found;
+}
+
+// the word of the record that holds each named field: by its address in each_double()
+static int layout() {
+    Env e{};
+    int bad = 0;
+    each_named(e, [&](const char *nm, double *d) {
+        int at = -1;
+        Env::each_double(e, [&](int w, double &v) { if (&v == d) at = w; });
+        if (at < 0 || at + 1 >= REC_WORDS) { ++bad; return; }
+        printf("%s %d f64\n", nm, at);
+    });
+    return bad ? 1 : 0;
+}
+
+struct Poke { int32_t env, step; char name[24]; double value; };
+static_assert(sizeof(Poke) == 40, "as space_station_host_check.py writes it");
+
 static void info10(const Env &e, double *gi) {
     for (int k = 0; k < 10; ++k) gi[k] = info_value(e, k);
 }
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
+    if (!strcmp(argv[1], "--layout")) return layout();
+    if (!strcmp(argv[1], "--record") && argc > 4) {
+        const long s0 = atol(argv[2]), n = atol(argv[3]), K = atol(argv[4]);
+        std::vector<int32_t> a((size_t)n * K);
+        if (fread(a.data(), 4, a.size(), stdin) != a.size()) return 2;
+        for (long i = 0; i < n; ++i) {
+            Mt rng;
+            rng.seed((uint32_t)(s0 + i));
+            Env e{};
+            construct(e);
+            reset_episode(e, rng);
+            for (long t = 0; t < K; ++t) {
+                bool term, trunc;
+                const int32_t act = a[(size_t)t * n + i];
+                env_step(e, rng, act, act >= 0 && act < ACTIONS, 8640u, term, trunc);
+                if (term) reset_episode(e, rng);
+            }
+            double rec[W_SCAL / 2] = {};
+            Env::each_double(e, [&](int w, const double &v) { rec[w / 2] = v; });
+            fwrite(rec, 8, W_SCAL / 2, stdout);
+        }
+        return 0;
+    }
     if (!strcmp(argv[1], "--mean") && argc > 2) {
         const int n = atoi(argv[2]);
         double v[NS];
@@ -104,12 +176,14 @@ int main(int argc, char **argv) {
     }
     FILE *f = fopen(argv[1], "rb");
     if (!f) return 2;
-    int32_t hd[5];
-    if (fread(hd, 4, 5, f) != 5) return 2;
+    int32_t hd[6];
+    if (fread(hd, 4, 6, f) != 6) return 2;
     const int n = hd[0], T = hd[1], autoreset = hd[2], nres = hd[3];
     const uint32_t max_t = (uint32_t)hd[4];
     std::vector<float> robs((size_t)nres * OBS);
     if (fread(robs.data(), 4, robs.size(), f) != robs.size()) return 2;
+    std::vector<Poke> pokes((size_t)hd[5]);
+    if (fread(pokes.data(), sizeof(Poke), pokes.size(), f) != pokes.size()) return 2;
     long bad = 0;
     for (int i = 0; i < n; ++i) {
         int32_t seed;
@@ -132,6 +206,10 @@ int main(int argc, char **argv) {
         info10(e, gi);
         if ((memcmp(got, obs0.data(), sizeof got) || memcmp(gi, info0.data(), sizeof gi)) && bad++ < 5) printf("env %d: reset observation or info differs\n", i);
         for (int t = 0; t < T; ++t) {
+            for (Poke &p : pokes) {
+                p.name[sizeof p.name - 1] = 0;
+                if (p.env == i && p.step == t && !poke(e, p.name, p.value)) { printf("no field %s\n", p.name); return 2; }
+            }
             repack(e);
             bool term, trunc;
             const double rew = env_step(e, rng, a[t], a[t] >= 0 && a[t] < ACTIONS, max_t, term, trunc);
