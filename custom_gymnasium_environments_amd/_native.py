@@ -115,6 +115,7 @@ _SHARED = {
 # what only some types have, by group; a group may replace a shared prototype (climate's two action pointers)
 _EXTRAS = {
     "final_obs": {"rollout_final_obs": (C.c_int, [_vp, _vp, _vp, _i64, _vp]), "final_obs_segment": (_i64, [_vp])},
+    "final_obs_rows": {},    # the same two under cge_rows_<env>_* (_env_signatures): beside a surface cge_<env>_* that stays as it is
     "state": {"state_bytes": (_sz, [_vp]), "get_state": _host_buf, "set_state": _host_buf},
     "snapshot": {"snapshot_bytes": (_sz, [_vp]), "snapshot_get": _host_buf, "snapshot_set": _host_buf},
     "done_mask": {"done_mask": (C.c_int, [_vp, _vp])},
@@ -140,9 +141,9 @@ _ENV_TYPES = {
     "world_builder": (WorldBuilderConfig, "info_indexed error_count state"),
     "restaurant": (RestaurantConfig, "info error_count snapshot"),
     "airline": (AirlineConfig, "info error_count snapshot"),
-    "emergency": (EmergencyConfig, "info error_count snapshot"),
-    "space_station": (SpaceStationConfig, "info error_count snapshot"),
-    "farm": (FarmConfig, "info error_count snapshot"),
+    "emergency": (EmergencyConfig, "final_obs_rows info error_count snapshot"),
+    "space_station": (SpaceStationConfig, "final_obs_rows info error_count snapshot"),
+    "farm": (FarmConfig, "final_obs_rows info error_count snapshot"),
 }
 _HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
 
@@ -153,7 +154,10 @@ def _env_signatures(env, config, extras):
         sig["default_config"] = (None, [C.POINTER(config)])
     for group in extras.split():
         sig.update(_EXTRAS[group])
-    return {f"cge_{env}_{name}": proto for name, proto in sig.items()}
+    out = {f"cge_{env}_{name}": proto for name, proto in sig.items()}
+    if "final_obs_rows" in extras.split():
+        out.update({f"cge_rows_{env}_{name}": proto for name, proto in _EXTRAS["final_obs"].items()})
+    return out
 
 
 SIGNATURES = {

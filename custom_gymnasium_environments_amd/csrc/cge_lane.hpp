@@ -1,4 +1,4 @@
-// cge_lane.hpp — what the lane-per-env types (bus, world builder, restaurant, airline, emergency, space station) share that is not dynamics.
+// cge_lane.hpp — what the lane-per-env types (bus, world builder, restaurant, airline, emergency, space station, farm) share that is not dynamics.
 //
 // Such a type steps one env per lane with the record in registers for the whole launch, and has step_kernel<MODE...>,
 // rollout_kernel<MODE..., ACTIONS> and reset_kernel(p, init, rewind), an error counter and a key-major observation slab.  Here are
@@ -11,7 +11,8 @@
 //   device  struct Params : LaneParams<Obs> with its own fields and `static constexpr bool terminates` (the flag it raises:
 //           terminated, or truncated), its run() loop calling the lane_* helpers below, and the three __global__ kernels;
 //   host    a handle derived from LaneHandle with Params, abi, kernel_ns, block, seed_kind, params(), step_elems(), reset_kernel(),
-//           kernel<MODE>(kind), and whichever of layout_arg() / actions_refusal() differ from the defaults;
+//           kernel<MODE>(kind), and whichever of layout_arg() / actions_refusal() differ from the defaults; for the terminal rows of fused
+//           rollouts (emergency, space station, farm) RowsParams, rows_ns and launch_rows() as well, see LaneHandle;
 //   C ABI   entry points that are one lane_seed / lane_reset / lane_step / lane_rollout call each, with the type's own pointer and
 //           stride predicates and error texts as arguments.
 // Parking's seed / reset have the same shape and use lane_seed / lane_reset (and lane_blocks for its grid); the rest of parking is its own.
@@ -85,6 +86,45 @@ __device__ __forceinline__ void lane_sums(const P &p, int64_t i, double rsum, in
     if (p.done_count) p.done_count[i] = dcount;
 }
 
+// One step's terminal rows in a rows rollout (rollout_rows_kernel<ACTIONS>: SAME_STEP, launched only while rows are registered; the
+// emergency, space-station and farm types).  The segment is the wave's 64 envs and `used` its fill count, wave-uniform and in a
+// register for the whole launch; it counts past the capacity, and lane 0 writes it to count[blockIdx.x] after the step loop.  The lanes
+// with `fin` take the segment's next rows in lane order and record (t, env) for them (final_slot).  Returns whether a row is to be
+// stored — the same for every lane, so the caller's store pass may have barriers: `dst` is then the segment's first free row, `keep`
+// how many of this step's rows fit and `rank` this lane's place among the finishing ones; its row is kept if fin && rank < keep.  A
+// type with a tile parks the kept lanes' groups in columns 0..keep-1 and writes `keep` dense rows at `dst` (lane_store_tile); a type
+// whose lanes store their own rows has the kept lanes store row `rank` of `dst`.
+template <class T>
+__device__ __forceinline__ bool lane_final_rows(const FinalSeg &f, uint32_t &used, bool fin, int64_t t, int64_t i, int64_t row_elems, T *&dst, int &keep,
+                                                int &rank) {
+    const unsigned long long m = __ballot(fin);
+    if (!m) return false;
+    (void)final_slot(f, (int64_t)blockIdx.x, used, fin, t, i);
+    const int64_t room = f.cap - (int64_t)used;
+    const int ends = __popcll(m);
+    keep = room <= 0 ? 0 : room < ends ? (int)room : ends;
+    rank = __popcll(m & ((1ull << (threadIdx.x & 63u)) - 1ull));
+    dst = static_cast<T *>(f.rows) + ((int64_t)blockIdx.x * f.cap + (int64_t)used) * row_elems;
+    used += (uint32_t)ends;
+    return keep > 0;
+}
+// The store pass of a tile parked [element][column] with STRIDE floats a row: floats [FIRST, FIRST + COUNT) of the dense rows
+// 0..nrows-1 at `rows` (`row` floats each) from columns 0..nrows-1, as pieces of PIECE floats with consecutive lanes on consecutive
+// pieces of a row.  Call with every lane of a one-wave workgroup, between the barriers that hand the tile over.
+template <int FIRST, int COUNT, int PIECE, int STRIDE>
+__device__ __forceinline__ void lane_store_tile(const float *__restrict__ stg, float *__restrict__ rows, int row, int nrows) {
+    static_assert((PIECE == 4 || PIECE == 2) && FIRST % PIECE == 0 && COUNT % PIECE == 0, "whole pieces");
+    constexpr int PER = COUNT / PIECE;
+    const int pieces = nrows * PER;
+    for (int q = (int)threadIdx.x; q < pieces; q += 64) {
+        const int r = q / PER, pc = q - r * PER;
+        const float *s = stg + (PIECE * pc) * STRIDE + r;
+        float *dst = rows + (int64_t)r * row + FIRST + PIECE * pc;
+        if (PIECE == 4) *reinterpret_cast<float4 *>(dst) = make_float4(s[0], s[STRIDE], s[2 * STRIDE], s[3 * STRIDE]);
+        else *reinterpret_cast<float2 *>(dst) = make_float2(s[0], s[STRIDE]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host
 enum LaneKind { LANE_STEP, LANE_ROLLOUT_GIVEN, LANE_ROLLOUT_HASHED };   // the kernel of a launch: step(), rollout() with / without actions
 
@@ -103,6 +143,9 @@ struct LaneHandle : HandleBase {
     // the shared fields a handle knows; the per-call ones are filled in by the drivers below
     template <class P>
     void fill(P &p) const { p.state = state; p.mt = mt; p.n = n; p.env0 = env0; p.err_count = err; p.ep_ret = ep_ret; p.ep_len = ep_len; }
+    // A type with terminal rows adds RowsParams (its Params and `FinalSeg fin`), launch_rows(given, blocks, stream, params) and this,
+    // the namespace of its rollout_rows_kernel
+    static constexpr const char *rows_ns = nullptr;
     const char *layout_arg() const { return ""; }                                   // template arguments between MODE and ACTIONS, as text
     static const char *actions_refusal(const int32_t *) { return nullptr; }         // why the type cannot read these actions, or nullptr
 };
@@ -163,7 +206,9 @@ int lane_step(H *h, bool have, const char *what, const int32_t *actions, O *obs,
 }
 
 // cge_<env>_rollout.  `env_ok` / `what`: as rollout_params_nofin (cge_host.hpp); `flags`: the per-step trajectory of the flag the
-// type raises.  k_steps == 0 launches nothing.
+// type raises.  k_steps == 0 launches nothing.  With terminal rows registered (cge_rows_<env>_rollout_final_obs, a type with rows_ns) a
+// SAME_STEP rollout runs rollout_rows_kernel; in the other modes no episode ends with a reset inside the step, so the usual instance
+// runs and the segments' counts are cleared on the call's stream.
 template <class H, class O>
 int lane_rollout(H *h, bool env_ok, const char *what, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, O *obs,
                  int64_t obs_step_stride, float *reward, uint8_t *flags, double *reward_sum, int32_t *done_count, void *stream) {
@@ -176,6 +221,17 @@ int lane_rollout(H *h, bool env_ok, const char *what, int32_t k_steps, const int
     DeviceGuard g(h->device);
     p.actions = actions;
     (H::Params::terminates ? p.terminated : p.truncated) = flags;
+    if constexpr (H::rows_ns != nullptr) {
+        if (h->fin_rows && h->cfg.autoreset_mode == CGE_AUTORESET_SAME_STEP) {
+            typename H::RowsParams rp;
+            static_cast<typename H::Params &>(rp) = p;
+            rp.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+            h->launch_rows(actions != nullptr, lane_blocks(h), as_stream(stream), rp);
+            h->last_kernel = std::string(H::rows_ns) + (actions ? "rollout_rows_kernel<true>" : "rollout_rows_kernel<false>");
+            return launched(h);
+        }
+        if (h->fin_rows) CGE_TRY(h, hipMemsetAsync(h->fin_count, 0, lane_blocks(h) * sizeof(int32_t), as_stream(stream)));
+    }
     lane_launch(h, actions ? LANE_ROLLOUT_GIVEN : LANE_ROLLOUT_HASHED, p, "rollout_kernel", actions ? ", true" : ", false", as_stream(stream));
     return launched(h);
 }

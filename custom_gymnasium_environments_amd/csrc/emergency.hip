@@ -47,6 +47,9 @@ struct Params : LaneParams<float> {
     uint32_t max_t;
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+struct RowsParams : Params {                                         // rollout_rows_kernel's: the other kernels' arguments stay as they are
+    FinalSeg fin;
+};
 
 // what a runtime index reaches (emergency_env.hpp's accessor): LDS rows of this lane
 struct Mem {
@@ -208,15 +211,48 @@ __device__ __forceinline__ void observe(const Env &e, Mem &m, float *__restrict_
     observe_group<200, 76>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
 }
 
+// observe_group for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` store row `rank` of
+// `rows` as they store their own rows everywhere else (there is no tile: the record fills the LDS); the LDS variant parks their group
+// in column `rank` and writes `keep` dense rows.  Call with every lane of the wave.
+template <int FIRST, int COUNT, class G>
+__device__ __forceinline__ void final_group(float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, G gen) {
+#ifndef CGE_EMERGENCY_LDS_ROWS
+    observe_group<FIRST, COUNT>(stg, rows, keep, rank, mine, gen);
+#else
+    if (mine) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + rank] = x; });
+    __syncthreads();
+    lane_store_tile<FIRST, COUNT, 4, STG_ROW>(stg, rows, OBS, keep);
+    __syncthreads();
+#endif
+}
+__device__ __forceinline__ void final_observe(const Env &e, Mem &m, float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, uint32_t max_t) {
+    final_group<0, 80>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < NI; ++s) observe_incident(e, m, out, s);
+    });
+    final_group<80, 60>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 20; ++u) observe_unit(e, m, out, u);
+    });
+    final_group<140, 60>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 20; u < 40; ++u) observe_unit(e, m, out, u);
+    });
+    final_group<200, 76>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
+}
+
 #define CGE_EMERGENCY_LDS                                                               \
     __shared__ uint32_t s_iw[NI * BLOCK], s_im[NI * BLOCK], s_is[NI * BLOCK], s_uw[NU * BLOCK]; \
     __shared__ double s_fa[NU * BLOCK];                                                 \
     __shared__ float s_stg[STG_FLOATS];
 
 // k steps with the record in registers and LDS.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else
-// the counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 50, 0).
-template <int MODE, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// the counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 50, 0).  With RowsParams (ROWS, a SAME_STEP rollout) the terminal rows
+// go to the wave's segment of p.fin.
+template <int MODE, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     CGE_EMERGENCY_LDS
     const int lane = (int)threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
@@ -230,6 +266,7 @@ __device__ __forceinline__ void run(const Params &p) {
     const uint64_t key = GIVEN ? 0 : hash_env_key(p.a_seed, (uint64_t)(p.env0 + li));
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                           // ROWS: terminal rows the wave's segment has been handed
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -252,6 +289,11 @@ __device__ __forceinline__ void run(const Params &p) {
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal rows: every env of a wave with a terminated one
             if (p.final_obs && __ballot(term)) observe(e, m, s_stg, p.final_obs, p.n, live, p.max_t);
         }
+        if constexpr (ROWS) {                                        // ... of the terminated envs only, compacted: lane_final_rows
+            float *dst;
+            int keep, rank;
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, OBS, dst, keep, rank), false)) final_observe(e, m, s_stg, dst, keep, rank, term && rank < keep, p.max_t);
+        }
         if (live && MODE != CGE_AUTORESET_DISABLED && reset_now) reset_episode(e, m, rng);
         if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, m, s_stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, live, p.max_t);
         if (live) {
@@ -272,6 +314,9 @@ __device__ __forceinline__ void run(const Params &p) {
         store_env(e, m, c);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if (lane == 0) p.fin.count[blockIdx.x] = (int32_t)fin_used;
+    }
 }
 
 template <int MODE>
@@ -279,6 +324,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, false
 
 template <int MODE, bool ACTIONS_GIVEN>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, true, ACTIONS_GIVEN>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_emergency_rollout_final_obs)
+template <bool ACTIONS_GIVEN>
+__global__ __launch_bounds__(BLOCK) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, true, ACTIONS_GIVEN>(p); }
 
 // reset (mask) / construction (init, or rewind after a re-seed: the constructor's draws from the start of the stream, which leave the
 // env without an incident until the reset that follows) + obs
@@ -346,9 +395,10 @@ using namespace cge;
 
 struct cge_emergency : LaneHandle {
     using Params = emergency::Params;
+    using RowsParams = emergency::RowsParams;
     cge_emergency_config cfg{};
     static constexpr uint32_t snap_tag = 9u;
-    static constexpr const char *abi = "cge_emergency", *kernel_ns = "cge::emergency::";
+    static constexpr const char *abi = "cge_emergency", *kernel_ns = "cge::emergency::", *rows_ns = kernel_ns;
     static constexpr int block = emergency::BLOCK, seed_kind = 0;
     Params params() const {
         Params p{};
@@ -362,6 +412,9 @@ struct cge_emergency : LaneHandle {
     auto kernel(LaneKind kind) const {
         return kind == LANE_STEP ? emergency::step_kernel<MODE>
                : kind == LANE_ROLLOUT_GIVEN ? emergency::rollout_kernel<MODE, true> : emergency::rollout_kernel<MODE, false>;
+    }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        hipLaunchKernelGGL(given ? emergency::rollout_rows_kernel<true> : emergency::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
     }
     static int check(const cge_emergency_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 1 || c.max_timesteps > 65535 ? CGE_ERR_INVALID_ARG : CGE_OK;
@@ -400,7 +453,8 @@ int cge_emergency_step(cge_emergency *h, const int32_t *actions, float *obs_out,
 int cge_emergency_rollout(cge_emergency *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                           int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                           int32_t *done_count_out, void *stream) {
-    return lane_rollout(h, obs_step_stride % 4 == 0 && rows_aligned(obs_out, nullptr), "cge_emergency_rollout: bad k_steps / obs_step_stride / obs alignment",
+    return lane_rollout(h, h && obs_step_stride % 4 == 0 && rows_aligned(obs_out, h->fin_rows),
+                        "cge_emergency_rollout: bad k_steps / obs_step_stride, or obs / the registered terminal rows not 16-byte aligned",
                         k_steps, actions, action_seed, t0, obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out,
                         stream);
 }
@@ -414,6 +468,7 @@ int cge_emergency_info(cge_emergency *h, int32_t field_id, double *out, void *st
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(emergency, float, 64)
 CGE_DEFINE_ERROR_COUNT(emergency)
 CGE_DEFINE_SNAPSHOT(emergency)
 

@@ -49,6 +49,9 @@ struct Params : LaneParams<float> {
     int32_t row;                                                     // floats of an observation row: 620, or 134 (compact_obs)
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+struct RowsParams : Params {                                         // rollout_rows_kernel's: the other kernels' arguments stay as they are
+    FinalSeg fin;
+};
 
 // the env's columns: word w of env i at rec[w * n + i].  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
 // addresses every column.  After fresh() the offset is a new value to the compiler: the addresses are formed again where they are
@@ -148,10 +151,50 @@ __device__ __forceinline__ void observe_rows(const Env &e, float *__restrict__ s
     }
 }
 
+// observe_group for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` park their group in
+// column `rank`, and the store pass writes `keep` dense rows at `rows`.  Call with every lane of the wave.
+template <int FIRST, int COUNT, int PIECE>
+__device__ __forceinline__ void final_group(const Env &e, float *__restrict__ stg, float *__restrict__ rows, int row, int keep, int rank, bool mine) {
+    static_assert(COUNT <= STG_COUNT, "the tile");
+    if (mine) {
+        auto sink = [&](int k, float x) __attribute__((always_inline)) {
+            if (k >= FIRST && k < FIRST + COUNT) stg[(k - FIRST) * STG_ROW + rank] = x;
+        };
+        observe(e, sink);
+#pragma unroll
+        for (int k = LIVE; k < FIRST + COUNT; ++k) stg[(k - FIRST) * STG_ROW + rank] = 0.0f;
+    }
+    __syncthreads();
+    lane_store_tile<FIRST, COUNT, PIECE, STG_ROW>(stg, rows, row, keep);
+    __syncthreads();                                                 // the tile is free for the next group
+}
+// ... and observe_rows: `keep` rows of `row` floats at `rows`, the padding of a full row included
+__device__ __forceinline__ void final_observe(const Env &e, float *__restrict__ stg, float *__restrict__ rows, int row, int keep, int rank, bool mine) {
+    if (row == OBS) {
+        final_group<0, 36, 4>(e, stg, rows, OBS, keep, rank, mine);
+        final_group<36, 36, 4>(e, stg, rows, OBS, keep, rank, mine);
+        final_group<72, 36, 4>(e, stg, rows, OBS, keep, rank, mine);
+        final_group<108, 4 * LIVE_PIECES - 108, 4>(e, stg, rows, OBS, keep, rank, mine);
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int q = (int)threadIdx.x; q < keep * ZERO_PIECES; q += BLOCK) {
+            const int r = q / ZERO_PIECES, pc = q - r * ZERO_PIECES;
+            *reinterpret_cast<float4 *>(rows + (int64_t)r * OBS + 4 * (LIVE_PIECES + pc)) = zero;
+        }
+    } else {
+        final_group<0, 36, 2>(e, stg, rows, LIVE, keep, rank, mine);
+        final_group<36, 36, 2>(e, stg, rows, LIVE, keep, rank, mine);
+        final_group<72, 36, 2>(e, stg, rows, LIVE, keep, rank, mine);
+        final_group<108, LIVE - 108, 2>(e, stg, rows, LIVE, keep, rank, mine);
+    }
+}
+
 // k steps with the record in registers.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else the
-// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 45, 0).
-template <int MODE, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 45, 0).  With RowsParams (ROWS, a SAME_STEP rollout) the terminal rows
+// go to the wave's segment of p.fin.
+template <int MODE, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     __shared__ float s_stg[STG_FLOATS];
     const int lane = (int)threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
@@ -164,6 +207,7 @@ __device__ __forceinline__ void run(const Params &p) {
     const uint64_t key = GIVEN ? 0 : hash_env_key(p.a_seed, (uint64_t)(p.env0 + li));
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                           // ROWS: terminal rows the wave's segment has been handed
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -183,6 +227,11 @@ __device__ __forceinline__ void run(const Params &p) {
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal rows: every env of a wave with a terminated one
             if (p.final_obs && __ballot(term)) observe_rows(e, s_stg, p.final_obs, p.n, p.row, live);
+        }
+        if constexpr (ROWS) {                                        // ... of the terminated envs only, compacted: lane_final_rows
+            float *dst;
+            int keep, rank;
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, p.row, dst, keep, rank), false)) final_observe(e, s_stg, dst, p.row, keep, rank, term && rank < keep);
         }
         if (live && MODE != CGE_AUTORESET_DISABLED && reset_now) reset_episode(e, rng);
         if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe_rows(e, s_stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, p.row, live);
@@ -204,6 +253,9 @@ __device__ __forceinline__ void run(const Params &p) {
         store_env(e, c);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if (lane == 0) p.fin.count[blockIdx.x] = (int32_t)fin_used;
+    }
 }
 
 template <int MODE>
@@ -211,6 +263,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, false
 
 template <int MODE, bool ACTIONS_GIVEN>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, true, ACTIONS_GIVEN>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_farm_rollout_final_obs)
+template <bool ACTIONS_GIVEN>
+__global__ __launch_bounds__(BLOCK) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, true, ACTIONS_GIVEN>(p); }
 
 // reset (mask) / construction (init, or rewind after a re-seed: a fresh AgriculturalFarmEnv(), which draws its fields, equipment and
 // market, on both streams at their start) + obs
@@ -253,10 +309,11 @@ using namespace cge;
 
 struct cge_farm : LaneHandle {
     using Params = farm::Params;
+    using RowsParams = farm::RowsParams;
     cge_farm_config cfg{};
     uint32_t *py = nullptr;
     static constexpr uint32_t snap_tag = 11u;
-    static constexpr const char *abi = "cge_farm", *kernel_ns = "cge::farm::";
+    static constexpr const char *abi = "cge_farm", *kernel_ns = "cge::farm::", *rows_ns = kernel_ns;
     static constexpr int block = farm::BLOCK, seed_kind = 1;         // `mt`: np.random.seed; `py` is seeded as random.seed (kind 0)
     int row() const { return cfg.compact_obs ? farm::LIVE : farm::OBS; }
     Params params() const {
@@ -273,6 +330,9 @@ struct cge_farm : LaneHandle {
     auto kernel(LaneKind kind) const {
         return kind == LANE_STEP ? farm::step_kernel<MODE>
                : kind == LANE_ROLLOUT_GIVEN ? farm::rollout_kernel<MODE, true> : farm::rollout_kernel<MODE, false>;
+    }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        hipLaunchKernelGGL(given ? farm::rollout_rows_kernel<true> : farm::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
     }
     static int check(const cge_farm_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_years < 1 || c.max_years > 255 || c.compact_obs < 0 || c.compact_obs > 1 ? CGE_ERR_INVALID_ARG : CGE_OK;
@@ -323,8 +383,8 @@ int cge_farm_step(cge_farm *h, const int32_t *actions, float *obs_out, float *re
 
 int cge_farm_rollout(cge_farm *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out, int64_t obs_step_stride,
                      float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out, int32_t *done_count_out, void *stream) {
-    return lane_rollout(h, h && obs_step_stride % (h->cfg.compact_obs ? 2 : 4) == 0 && rows_aligned(h, obs_out, nullptr),
-                        "cge_farm_rollout: bad k_steps / obs_step_stride / obs alignment", k_steps, actions, action_seed, t0, obs_out, obs_step_stride,
+    return lane_rollout(h, h && obs_step_stride % (h->cfg.compact_obs ? 2 : 4) == 0 && rows_aligned(h, obs_out, h->fin_rows),
+                        "cge_farm_rollout: bad k_steps / obs_step_stride, or obs / the registered terminal rows not 16-byte aligned (compact_obs: 8-byte)", k_steps, actions, action_seed, t0, obs_out, obs_step_stride,
                         reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out, stream);
 }
 
@@ -336,6 +396,7 @@ int cge_farm_info(cge_farm *h, int32_t field_id, double *out, void *stream) {
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(farm, float, 64)
 CGE_DEFINE_ERROR_COUNT(farm)
 CGE_DEFINE_SNAPSHOT(farm)
 

@@ -49,6 +49,9 @@ struct Params : LaneParams<float> {
     uint32_t max_t;
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+struct RowsParams : Params {                                         // rollout_rows_kernel's: the other kernels' arguments stay as they are
+    FinalSeg fin;
+};
 
 // the env's columns: word w of env i at rec[w * n + i].  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
 // addresses every column.  After fresh() the offset is a new value to the compiler: the addresses are formed again where they are
@@ -164,10 +167,33 @@ __device__ __forceinline__ void observe(const Env &e, float *__restrict__ stg, f
     observe_group<92, 28>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) { observe_rest(e, out); });
 }
 
+// observe_group for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` park their group in
+// column `rank`, and the store pass writes `keep` dense rows at `rows`.  Call with every lane of the wave.
+template <int FIRST, int COUNT, class G>
+__device__ __forceinline__ void final_group(float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, G gen) {
+#ifndef CGE_STATION_LANE_ROWS
+    if (mine) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + rank] = x; });
+    __syncthreads();
+    lane_store_tile<FIRST, COUNT, 4, STG_ROW>(stg, rows, OBS, keep);
+    __syncthreads();                                                 // the tile is free for the next group
+#else
+    observe_group<FIRST, COUNT>(stg, rows, keep, rank, mine, gen);   // per-lane stores: the lane's row is row `rank`
+#endif
+}
+__device__ __forceinline__ void final_observe(const Env &e, float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine) {
+    final_group<0, 24>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_crew(e, out); });
+    final_group<24, 36>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_systems(e, out); });
+    final_group<60, 32>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_modules(e, out); });
+    final_group<92, 28>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_rest(e, out); });
+}
+
 // k steps with the record in registers.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else the
-// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 40, 0).
-template <int MODE, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 40, 0).  With RowsParams (ROWS, a SAME_STEP rollout) the terminal rows
+// go to the wave's segment of p.fin.
+template <int MODE, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     __shared__ float s_stg[STG_FLOATS];
     const int lane = (int)threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
@@ -180,6 +206,7 @@ __device__ __forceinline__ void run(const Params &p) {
     const uint64_t key = GIVEN ? 0 : hash_env_key(p.a_seed, (uint64_t)(p.env0 + li));
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                           // ROWS: terminal rows the wave's segment has been handed
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -199,6 +226,11 @@ __device__ __forceinline__ void run(const Params &p) {
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal rows: every env of a wave with a terminated one
             if (p.final_obs && __ballot(term)) observe(e, s_stg, p.final_obs, p.n, live);
+        }
+        if constexpr (ROWS) {                                        // ... of the terminated envs only, compacted: lane_final_rows
+            float *dst;
+            int keep, rank;
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, OBS, dst, keep, rank), false)) final_observe(e, s_stg, dst, keep, rank, term && rank < keep);
         }
         if (live && MODE != CGE_AUTORESET_DISABLED && reset_now) reset_episode(e, rng);
         if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, s_stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, live);
@@ -221,6 +253,9 @@ __device__ __forceinline__ void run(const Params &p) {
         store_env(e, c);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if (lane == 0) p.fin.count[blockIdx.x] = (int32_t)fin_used;
+    }
 }
 
 template <int MODE>
@@ -228,6 +263,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, false
 
 template <int MODE, bool ACTIONS_GIVEN>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, true, ACTIONS_GIVEN>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_space_station_rollout_final_obs)
+template <bool ACTIONS_GIVEN>
+__global__ __launch_bounds__(BLOCK) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, true, ACTIONS_GIVEN>(p); }
 
 // reset (mask) / construction (init, or rewind after a re-seed: a fresh SpaceStationEnv(), which draws nothing, on a stream at its
 // start) + obs
@@ -270,9 +309,10 @@ using namespace cge;
 
 struct cge_space_station : LaneHandle {
     using Params = station::Params;
+    using RowsParams = station::RowsParams;
     cge_space_station_config cfg{};
     static constexpr uint32_t snap_tag = 10u;
-    static constexpr const char *abi = "cge_space_station", *kernel_ns = "cge::station::";
+    static constexpr const char *abi = "cge_space_station", *kernel_ns = "cge::station::", *rows_ns = kernel_ns;
     static constexpr int block = station::BLOCK, seed_kind = 1;      // np.random.seed
     Params params() const {
         Params p{};
@@ -286,6 +326,9 @@ struct cge_space_station : LaneHandle {
     auto kernel(LaneKind kind) const {
         return kind == LANE_STEP ? station::step_kernel<MODE>
                : kind == LANE_ROLLOUT_GIVEN ? station::rollout_kernel<MODE, true> : station::rollout_kernel<MODE, false>;
+    }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        hipLaunchKernelGGL(given ? station::rollout_rows_kernel<true> : station::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
     }
     static int check(const cge_space_station_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 1 || c.max_steps > 65535 ? CGE_ERR_INVALID_ARG : CGE_OK;
@@ -324,7 +367,8 @@ int cge_space_station_step(cge_space_station *h, const int32_t *actions, float *
 int cge_space_station_rollout(cge_space_station *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                               int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                               int32_t *done_count_out, void *stream) {
-    return lane_rollout(h, obs_step_stride % 4 == 0 && rows_aligned(obs_out, nullptr), "cge_space_station_rollout: bad k_steps / obs_step_stride / obs alignment",
+    return lane_rollout(h, h && obs_step_stride % 4 == 0 && rows_aligned(obs_out, h->fin_rows),
+                        "cge_space_station_rollout: bad k_steps / obs_step_stride, or obs / the registered terminal rows not 16-byte aligned",
                         k_steps, actions, action_seed, t0, obs_out, obs_step_stride, reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out,
                         stream);
 }
@@ -337,6 +381,7 @@ int cge_space_station_info(cge_space_station *h, int32_t field_id, double *out, 
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(space_station, float, 64)
 CGE_DEFINE_ERROR_COUNT(space_station)
 CGE_DEFINE_SNAPSHOT(space_station)
 

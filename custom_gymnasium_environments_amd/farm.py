@@ -41,6 +41,8 @@ class AgriculturalFarmVectorEnv(DeviceVectorEnv):
     `terminated` when `year > max_years` (the reference's attribute, 1; 1..255) — in the step that makes the day a multiple of 360 —
     or when `cash_flow < -50000` (-5000).  The reference never truncates.  In Disabled mode the reference may be stepped on past
     termination; so may this.  In SameStep mode `infos["final_obs"]` is valid where `terminated`; its other rows are unspecified.
+    The terminal rows of a fused rollout go to a side output once `collect_final_obs()` has registered one (`final_obs()`,
+    `final_obs_dropped()`; segments of 64 envs), in either layout.
 
     Streams: the reference draws from the process-global `np.random` and, for the crop it plants, from CPython's global `random`,
     and seeds neither, so env i owns both streams of `s_i = seed + env_index0 + i`.  `reset(seed=s)` is `random.seed(s_i);
@@ -56,7 +58,7 @@ class AgriculturalFarmVectorEnv(DeviceVectorEnv):
     step's; with per_step=True (obs, reward[k, N], terminated[k, N], reward_sum, done_count).  A SAME_STEP trajectory holds the reset
     observation at a terminated step, as step()'s `obs` does.
 
-    Not built: a registry id (the reference registers none), rendering, terminal rows of fused SameStep rollouts, a bench workload,
+    Not built: a registry id (the reference registers none), rendering, a bench workload,
     canonical get_state / set_state records (`snapshot()` / `restore()` checkpoint the whole batch)."""
 
     _abi = "cge_farm"

@@ -50,10 +50,11 @@ class SpaceStationVectorEnv(DeviceVectorEnv):
     rollout(k): k fused step()s in one launch.  actions: None -> counter-hash actions cge_hash_action(action_seed, env_index0 + i,
     t0 + t, 40, 0), or int32 [k, N].  Returns (obs, reward_sum, done_count) with obs [k, N, 120] if trajectory else the last step's
     [N, 120]; with per_step=True (obs, reward[k, N], terminated[k, N], reward_sum, done_count).  A SAME_STEP trajectory holds the reset
-    observation at a terminated step, as step()'s `obs` does; the terminal rows of a fused rollout and its per-step `truncated`
-    (terminated in the step that reaches `max_steps`) are not delivered.
+    observation at a terminated step, as step()'s `obs` does; the terminal rows of a fused rollout go to a side
+    output once `collect_final_obs()` has registered one (`final_obs()`, `final_obs_dropped()`; segments of 64 envs).  Its per-step
+    `truncated` (terminated in the step that reaches `max_steps`) is not delivered.
 
-    Not built: a registry id, rendering, terminal rows of fused SameStep rollouts, a bench workload, canonical get_state / set_state
+    Not built: a registry id, rendering, a bench workload, canonical get_state / set_state
     records (`snapshot()` / `restore()` checkpoint the whole batch)."""
 
     _abi = "cge_space_station"

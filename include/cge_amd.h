@@ -860,6 +860,11 @@ int cge_emergency_step(cge_emergency *h, const int32_t *actions, float *obs_out,
 int cge_emergency_rollout(cge_emergency *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                           int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                           int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * While rows are registered a SAME_STEP rollout runs its rollout_rows_kernel instance; rows_out must be 16-byte aligned, or
+ * cge_emergency_rollout refuses it.  The two are named cge_rows_emergency_*: they stand beside the type's surface cge_emergency_*, which is as it was */
+int cge_rows_emergency_rollout_final_obs(cge_emergency *h, float *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_emergency_final_obs_segment(const cge_emergency *h);
 int cge_emergency_info(cge_emergency *h, int32_t field_id, double *out, void *stream);
 /* env-steps whose action was outside 0..49 since the last call; synchronises */
 int64_t cge_emergency_error_count(cge_emergency *h, void *stream);
@@ -940,6 +945,11 @@ int cge_space_station_step(cge_space_station *h, const int32_t *actions, float *
 int cge_space_station_rollout(cge_space_station *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out,
                               int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                               int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * While rows are registered a SAME_STEP rollout runs its rollout_rows_kernel instance; rows_out must be 16-byte aligned, or
+ * cge_space_station_rollout refuses it.  The two are named cge_rows_space_station_*: they stand beside the type's surface cge_space_station_*, which is as it was */
+int cge_rows_space_station_rollout_final_obs(cge_space_station *h, float *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_space_station_final_obs_segment(const cge_space_station *h);
 int cge_space_station_info(cge_space_station *h, int32_t field_id, double *out, void *stream);
 /* env-steps whose action was outside 0..39 since the last call; synchronises */
 int64_t cge_space_station_error_count(cge_space_station *h, void *stream);
@@ -1027,6 +1037,11 @@ int cge_farm_step(cge_farm *h, const int32_t *actions, float *obs_out, float *re
  * not delivered. */
 int cge_farm_rollout(cge_farm *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out, int64_t obs_step_stride,
                      float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out, int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * While rows are registered a SAME_STEP rollout runs its rollout_rows_kernel instance; rows_out must be 16-byte aligned (compact_obs: 8-byte), or
+ * cge_farm_rollout refuses it.  The two are named cge_rows_farm_*: they stand beside the type's surface cge_farm_*, which is as it was */
+int cge_rows_farm_rollout_final_obs(cge_farm *h, float *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_farm_final_obs_segment(const cge_farm *h);
 int cge_farm_info(cge_farm *h, int32_t field_id, double *out, void *stream);
 /* env-steps whose action was outside 0..44 since the last call; synchronises */
 int64_t cge_farm_error_count(cge_farm *h, void *stream);
