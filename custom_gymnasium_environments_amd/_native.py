@@ -137,9 +137,9 @@ _ENV_TYPES = {
     "fleet": (FleetConfig, "final_obs info snapshot done_mask"),
     "manufacturing": (ManufacturingConfig, "final_obs info snapshot done_mask"),
     "hospital": (HospitalConfig, "final_obs info snapshot done_mask"),
-    "bus": (BusConfig, "info_indexed error_count snapshot"),
-    "world_builder": (WorldBuilderConfig, "info_indexed error_count state"),
-    "restaurant": (RestaurantConfig, "info error_count snapshot"),
+    "bus": (BusConfig, "final_obs_rows info_indexed error_count snapshot"),
+    "world_builder": (WorldBuilderConfig, "final_obs_rows info_indexed error_count state"),
+    "restaurant": (RestaurantConfig, "final_obs_rows info error_count snapshot"),
     "airline": (AirlineConfig, "info error_count snapshot"),
     "emergency": (EmergencyConfig, "final_obs_rows info error_count snapshot"),
     "space_station": (SpaceStationConfig, "final_obs_rows info error_count snapshot"),

@@ -62,3 +62,43 @@ class SlabVectorEnv(DeviceVectorEnv):
     def obs_slab(self, obs):
         """The flat slab ([slab_elems], or [k, slab_elems] for a trajectory) behind an observation dict of this env."""
         return slab_of(obs, self._planes, self._slab, self._obs_dtype)
+
+    # ------------------------------------------------------------------ terminal observations of fused SAME_STEP rollouts
+    # The compacted rows are a slab too: the type's ordinary observation slab for R = segments * capacity "envs", row j of segment s
+    # being env s * capacity + j of it (include/cge_amd.h).  A type without a slab (world builder's flatten_obs) has the base class's rows.
+    def _rows_layout(self, num_rows):
+        """(the plane table, slab elements) of this type's observation slab for `num_rows` envs."""
+        raise NotImplementedError
+
+    def collect_final_obs(self, rows_per_env=4):
+        if rows_per_env <= 0 or getattr(self, "_planes", None) is None:
+            self._fin_planes = None
+            return super().collect_final_obs(rows_per_env)
+        seg = self.final_obs_segment = int(self._fn("final_obs_segment")(self._h))
+        nseg, cap = -(-self.num_envs // seg), int(seg * rows_per_env)
+        planes, elems = self._rows_layout(nseg * cap)
+        rows = torch.empty(elems, dtype=self._obs_dtype, device=self.device)
+        index = torch.empty(nseg * cap, dtype=torch.int64, device=self.device)
+        count = torch.zeros(nseg, dtype=torch.int32, device=self.device)
+        self._check(self._fn("rollout_final_obs")(self._h, rows.data_ptr(), index.data_ptr(), cap, count.data_ptr()), "rollout_final_obs")
+        self._fin, self._fin_planes = (rows, index, count, cap), planes
+
+    collect_final_obs.__doc__ = DeviceVectorEnv.collect_final_obs.__doc__
+
+    def final_obs(self):
+        """(rows, step [m], env [m]) delivered by the last rollout(), sorted by (step, env): `rows` is a dict {key: tensor [m, ...]} in
+        the keys' dtypes and gymnasium's batched-Dict shapes, and rows[key][j] belongs to the terminal observation of env[j] at step
+        step[j] of that call.  Gathers the segments' rows on the device (boolean indexing: synchronises)."""
+        rows, index, count, cap = self._fin_buffers()
+        if getattr(self, "_fin_planes", None) is None:
+            return super().final_obs()
+        keep = (torch.arange(cap, device=rows.device)[None, :] < count.clamp(max=cap)[:, None]).reshape(-1)
+        idx = index[keep]
+        order = torch.argsort(idx)
+        idx = idx[order]
+        return gather_rows(rows, keep, order, self._fin_planes), idx // self.num_envs, idx % self.num_envs
+
+
+def gather_rows(slab, keep, order, planes):
+    """The rows `keep` (bool [R]) of every plane of a rows slab for R = keep.numel() envs, permuted by `order`: {key: tensor [m, ...]}."""
+    return {key: v[keep][order] for key, v in plane_views(slab, keep.numel(), planes).items()}

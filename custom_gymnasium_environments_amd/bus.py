@@ -53,7 +53,9 @@ class BusVectorEnv(SlabVectorEnv):
     (cge_hash_action(action_seed, env_index0 + i, t0 + t, 11, bus)) or int32 [k, N, 4].  Returns (obs, reward_sum, done_count)
     with obs a dict of views [k, N, ...] if trajectory else the last step's [N, ...]; with per_step=True
     (obs, reward[k, N], truncated[k, N], reward_sum, done_count) — the outputs of k step() calls (a SAME_STEP trajectory holds
-    the reset observation at a truncated step, as step()'s `obs` does)."""
+    the reset observation at a truncated step, as step()'s `obs` does; the terminal observations of a fused rollout go to a side output
+    once `collect_final_obs()` has registered one: `final_obs()` returns them as a dict of per-key tensors [m, ...] with their steps and
+    envs, `final_obs_dropped()` what did not fit; segments of 64 envs)."""
 
     _abi = "cge_bus"
     INFO_FIELDS = INFO_FIELDS
@@ -71,6 +73,9 @@ class BusVectorEnv(SlabVectorEnv):
         self.single_observation_space, self.single_action_space = make_spaces(self.max_timesteps)
         self._init_slab(*packed_planes(PLANES, self.num_envs), torch.int32)   # int32 [56 * N] per step
         self._create(_native.BusConfig(self.max_timesteps, self._mode_code), info_fields, record_episode_statistics, reference_info)
+
+    def _rows_layout(self, num_rows):
+        return packed_planes(PLANES, num_rows)
 
     # ------------------------------------------------------------------ extras
     def reference_info(self):

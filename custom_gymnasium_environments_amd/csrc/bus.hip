@@ -50,6 +50,12 @@ struct Params : LaneParams<int32_t> {
     static constexpr bool terminates = false;                       // truncated after max_t steps; terminated is never set (:156)
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+// rollout_rows_kernel's: the other kernels' arguments stay as they are.  fin.rows is the observation slab of R = n_segments * fin.cap
+// "envs" (plane p at p * R ints); row j of segment s is env s * fin.cap + j of it.
+struct RowsParams : Params {
+    FinalSeg fin;
+    int64_t R;
+};
 
 __device__ __forceinline__ uint32_t bsum(uint32_t x) { return (x & 255u) + ((x >> 8) & 255u) + ((x >> 16) & 255u) + (x >> 24); }
 // a[i] for a runtime i in 0..3, mask form (a ternary over array elements becomes "select the address, then load": scratch)
@@ -211,9 +217,12 @@ __device__ __forceinline__ void observe(const Env &e, int32_t *__restrict__ o, i
 }
 
 // k steps with the record in registers.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else the
-// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 11, bus).
-template <int MODE, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 11, bus).  With RowsParams (ROWS, a SAME_STEP rollout) a
+// truncated env's terminal observation goes to the wave's segment of p.fin, each lane storing its own pieces.
+template <int MODE, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
@@ -223,6 +232,9 @@ __device__ __forceinline__ void run(const Params &p) {
     const uint64_t key = GIVEN ? 0 : hash_env_key(p.a_seed, (uint64_t)(p.env0 + li));
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                          // ROWS: terminal rows the wave's segment has been handed
+    // the segment is the wave, not the workgroup: wave-uniform, so a scalar
+    const int64_t seg = ROWS ? (int64_t)blockIdx.x * (BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -255,6 +267,14 @@ __device__ __forceinline__ void run(const Params &p) {
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {
             if (p.final_obs && trunc && reset_now) observe(e, p.final_obs, p.n, i);   // the terminal rows; the others are not written
         }
+        if constexpr (ROWS) {                                       // ... of a rollout, compacted: row `rank` after the segment's `first` used ones
+            const int64_t first = seg * p.fin.cap + (int64_t)fin_used;
+            int32_t *dst;
+            int keep, rank;
+            if (lane_final_rows(p.fin, seg, fin_used, trunc, t, i, 0, dst, keep, rank)) {
+                if (trunc && rank < keep) observe(e, static_cast<int32_t *>(p.fin.rows), p.R, first + rank);
+            }
+        }
         if (MODE != CGE_AUTORESET_DISABLED) {
             if (__ballot(reset_now)) env_reset(e, blk, reset_now);
         }
@@ -275,6 +295,9 @@ __device__ __forceinline__ void run(const Params &p) {
         e.store(p.state, p.n, i);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if ((threadIdx.x & 63u) == 0 && live) p.fin.count[seg] = (int32_t)fin_used;   // a wave past the last env has no segment
+    }
 }
 
 template <int MODE>
@@ -282,6 +305,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, false
 
 template <int MODE, bool ACTIONS>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, true, ACTIONS>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_bus_rollout_final_obs)
+template <bool ACTIONS>
+__global__ __launch_bounds__(BLOCK) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, true, ACTIONS>(p); }
 
 // reset (mask) / initial state (init: cleared buses, no passengers, cursor rewound) / rewind (after a re-seed) + obs
 __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int rewind) {
@@ -332,9 +359,10 @@ using namespace cge;
 
 struct cge_bus : LaneHandle {
     using Params = bus::Params;
+    using RowsParams = bus::RowsParams;
     cge_bus_config cfg{};
     static constexpr uint32_t snap_tag = 6u;
-    static constexpr const char *abi = "cge_bus", *kernel_ns = "cge::bus::";
+    static constexpr const char *abi = "cge_bus", *kernel_ns = "cge::bus::", *rows_ns = kernel_ns;
     static constexpr int block = bus::BLOCK, seed_kind = 0;
     Params params() const {
         Params p{};
@@ -347,6 +375,14 @@ struct cge_bus : LaneHandle {
     template <int MODE>
     auto kernel(LaneKind kind) const {
         return kind == LANE_STEP ? bus::step_kernel<MODE> : kind == LANE_ROLLOUT_GIVEN ? bus::rollout_kernel<MODE, true> : bus::rollout_kernel<MODE, false>;
+    }
+    void fill_rows(RowsParams &p) const { p.R = (int64_t)lane_segments(this) * fin_cap; }
+    // a finishing lane stores 16-byte pieces of every plane of the rows slab
+    const char *rows_refusal() const {
+        return (reinterpret_cast<uintptr_t>(fin_rows) & 15u) != 0 ? "the registered terminal rows are not 16-byte aligned" : nullptr;
+    }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        hipLaunchKernelGGL(given ? bus::rollout_rows_kernel<true> : bus::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
     }
     static int check(const cge_bus_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 0 || c.max_timesteps > 60000 ? CGE_ERR_INVALID_ARG : CGE_OK;
@@ -394,6 +430,7 @@ int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(bus, int32_t, 64)
 CGE_DEFINE_ERROR_COUNT(bus)
 CGE_DEFINE_SNAPSHOT(bus)
 

@@ -96,7 +96,7 @@ int register_final_obs(H *h, void *rows, int64_t *index, int64_t seg_capacity, i
                                        "cge_" #ENV "_rollout_final_obs: rows, index and count go together (all NULL unregisters)");      \
     }                                                                                                                                    \
     int64_t cge_##ENV##_final_obs_segment(const cge_##ENV *h) { return h ? (SEG) : 0; }
-// ... under the names cge_rows_<env>_*: the three types that got the output after their surface cge_<env>_* was fixed at fifteen entry points
+// ... under the names cge_rows_<env>_*: the six types that got the output after their surface cge_<env>_* was fixed at fifteen entry points
 #define CGE_DEFINE_ROWS_FINAL_OBS(ENV, ROWTYPE, SEG)                                                                                          \
     int cge_rows_##ENV##_rollout_final_obs(cge_##ENV *h, ROWTYPE *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out) {   \
         return cge::register_final_obs(h, rows_out, index_out, seg_capacity, count_out,                                                       \

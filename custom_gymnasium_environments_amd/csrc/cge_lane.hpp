@@ -12,7 +12,8 @@
 //           terminated, or truncated), its run() loop calling the lane_* helpers below, and the three __global__ kernels;
 //   host    a handle derived from LaneHandle with Params, abi, kernel_ns, block, seed_kind, params(), step_elems(), reset_kernel(),
 //           kernel<MODE>(kind), and whichever of layout_arg() / actions_refusal() differ from the defaults; for the terminal rows of fused
-//           rollouts (emergency, space station, farm) RowsParams, rows_ns and launch_rows() as well, see LaneHandle;
+//           rollouts (all but airline) RowsParams, rows_ns and launch_rows() as well, and fill_rows() where RowsParams holds more than
+//           `fin` (the Dict types' slab of compacted rows), see LaneHandle;
 //   C ABI   entry points that are one lane_seed / lane_reset / lane_step / lane_rollout call each, with the type's own pointer and
 //           stride predicates and error texts as arguments.
 // Parking's seed / reset have the same shape and use lane_seed / lane_reset (and lane_blocks for its grid); the rest of parking is its own.
@@ -86,27 +87,34 @@ __device__ __forceinline__ void lane_sums(const P &p, int64_t i, double rsum, in
     if (p.done_count) p.done_count[i] = dcount;
 }
 
-// One step's terminal rows in a rows rollout (rollout_rows_kernel<ACTIONS>: SAME_STEP, launched only while rows are registered; the
-// emergency, space-station and farm types).  The segment is the wave's 64 envs and `used` its fill count, wave-uniform and in a
-// register for the whole launch; it counts past the capacity, and lane 0 writes it to count[blockIdx.x] after the step loop.  The lanes
+// One step's terminal rows in a rows rollout (rollout_rows_kernel<ACTIONS>: SAME_STEP, launched only while rows are registered; every
+// lane-per-env type but airline).  The segment `seg` is the wave's 64 envs and `used` its fill count, wave-uniform and in a
+// register for the whole launch; it counts past the capacity, and the wave's first lane writes it to count[seg] after the step loop.  The lanes
 // with `fin` take the segment's next rows in lane order and record (t, env) for them (final_slot).  Returns whether a row is to be
 // stored — the same for every lane, so the caller's store pass may have barriers: `dst` is then the segment's first free row, `keep`
 // how many of this step's rows fit and `rank` this lane's place among the finishing ones; its row is kept if fin && rank < keep.  A
 // type with a tile parks the kept lanes' groups in columns 0..keep-1 and writes `keep` dense rows at `dst` (lane_store_tile); a type
-// whose lanes store their own rows has the kept lanes store row `rank` of `dst`.
+// whose lanes store their own rows has the kept lanes store row `rank` of `dst`.  The types whose rows are a slab (bus, restaurant, world
+// builder) pass row_elems 0 and take the row's number, seg * f.cap + used (before the call) + rank, to the planes of the slab themselves.
 template <class T>
-__device__ __forceinline__ bool lane_final_rows(const FinalSeg &f, uint32_t &used, bool fin, int64_t t, int64_t i, int64_t row_elems, T *&dst, int &keep,
-                                                int &rank) {
+__device__ __forceinline__ bool lane_final_rows(const FinalSeg &f, int64_t seg, uint32_t &used, bool fin, int64_t t, int64_t i, int64_t row_elems, T *&dst,
+                                                int &keep, int &rank) {
     const unsigned long long m = __ballot(fin);
     if (!m) return false;
-    (void)final_slot(f, (int64_t)blockIdx.x, used, fin, t, i);
+    (void)final_slot(f, seg, used, fin, t, i);
     const int64_t room = f.cap - (int64_t)used;
     const int ends = __popcll(m);
     keep = room <= 0 ? 0 : room < ends ? (int)room : ends;
     rank = __popcll(m & ((1ull << (threadIdx.x & 63u)) - 1ull));
-    dst = static_cast<T *>(f.rows) + ((int64_t)blockIdx.x * f.cap + (int64_t)used) * row_elems;
+    dst = static_cast<T *>(f.rows) + (seg * f.cap + (int64_t)used) * row_elems;
     used += (uint32_t)ends;
     return keep > 0;
+}
+// ... in a workgroup of one wave: the segment is the workgroup
+template <class T>
+__device__ __forceinline__ bool lane_final_rows(const FinalSeg &f, uint32_t &used, bool fin, int64_t t, int64_t i, int64_t row_elems, T *&dst, int &keep,
+                                                int &rank) {
+    return lane_final_rows(f, (int64_t)blockIdx.x, used, fin, t, i, row_elems, dst, keep, rank);
 }
 // The store pass of a tile parked [element][column] with STRIDE floats a row: floats [FIRST, FIRST + COUNT) of the dense rows
 // 0..nrows-1 at `rows` (`row` floats each) from columns 0..nrows-1, as pieces of PIECE floats with consecutive lanes on consecutive
@@ -146,12 +154,18 @@ struct LaneHandle : HandleBase {
     // A type with terminal rows adds RowsParams (its Params and `FinalSeg fin`), launch_rows(given, blocks, stream, params) and this,
     // the namespace of its rollout_rows_kernel
     static constexpr const char *rows_ns = nullptr;
+    template <class RP>
+    void fill_rows(RP &) const {}                                                   // what RowsParams holds beside Params and `fin`
+    const char *rows_refusal() const { return nullptr; }                            // why the store pass cannot take the registered rows, or nullptr
     const char *layout_arg() const { return ""; }                                   // template arguments between MODE and ACTIONS, as text
     static const char *actions_refusal(const int32_t *) { return nullptr; }         // why the type cannot read these actions, or nullptr
 };
 
 template <class H>
 unsigned lane_blocks(const H *h) { return (unsigned)((h->n + H::block - 1) / H::block); }
+// segments of the terminal-row output: one per wave of 64 envs, whatever H::block is
+template <class H>
+unsigned lane_segments(const H *h) { return (unsigned)((h->n + 63) / 64); }
 
 template <class H, class P>
 void lane_launch_reset(const H *h, const P &p, int init, int rewind, hipStream_t s) {
@@ -222,15 +236,19 @@ int lane_rollout(H *h, bool env_ok, const char *what, int32_t k_steps, const int
     p.actions = actions;
     (H::Params::terminates ? p.terminated : p.truncated) = flags;
     if constexpr (H::rows_ns != nullptr) {
+        if (const char *why = h->fin_rows ? h->rows_refusal() : nullptr) return lane_refuse_actions(h, "rollout", why);
         if (h->fin_rows && h->cfg.autoreset_mode == CGE_AUTORESET_SAME_STEP) {
             typename H::RowsParams rp;
             static_cast<typename H::Params &>(rp) = p;
             rp.fin = FinalSeg{h->fin_rows, h->fin_index, h->fin_count, h->fin_cap, h->n};
+            h->fill_rows(rp);
             h->launch_rows(actions != nullptr, lane_blocks(h), as_stream(stream), rp);
-            h->last_kernel = std::string(H::rows_ns) + (actions ? "rollout_rows_kernel<true>" : "rollout_rows_kernel<false>");
+            std::string layout = h->layout_arg();                                   // ", true" -> "true, ": the arguments before ACTIONS
+            if (!layout.empty()) layout = layout.substr(2) + ", ";
+            h->last_kernel = std::string(H::rows_ns) + "rollout_rows_kernel<" + layout + (actions ? "true>" : "false>");
             return launched(h);
         }
-        if (h->fin_rows) CGE_TRY(h, hipMemsetAsync(h->fin_count, 0, lane_blocks(h) * sizeof(int32_t), as_stream(stream)));
+        if (h->fin_rows) CGE_TRY(h, hipMemsetAsync(h->fin_count, 0, lane_segments(h) * sizeof(int32_t), as_stream(stream)));
     }
     lane_launch(h, actions ? LANE_ROLLOUT_GIVEN : LANE_ROLLOUT_HASHED, p, "rollout_kernel", actions ? ", true" : ", false", as_stream(stream));
     return launched(h);

@@ -38,6 +38,12 @@ struct Params : LaneParams<int32_t> {
     static constexpr bool terminates = false;                        // truncated after max_t steps; terminated is never set (:100)
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+// rollout_rows_kernel's: the other kernels' arguments stay as they are.  fin.rows is the observation slab of R = n_segments * fin.cap
+// "envs" (plane p at p * R ints); row j of segment s is env s * fin.cap + j of it.
+struct RowsParams : Params {
+    FinalSeg fin;
+    int64_t R;
+};
 
 __device__ __forceinline__ void load_env(Env &e, const uint4 *__restrict__ s, int64_t n, int64_t i) {
     uint32_t w[REC_WORDS];
@@ -99,10 +105,32 @@ __device__ __forceinline__ void observe(const Env &e, uint32_t *__restrict__ stg
     __syncthreads();                                                 // the rows are free for the next observation
 }
 
+// observe() for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` park their bytes at LDS
+// row `rank`, and the wave writes `keep` dense envs of every plane of the rows slab `o` (R envs) from env `row0` on: [row0, row0 + keep)
+// of each plane and nothing else.  Call with every lane of the wave.
+__device__ __forceinline__ void final_observe(const Env &e, uint32_t *__restrict__ stg, int32_t *__restrict__ o, int64_t R, int64_t row0, int keep, int rank,
+                                              bool mine) {
+    const int lane = (int)threadIdx.x;
+    if (mine) e.stage([&](int k, uint32_t v) { stg[rank * STG_WORDS + k] = v; });
+    __syncthreads();
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(stg);
+    store_plane<N_WAITING, LIM_WAITING, STG_WAITING>(b, o + (int64_t)P_WAITING * R + row0 * N_WAITING, keep * N_WAITING, lane);
+    store_plane<N_WAITERS, LIM_WAITERS, STG_WAITERS>(b, o + (int64_t)P_WAITERS * R + row0 * N_WAITERS, keep * N_WAITERS, lane);
+    store_plane<N_TABLES, LIM_TABLES, STG_OCC>(b, o + (int64_t)P_OCC * R + row0 * N_TABLES, keep * N_TABLES, lane);
+    store_plane<N_TABLES, LIM_TABLES, STG_DIRTY>(b, o + (int64_t)P_DIRTY * R + row0 * N_TABLES, keep * N_TABLES, lane);
+    store_plane<N_COOKING, LIM_COOKING, STG_COOKING>(b, o + (int64_t)P_COOKING * R + row0 * N_COOKING, keep * N_COOKING, lane);
+    store_plane<N_READY, LIM_READY, STG_READY>(b, o + (int64_t)P_READY * R + row0 * N_READY, keep * N_READY, lane);
+    if (mine) o[(int64_t)P_TIMESTEP * R + row0 + rank] = (int32_t)e.t;
+    __syncthreads();                                                 // the rows are free for the next observation
+}
+
 // k steps with the record in registers.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else the
-// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, (4, 10, 50, 10)[c], c).
-template <int MODE, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, (4, 10, 50, 10)[c], c).  With RowsParams (ROWS, a SAME_STEP
+// rollout) the terminal observations of the truncated envs go to the wave's segment of p.fin.
+template <int MODE, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     __shared__ uint32_t stg[BLOCK * STG_WORDS];
     constexpr int RUN = ROLLOUT ? 16 : 2;                            // ready generator words a lane holds (<= MT_PAD)
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -120,6 +148,7 @@ __device__ __forceinline__ void run(const Params &p) {
     if (GIVEN) next = acts[li];
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                           // ROWS: terminal rows the wave's segment has been handed
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -158,6 +187,13 @@ __device__ __forceinline__ void run(const Params &p) {
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal slab: every env of a wave with a truncated one
             if (p.final_obs && __ballot(trunc)) observe(e, stg, p.final_obs, p.n, i, live);
         }
+        if constexpr (ROWS) {                                        // ... of a rollout: the truncated envs only, compacted (lane_final_rows)
+            const int64_t row0 = (int64_t)blockIdx.x * p.fin.cap + (int64_t)fin_used;
+            int32_t *dst;
+            int keep, rank;
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, trunc, t, i, 0, dst, keep, rank), false))
+                final_observe(e, stg, static_cast<int32_t *>(p.fin.rows), p.R, row0, keep, rank, trunc && rank < keep);
+        }
         if (MODE != CGE_AUTORESET_DISABLED && reset_now) e.clear();
         if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, i, live);
         if (live) {
@@ -176,6 +212,9 @@ __device__ __forceinline__ void run(const Params &p) {
         store_env(e, p.state, p.n, i);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if (threadIdx.x == 0) p.fin.count[blockIdx.x] = (int32_t)fin_used;
+    }
 }
 
 template <int MODE>
@@ -183,6 +222,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, false
 
 template <int MODE, bool ACTIONS>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, true, ACTIONS>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_restaurant_rollout_final_obs)
+template <bool ACTIONS>
+__global__ __launch_bounds__(BLOCK) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, true, ACTIONS>(p); }
 
 // reset (mask) / initial state (init: an empty restaurant, cursor rewound) / rewind (after a re-seed) + obs
 __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int rewind) {
@@ -232,9 +275,10 @@ using namespace cge;
 
 struct cge_restaurant : LaneHandle {
     using Params = restaurant::Params;
+    using RowsParams = restaurant::RowsParams;
     cge_restaurant_config cfg{};
     static constexpr uint32_t snap_tag = 7u;
-    static constexpr const char *abi = "cge_restaurant", *kernel_ns = "cge::restaurant::";
+    static constexpr const char *abi = "cge_restaurant", *kernel_ns = "cge::restaurant::", *rows_ns = kernel_ns;
     static constexpr int block = restaurant::BLOCK, seed_kind = 0;
     Params params() const {
         Params p{};
@@ -248,6 +292,14 @@ struct cge_restaurant : LaneHandle {
     auto kernel(LaneKind kind) const {
         return kind == LANE_STEP ? restaurant::step_kernel<MODE>
                : kind == LANE_ROLLOUT_GIVEN ? restaurant::rollout_kernel<MODE, true> : restaurant::rollout_kernel<MODE, false>;
+    }
+    void fill_rows(RowsParams &p) const { p.R = (int64_t)lane_segments(this) * fin_cap; }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        hipLaunchKernelGGL(given ? restaurant::rollout_rows_kernel<true> : restaurant::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
+    }
+    // store_plane leads in to a 16-byte boundary with single ints: the rows slab has to hold whole ints
+    const char *rows_refusal() const {
+        return (reinterpret_cast<uintptr_t>(fin_rows) & 3u) != 0 ? "the registered terminal rows are not 4-byte aligned" : nullptr;
     }
     // an env's four action components are fetched as one 16-byte load
     static const char *actions_refusal(const int32_t *actions) {
@@ -296,6 +348,7 @@ int cge_restaurant_info(cge_restaurant *h, int32_t field_id, double *out, void *
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(restaurant, int32_t, 64)
 CGE_DEFINE_ERROR_COUNT(restaurant)
 CGE_DEFINE_SNAPSHOT(restaurant)
 

@@ -51,6 +51,12 @@ struct Params : LaneParams<void> {     // obs_step_stride in elements of the lay
     static constexpr bool terminates = true;   // terminated only: the reference never truncates (world_builder_env.py:150)
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
+// rollout_rows_kernel's: the other kernels' arguments stay as they are.  Dict: fin.rows is the observation slab of R = n_segments *
+// fin.cap "envs", its planes at the byte offsets below; row j of segment s is env s * fin.cap + j of it.  FLAT: plain rows [R, W].
+struct RowsParams : Params {
+    FinalSeg fin;
+    int64_t rows_off_res, rows_off_cap, rows_off_win;
+};
 
 // bit j = nibble j of w is non-zero
 __device__ __forceinline__ uint32_t nonzero_nibbles(uint32_t w) {
@@ -251,10 +257,62 @@ __device__ __forceinline__ void write_obs(const Env &e, const Params &p, void *b
     lds_barrier();                                                   // the tile is free again
 }
 
+// write_obs for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` stage at column `rank`,
+// and the wave writes `keep` dense rows from row `row0` of the rows output on.  FLAT: the dword path of write_obs.  Dict: the grid run
+// is bytes [row0 * GG, (row0 + keep) * GG) of the slab, which starts and ends wherever that puts it — its whole dwords are composed from
+// the tile, the up-to-three bytes before the first and after the last are byte stores, so nothing outside the run is written; the
+// three small planes are stored by the kept lanes.  Call with all lanes of the wave.
+template <bool FLAT>
+__device__ __forceinline__ void write_final_rows(const Env &e, const RowsParams &p, int64_t row0, uint32_t keep, uint32_t rank, bool mine, uint32_t lane,
+                                                 uint32_t *__restrict__ tile, float *__restrict__ ex) {
+    if (mine) stage(e, tile, ex, rank, p.RS, FLAT);
+    lds_barrier();
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    const uint32_t GG = (uint32_t)p.GG, RSB = 4u * (uint32_t)p.RS;
+    if (FLAT) {
+        const uint32_t W = (uint32_t)p.W, total = keep * W;
+        float *dst = static_cast<float *>(p.fin.rows) + row0 * (int64_t)W;
+#pragma unroll 2
+        for (uint32_t q = lane; q < total; q += 64u) {
+            const uint32_t r = __umulhi(q, p.magic_w), c = q - r * W;
+            dst[q] = c < GG ? (float)tb[r * RSB + c] : ex[r * NEXTRA + (c - GG)];
+        }
+    } else {
+        uint8_t *slab = static_cast<uint8_t *>(p.fin.rows);
+        uint8_t *run = slab + row0 * (int64_t)GG;                                      // the slab is 16-byte aligned; the run is not
+        const uint32_t nbytes = keep * GG;
+        auto byte_at = [&](uint32_t b) -> uint32_t {                                   // byte b of the run: cell b % GG of tile column b / GG
+            const uint32_t r = __umulhi(b, p.magic_gg), c = b - r * GG;
+            return (uint32_t)tb[r * RSB + c];
+        };
+        const uint32_t lead = (4u - (uint32_t)(reinterpret_cast<uintptr_t>(run) & 3u)) & 3u, head = lead < nbytes ? lead : nbytes;
+        if (lane < head) run[lane] = (uint8_t)byte_at(lane);
+        const uint32_t ndw = (nbytes - head) >> 2;
+        uint32_t *dst = reinterpret_cast<uint32_t *>(run + head);
+#pragma unroll 1
+        for (uint32_t q = lane; q < ndw; q += 64u) {
+            const uint32_t b = head + 4u * q;
+            dst[q] = byte_at(b) | (byte_at(b + 1u) << 8) | (byte_at(b + 2u) << 16) | (byte_at(b + 3u) << 24);
+        }
+        const uint32_t b = head + 4u * ndw + lane;
+        if (b < nbytes) run[b] = (uint8_t)byte_at(b);
+        if (mine) {
+            const int64_t i = row0 + rank;
+            reinterpret_cast<float4 *>(slab + p.rows_off_res)[i] = make_float4((float)e.food, (float)e.wood, (float)e.stone, (float)e.pop);
+            reinterpret_cast<float *>(slab + p.rows_off_cap)[i] = (float)e.capacity();
+            reinterpret_cast<int32_t *>(slab + p.rows_off_win)[i] = (int32_t)e.win;
+        }
+    }
+    lds_barrier();                                                   // the tile is free again
+}
+
 // k steps with the record in registers.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else the
-// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 5, 0).
-template <int MODE, bool FLAT, bool ROLLOUT, bool GIVEN>
-__device__ __forceinline__ void run(const Params &p) {
+// counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 5, 0).  With RowsParams (ROWS, a SAME_STEP rollout) the terminal
+// observations of the terminated envs go to the wave's segment of p.fin.
+template <int MODE, bool FLAT, bool ROLLOUT, bool GIVEN, class P = Params>
+__device__ __forceinline__ void run(const P &p) {
+    constexpr bool ROWS = std::is_same<P, RowsParams>::value;
+    static_assert(!ROWS || (ROLLOUT && MODE == CGE_AUTORESET_SAME_STEP), "terminal rows: fused SAME_STEP rollouts");
     __shared__ __attribute__((aligned(16))) uint32_t tile[BLOCK * MAX_RS];
     __shared__ float ex[BLOCK * NEXTRA];
     const uint32_t lane = threadIdx.x;
@@ -269,6 +327,7 @@ __device__ __forceinline__ void run(const Params &p) {
     const uint64_t key = GIVEN ? 0 : hash_env_key(p.a_seed, (uint64_t)(p.env0 + li));
     double rsum = 0.0;
     int32_t dcount = 0;
+    uint32_t fin_used = 0;                                           // ROWS: terminal rows the wave's segment has been handed
     const int ksteps = ROLLOUT ? p.k_steps : 1;
 #pragma unroll 1
     for (int t = 0; t < ksteps; ++t) {
@@ -292,6 +351,13 @@ __device__ __forceinline__ void run(const Params &p) {
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {          // the terminal rows; a wave with none writes nothing
             if (p.final_obs && __ballot(term)) write_obs<FLAT>(e, p, p.final_obs, row0, nrows, lane, live, tile, ex);
         }
+        if constexpr (ROWS) {                                       // ... of a rollout: the terminated envs only, compacted (lane_final_rows)
+            const int64_t first = (int64_t)blockIdx.x * p.fin.cap + (int64_t)fin_used;
+            uint8_t *dst;
+            int keep, rank;
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, 0, dst, keep, rank), false))
+                write_final_rows<FLAT>(e, p, first, (uint32_t)keep, (uint32_t)rank, term && rank < keep, lane, tile, ex);
+        }
         if (MODE != CGE_AUTORESET_DISABLED && reset_now) e.clear();
         if (lane_obs_due<ROLLOUT>(p, t, ksteps))
             write_obs<FLAT>(e, p, static_cast<char *>(p.obs) + (int64_t)t * step_bytes, row0, nrows, lane, live, tile, ex);
@@ -311,6 +377,9 @@ __device__ __forceinline__ void run(const Params &p) {
         e.store(p.state, p.ret, p.n, i);
         if (ROLLOUT) lane_sums(p, i, rsum, dcount);
     }
+    if constexpr (ROWS) {
+        if (lane == 0) p.fin.count[blockIdx.x] = (int32_t)fin_used;
+    }
 }
 
 template <int MODE, bool FLAT>
@@ -318,6 +387,12 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(Params p) { run<MODE, FLAT,
 
 template <int MODE, bool FLAT, bool ACTIONS>
 __global__ __launch_bounds__(BLOCK) void rollout_kernel(Params p) { run<MODE, FLAT, true, ACTIONS>(p); }
+
+// the SAME_STEP rollout while terminal rows are registered (cge_rows_world_builder_rollout_final_obs).  The register budget is the
+// sibling rollout_kernel's waves per SIMD, stated: left alone the hashed FLAT instance takes 170 registers, two over the 168 of three
+// waves (the sibling: 161); held to them it needs no scratch.
+template <bool FLAT, bool ACTIONS>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FLAT ? 3 : 2))) void rollout_rows_kernel(RowsParams p) { run<CGE_AUTORESET_SAME_STEP, FLAT, true, ACTIONS>(p); }
 
 // reset (mask, or all) / initial state (init: the reset state, cursor rewound) / rewind (after a re-seed) + obs.  Draws nothing.
 template <bool FLAT>
@@ -370,9 +445,10 @@ static inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 struct cge_world_builder : LaneHandle {
     using Params = wb::Params;
+    using RowsParams = wb::RowsParams;
     cge_world_builder_config cfg{};
     int32_t *ret = nullptr;
-    static constexpr const char *kernel_ns = "cge::wb::";
+    static constexpr const char *kernel_ns = "cge::wb::", *rows_ns = kernel_ns;
     static constexpr int block = wb::BLOCK, seed_kind = 1;
     int64_t cells() const { return (int64_t)cfg.grid_size * cfg.grid_size; }
     int64_t off_res() const { return align16(n * cells()); }
@@ -406,6 +482,22 @@ struct cge_world_builder : LaneHandle {
     template <int MODE>
     auto kernel(LaneKind kind) const { return cfg.flatten_obs ? kernel_of<MODE, true>(kind) : kernel_of<MODE, false>(kind); }
     const char *layout_arg() const { return cfg.flatten_obs ? ", true" : ", false"; }
+    // the Dict slab of compacted rows: this type's slab layout for R = segments * capacity envs
+    void fill_rows(RowsParams &p) const {
+        const int64_t R = (int64_t)lane_segments(this) * fin_cap;
+        p.rows_off_res = align16(R * cells());
+        p.rows_off_cap = p.rows_off_res + 16 * R;
+        p.rows_off_win = align16(p.rows_off_cap + 4 * R);
+    }
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
+        auto k = cfg.flatten_obs ? (given ? wb::rollout_rows_kernel<true, true> : wb::rollout_rows_kernel<true, false>)
+                                 : (given ? wb::rollout_rows_kernel<false, true> : wb::rollout_rows_kernel<false, false>);
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(block), 0, s, p);
+    }
+    const char *rows_refusal() const {
+        if (aligned(fin_rows)) return nullptr;
+        return cfg.flatten_obs ? "the registered terminal rows are not 4-byte aligned" : "the registered terminal rows are not 16-byte aligned";
+    }
     hipError_t init() {
         CGE_HIP(alloc(state, (size_t)wb::COLS * n * sizeof(uint4), true, true));
         CGE_HIP(alloc(ret, (size_t)n * sizeof(int32_t), true, true));
@@ -511,6 +603,7 @@ int cge_world_builder_info(cge_world_builder *h, int32_t field_id, int32_t index
     return launched(h);
 }
 
+CGE_DEFINE_ROWS_FINAL_OBS(world_builder, void, 64)
 CGE_DEFINE_ERROR_COUNT(world_builder)
 
 CGE_DEFINE_RECORDS(world_builder)

@@ -64,7 +64,9 @@ class RestaurantVectorEnv(SlabVectorEnv):
     cge_hash_action(action_seed, env_index0 + i, t0 + t, (4, 10, 50, 10)[c], c)), the packed int32 [k, N, 4] or the mapping form.
     Returns (obs, reward_sum, done_count) with obs a dict of views [k, N, ...] if trajectory else the last step's [N, ...]; with
     per_step=True (obs, reward[k, N], truncated[k, N], reward_sum, done_count) — the outputs of k step() calls (a SAME_STEP trajectory
-    holds the reset observation at a truncated step, as step()'s `obs` does; the terminal rows of a fused rollout are not delivered)."""
+    holds the reset observation at a truncated step, as step()'s `obs` does; the terminal observations of a fused rollout go to a side
+    output once `collect_final_obs()` has registered one: `final_obs()` returns them as a dict of per-key tensors [m, ...] with their
+    steps and envs, `final_obs_dropped()` what did not fit; segments of 64 envs)."""
 
     _abi = "cge_restaurant"
     INFO_FIELDS = INFO_FIELDS
@@ -86,6 +88,9 @@ class RestaurantVectorEnv(SlabVectorEnv):
         if status == -1 and not 1 <= self.max_episode_steps <= MAX_EPISODE_STEPS:
             return ValueError(f"max_episode_steps must be in 1..{MAX_EPISODE_STEPS}, got {self.max_episode_steps}")
         return None
+
+    def _rows_layout(self, num_rows):
+        return packed_planes(PLANES, num_rows)
 
     # ------------------------------------------------------------------ actions
     def _device_actions(self, actions, k=None):

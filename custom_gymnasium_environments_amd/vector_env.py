@@ -127,7 +127,7 @@ class DeviceVectorEnv(VectorEnvBase):
     # ------------------------------------------------------------------ native helpers
     def _fn(self, name):
         if name in ("rollout_final_obs", "final_obs_segment") and not hasattr(self._lib, f"{self._abi}_{name}"):
-            return getattr(self._lib, f"cge_rows_{self._abi[4:]}_{name}")      # emergency, space station, farm: cge_rows_<env>_* (cge_amd.h)
+            return getattr(self._lib, f"cge_rows_{self._abi[4:]}_{name}")      # the lane-per-env types but airline: cge_rows_<env>_* (cge_amd.h)
         return getattr(self._lib, f"{self._abi}_{name}")
 
     def _check(self, status, what):

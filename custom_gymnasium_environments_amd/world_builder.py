@@ -66,8 +66,12 @@ class WorldBuilderVectorEnv(SlabVectorEnv):
     SnakeVectorEnv and BusVectorEnv do.  reset() draws nothing.
 
     rollout(k): k fused step()s in one launch (the record stays in registers).  actions: None -> counter-hash actions
-    (cge_hash_action(action_seed, env_index0 + i, t0 + t, 5, 0)) or int32 [k, N].  get_state() / set_state(): canonical per-env
-    records holding NumPy's own (key, pos) generator state (include/cge_amd.h)."""
+    (cge_hash_action(action_seed, env_index0 + i, t0 + t, 5, 0)) or int32 [k, N].  A SAME_STEP trajectory holds the reset observation at
+    a terminated step, as step()'s `obs` does; the terminal observations of a fused rollout go to a side output once
+    `collect_final_obs()` has registered one: `final_obs()` returns (rows, step, env) with rows a dict of per-key tensors [m, G, G],
+    [m, 4], [m, 1], [m, 1] — float32 rows [m, G*G + 6] with `flatten_obs=True` — and `final_obs_dropped()` what did not fit (segments
+    of 64 envs).  get_state() / set_state(): canonical per-env records holding NumPy's own (key, pos) generator state
+    (include/cge_amd.h)."""
 
     _abi = "cge_world_builder"
     INFO_FIELDS = INFO_FIELDS
@@ -95,6 +99,9 @@ class WorldBuilderVectorEnv(SlabVectorEnv):
         if status == -1 and not MIN_GRID <= self.grid_size <= MAX_GRID:
             return ValueError(f"grid_size must be in {MIN_GRID}..{MAX_GRID}, got {self.grid_size}")
         return None
+
+    def _rows_layout(self, num_rows):
+        return plane_table(num_rows, self.grid_size)
 
     # ------------------------------------------------------------------ extras
     def reference_info(self):

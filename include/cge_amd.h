@@ -25,6 +25,12 @@
  *                       first min(count, seg_capacity) of them, in step order, to the segment's rows; the surplus is dropped (the count
  *                       still says so).  All NULL unregisters.  NEXT_STEP / DISABLED rollouts deliver nothing: slot t of their
  *                       trajectory IS the terminal observation.
+ *                       A type whose observation is a key-major SLAB (bus, restaurant, world builder's Dict) has no [rows, row] array
+ *                       to compact into: with R = n_segments * seg_capacity its rows_out is the type's ordinary observation slab for
+ *                       R envs — bus and restaurant: int32 planes packed, plane p at p * R ints; world builder's Dict: its uint8 slab of
+ *                       typed planes for R envs, each plane at a multiple of 16 bytes — and row j of segment g is "env"
+ *                       g * seg_capacity + j of that slab.  A row write touches the bytes of its own row in each plane and no others.
+ *                       index_out and count_out are as above.
  *   <env>_info     <->  the `info` dicts        snake_env.py:63,117
  *   <env>_episode_stats <-> the per-episode return / length that the reference's training scripts read back from their
  *                       vector-env wrapper as episode_return_mean / episode_len_mean
@@ -629,6 +635,12 @@ int cge_bus_step(cge_bus *h, const int32_t *actions, int32_t *obs_out, float *re
 int cge_bus_rollout(cge_bus *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
                     int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
                     int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * rows_out is a slab: CGE_BUS_OBS_INTS * R ints for R = n_segments * seg_capacity rows, plane p at p * R ints.  While rows are registered
+ * a SAME_STEP rollout runs its rollout_rows_kernel instance (64-lane workgroups); rows_out must be 16-byte aligned, or cge_bus_rollout
+ * refuses it.  The two are named cge_rows_bus_*: they stand beside the type's surface cge_bus_*, which is as it was */
+int cge_rows_bus_rollout_final_obs(cge_bus *h, int32_t *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_bus_final_obs_segment(const cge_bus *h);
 /* _get_info :339-350 */
 int cge_bus_info(cge_bus *h, int32_t field_id, int32_t index, int32_t *out, void *stream);
 /* env-steps refused for an invalid action since the last call; synchronises */
@@ -713,6 +725,12 @@ int cge_restaurant_step(cge_restaurant *h, const int32_t *actions, int32_t *obs_
 int cge_restaurant_rollout(cge_restaurant *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, int32_t *obs_out,
                            int64_t obs_step_stride, float *reward_traj_out, uint8_t *truncated_traj_out, double *reward_sum_out,
                            int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * rows_out is a slab: CGE_RESTAURANT_OBS_INTS * R ints for R = n_segments * seg_capacity rows, plane p at p * R ints.  While rows are
+ * registered a SAME_STEP rollout runs its rollout_rows_kernel instance; rows_out must be 4-byte aligned, or cge_restaurant_rollout
+ * refuses it.  The two are named cge_rows_restaurant_*: they stand beside the type's surface cge_restaurant_*, which is as it was */
+int cge_rows_restaurant_rollout_final_obs(cge_restaurant *h, int32_t *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_restaurant_final_obs_segment(const cge_restaurant *h);
 /* _get_info :478-494 */
 int cge_restaurant_info(cge_restaurant *h, int32_t field_id, double *out, void *stream);
 /* env-steps whose action had a component out of range since the last call; synchronises */
@@ -1129,6 +1147,14 @@ int cge_world_builder_step(cge_world_builder *h, const int32_t *actions, void *o
 int cge_world_builder_rollout(cge_world_builder *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, void *obs_out,
                               int64_t obs_step_stride, float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out,
                               int32_t *done_count_out, void *stream);
+/* terminal observations of SAME_STEP rollouts, compacted per segment of 64 envs: see <env>_rollout_final_obs at the top of this file.
+ * With R = n_segments * seg_capacity rows, rows_out is the Dict slab for R envs (grid int8 [R, G, G] at byte 0 | resources f32 [R, 4] |
+ * population_capacity f32 [R, 1] | win_steps i32 [R, 1], each plane at the next multiple of 16 bytes), or with flatten_obs float32 rows
+ * [R, G*G + 6].  While rows are registered a SAME_STEP rollout runs its rollout_rows_kernel instance; rows_out must be 16-byte (Dict) /
+ * 4-byte (flat) aligned, or cge_world_builder_rollout refuses it.  The two are named cge_rows_world_builder_*: they stand beside the
+ * type's surface cge_world_builder_*, which is as it was */
+int cge_rows_world_builder_rollout_final_obs(cge_world_builder *h, void *rows_out, int64_t *index_out, int64_t seg_capacity, int32_t *count_out);
+int64_t cge_rows_world_builder_final_obs_segment(const cge_world_builder *h);
 /* _get_info :218-232 */
 int cge_world_builder_info(cge_world_builder *h, int32_t field_id, int32_t index, int32_t *out, void *stream);
 /* env-steps refused for an invalid action since the last call; synchronises */

@@ -1,0 +1,448 @@
+"""Terminal rows of fused SAME_STEP rollouts for the three types with a `Dict` observation — bus, world builder (both layouts) and
+restaurant (rollout_rows_kernel): `collect_final_obs()` + `rollout()` deliver, compacted per wave of 64 envs, the
+observation the reference's step() returned when an episode ended, as a dict of per-key tensors read from a rows SLAB (the type's own
+observation slab for R = segments * capacity envs), bit for bit and in (step, env) order, while slot t of the trajectory holds the reset
+observation as before.
+
+Every case runs 64 * 2 + 37 = 165 envs: two full waves and a ragged one.  The fixture cases tile a fixture (env i replays fixture env
+i % m: its seed, its actions) and compute what they expect from the fixture alone; the hashed cases compare with a twin stepped by
+step(), and world builder's with tests/world_builder_model.py as well.  A flat world-builder observation is handled as a dict with
+the one key "flat"."""
+import numpy as np
+import pytest
+import torch
+
+import bus_model as bm
+import restaurant_model as rm
+import world_builder_model as wm
+from conftest import golden
+from custom_gymnasium_environments_amd._slab import plane_views
+
+pytestmark = pytest.mark.gpu
+
+N, SEG = 64 * 2 + 37, 64
+NSEG = -(-N // SEG)
+WB_DTYPES = {"grid": torch.int8, "resources": torch.float32, "population_capacity": torch.float32, "win_steps": torch.int32}
+
+
+@pytest.fixture(scope="module")
+def cge():
+    import custom_gymnasium_environments_amd as m
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    m.native_lib()
+    return m
+
+
+def as_dict(x):
+    return x if isinstance(x, dict) else {"flat": x}
+
+
+def host(x):
+    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in as_dict(x).items()}
+
+
+def same(dev, ref, what):
+    dev, ref = host(dev), host(ref)
+    assert list(dev) == list(ref), what
+    for k in ref:
+        assert dev[k].dtype == ref[k].dtype and dev[k].shape == ref[k].shape, (what, k, dev[k].dtype, dev[k].shape, ref[k].dtype, ref[k].shape)
+        assert np.array_equal(dev[k].view(np.uint8), np.ascontiguousarray(ref[k]).view(np.uint8)), (what, k)
+
+
+def take(x, *idx):
+    return {k: v[idx] for k, v in as_dict(x).items()}
+
+
+def wb_pieces(z, prefix, flat):
+    """a world-builder fixture's recorded observation pieces in the reference's dtypes and shapes (as tests/test_world_builder_gpu.py)"""
+    if flat:
+        return {"flat": z[prefix + "flat"]}
+    return {"grid": z[prefix + "grid"], "resources": z[prefix + "resources"].astype(np.float32),
+            "population_capacity": z[prefix + "population_capacity"][..., None].astype(np.float32),
+            "win_steps": z[prefix + "win_steps"][..., None].astype(np.int32)}
+
+
+def int_pieces(keys):
+    return lambda z, prefix, flat: {k: z[prefix + k].astype(np.int32) for k in keys}
+
+
+# case -> (env class, fixture, the fixture's flag, constructor arguments read from the fixture, its pieces, steps replayed)
+CASES = {
+    "bus_short": ("BusVectorEnv", "bus_short.npz", "truncated", {"max_timesteps": "max_timesteps"}, int_pieces(bm.KEYS), None),
+    "restaurant_short": ("RestaurantVectorEnv", "restaurant_short.npz", "truncated", {"max_episode_steps": "max_episode_steps"}, int_pieces(rm.KEYS), None),
+    "wb_g2": ("WorldBuilderVectorEnv", "wb_g2.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, None),
+    "wb_builder": ("WorldBuilderVectorEnv", "wb_builder.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, 160),
+    "wb_flat": ("WorldBuilderVectorEnv", "wb_flat.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, None),
+}
+
+
+class Tiled:
+    """A fixture tiled over N envs: what a SAME_STEP replay of it has to deliver, from the fixture alone."""
+
+    def __init__(self, case):
+        self.case = case
+        self.cls, name, flag, from_fixture, pieces, steps = CASES[case]
+        z = golden(name)
+        self.m = z["reward"].shape[0]
+        self.T = T = z["reward"].shape[1] if steps is None else steps
+        self.kw = {k: (bool(z[v]) if z[v].dtype == bool else int(z[v])) for k, v in from_fixture.items()}
+        flat = bool(self.kw.get("flatten_obs"))
+        self.src = np.arange(N) % self.m                                  # env i replays fixture env src[i]
+        self.seeds = int(z["seed0"]) + self.src
+        self.actions = np.ascontiguousarray(np.moveaxis(z["actions"][:, :T], 0, 1)[:, self.src], dtype=np.int32)   # [T, N(, 4)]
+        self.term = z[flag][:, :T].T[:, self.src].astype(bool)            # [T, N]
+        final = {k: v[:, :T] for k, v in pieces(z, "obs_", flat).items()}   # [m, T, ...]: what the reference's step() returned
+        resets = pieces(z, "reset_", flat)
+        traj = {k: v.copy() for k, v in final.items()}                    # slot t: the recorded observation, or the reset one at an end
+        ends = 0
+        for j, (i, t) in enumerate(z["reset_index"]):
+            if t < T:
+                assert z[flag][i, t]
+                ends += 1
+                for k in traj:
+                    traj[k][i, t] = resets[k][j]
+        assert ends == int(z[flag][:, :T].sum()) > 0, "every recorded end has its reset observation"
+        self.final = {k: np.moveaxis(v, 0, 1)[:, self.src] for k, v in final.items()}    # [T, N, ...]: valid where term
+        self.traj = {k: np.moveaxis(v, 0, 1)[:, self.src] for k, v in traj.items()}
+
+    def make(self, cge, mode="SameStep"):
+        env = getattr(cge, self.cls)(N, autoreset_mode=mode, **self.kw)
+        env.reset(seed=self.seeds)
+        return env
+
+    def expected(self):
+        t, i = np.nonzero(self.term)                                     # row-major: by step, then by env
+        return take(self.final, t, i), t, i
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_rows_equal_the_recorded_terminal_observations(cge, case):
+    f = Tiled(case)
+    wave_ends = np.array([f.term[:, s:s + SEG].sum() for s in range(0, N, SEG)])
+    assert (wave_ends > 0).all(), "every wave, the ragged one included, sees an end"
+    if case in ("bus_short", "restaurant_short"):
+        assert f.term[:, :SEG].all(1).any() and f.term[:, SEG:2 * SEG].all(1).any(), "all 64 lanes of a wave end at one step"
+    env = f.make(cge)
+    env.collect_final_obs(rows_per_env=int(f.term.sum(0).max()))
+    assert env.final_obs_segment == SEG
+    traj, rt, ft, rs, dc = env.rollout(f.T, actions=torch.from_numpy(f.actions).cuda(), trajectory=True, per_step=True)
+    assert "rollout_rows_kernel" in env.last_kernel() and env.last_kernel().endswith("true>")
+    assert np.array_equal(ft.cpu().numpy(), f.term), "flags"
+    rows, step, who = env.final_obs()
+    erows, et, ei = f.expected()
+    assert np.array_equal(step.cpu().numpy(), et) and np.array_equal(who.cpu().numpy(), ei), (case, "order")
+    same(rows, erows, (case, "rows"))
+    assert env.final_obs_dropped() == 0
+    for k, v in as_dict(traj).items():                                    # key by key: restaurant's trajectory is a quarter of a gigabyte
+        same({k: v}, {k: f.traj[k]}, (case, "trajectory"))
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- hashed rollouts
+A_SEED, ENV0, T0 = 11, 1000, 5
+WB_K = 24
+
+
+class Hashed:
+    """A kind of env in the state the hashed tests start from, twice over (env and twin), and the actions of a hashed rollout."""
+
+    def __init__(self, kind):
+        self.kind = kind
+        self.type = kind.split("-")[0]
+        if self.type == "wb":
+            _, g, layout = kind.split("-")
+            self.G, self.flat = int(g), layout == "flat"
+            self.cls, self.kw, self.k, self.model = "WorldBuilderVectorEnv", {"grid_size": self.G, "flatten_obs": self.flat}, WB_K, wm
+        elif self.type == "bus":
+            self.cls, self.kw, self.k, self.model = "BusVectorEnv", {"max_timesteps": 5}, 13, bm
+        else:
+            self.cls, self.kw, self.k, self.model = "RestaurantVectorEnv", {"max_episode_steps": 5}, 13, rm
+
+    def actions(self, k, t0=T0, a_seed=A_SEED):
+        return torch.from_numpy(np.ascontiguousarray(self.model.hash_actions(a_seed, k, N, t0=t0, env0=ENV0), dtype=np.int32)).cuda()
+
+    def make(self, cge, mode="SameStep", **kw):
+        env = getattr(cge, self.cls)(N, autoreset_mode=mode, env_index0=ENV0, **self.kw, **kw)
+        env.reset(seed=3)
+        if self.type != "wb":                                             # stagger the episodes: the ends fall on different steps for different lanes
+            pre = self.actions(3, t0=0, a_seed=2)
+            for s in range(3):
+                env.step(pre[s])
+                env.reset(options={"reset_mask": np.arange(N) % 4 == s})
+        return env
+
+
+def steps_of_twin(twin, acts):
+    """k step() calls -> per step (obs, reward, flag, final_obs): all on the device"""
+    out = []
+    for a in acts:
+        ob, r, te, tr, info = twin.step(a)
+        out.append((take(ob, ...), r.clone(), (te | tr).clone(), take(info["final_obs"], ...), info["_final_obs"].clone()))
+    return out
+
+
+def check_against_twin(env, twin, acts, traj, rt, ft, what, cap=None):
+    """rows against infos["final_obs"] where _final_obs, then order and trajectory; with `cap`, a segment's first cap rows.  Returns the flags [k, N]."""
+    rows, step, who = env.final_obs()
+    rows = as_dict(rows)
+    j, used, flags = 0, np.zeros(NSEG, np.int64), []
+    for t, (ob, r, done, fin, has) in enumerate(steps_of_twin(twin, acts)):
+        assert torch.equal(done, has) and torch.equal(r, rt[t]) and torch.equal(done, ft[t]), (what, t)
+        for k, v in as_dict(traj).items():
+            assert torch.equal(ob[k], v[t]), (what, t, k, "trajectory")
+        d = torch.nonzero(done).flatten().cpu().numpy()
+        flags.append(done.cpu().numpy())
+        if cap is not None:                                               # the rows a full segment still takes, in lane order
+            kept = []
+            for i in d:
+                if used[i // SEG] < cap:
+                    kept.append(i)
+                used[i // SEG] += 1
+            d = np.array(kept, np.int64)
+        m = d.size
+        if m:
+            dd = torch.from_numpy(d).cuda()
+            assert torch.equal(step[j:j + m], torch.full((m,), t, device="cuda")) and torch.equal(who[j:j + m], dd), (what, t, "order")
+            for k in rows:
+                assert rows[k].dtype == fin[k].dtype and torch.equal(rows[k][j:j + m].view(torch.uint8), fin[k][dd].contiguous().view(torch.uint8)), (what, t, k)
+            j += m
+    assert j == step.shape[0] == who.shape[0] and all(v.shape[0] == j for v in rows.values()), (what, "row count")
+    flags = np.array(flags)
+    if cap is not None:
+        assert env.final_obs_dropped() == int(sum(max(0, int(flags[:, s:s + SEG].sum()) - cap) for s in range(0, N, SEG))), (what, "dropped")
+    return flags
+
+
+WB_KINDS = [f"wb-{g}-{layout}" for g in (2, 3, 7, 10) for layout in ("dict", "flat")]
+
+
+@pytest.fixture(scope="module")
+def wb_model_run():
+    """grid size -> (terminated [k, N], the model's `final` per step) of the hashed world-builder case, computed once on the CPU"""
+    cache = {}
+
+    def run(G):
+        if G not in cache:
+            m = wm.WorldBuilderModel(3 + ENV0 + np.arange(N), G, wm.SAME_STEP, False)
+            acts = wm.hash_actions(A_SEED, WB_K, N, t0=T0, env0=ENV0)
+            term, final = [], []
+            for t in range(WB_K):
+                _, _, te, fin = m.step(acts[t])
+                term.append(te)
+                final.append(fin)
+            term = np.array(term)
+            per_wave = [int(term[:, s:s + SEG].sum()) for s in range(0, N, SEG)]
+            assert term[4:].any(1).all() and not term[:4].any() and max(per_wave) < 4 * SEG and min(per_wave) > 2 * SEG and term.sum(0).max() == 4
+            assert term[8, 2 * SEG:].sum() == 1 and (G == 2 or term[8, SEG:2 * SEG].sum() == 1), "step 8: a single finishing lane in a wave"
+            cache[G] = (term, final)
+        return cache[G]
+
+    return run
+
+
+@pytest.mark.parametrize("kind", WB_KINDS + ["bus", "restaurant"])
+def test_hashed_rollout_with_rows_equals_k_step_calls(cge, wb_model_run, kind):
+    h = Hashed(kind)
+    env, twin = h.make(cge), h.make(cge)
+    env.collect_final_obs(rows_per_env=4)
+    traj, rt, ft, rs, dc = env.rollout(h.k, action_seed=A_SEED, t0=T0, trajectory=True, per_step=True)
+    name = env.last_kernel()
+    assert name == {"wb": f"cge::wb::rollout_rows_kernel<{str(getattr(h, 'flat', False)).lower()}, false>"}.get(h.type, f"cge::{h.type}::rollout_rows_kernel<false>")
+    assert env.final_obs_dropped() == 0
+    flags = check_against_twin(env, twin, h.actions(h.k), traj, rt, ft, kind)
+    rows, step, who = env.final_obs()
+    if h.type == "wb":
+        term, final = wb_model_run(h.G)
+        assert np.array_equal(flags, term)
+        t, i = np.nonzero(term)
+        want = {k: np.stack([final[a][k][b] for a, b in zip(t, i)]) for k in wm.KEYS}
+        same(rows, {"flat": wm.flatten(want)} if h.flat else want, (kind, "model"))
+        if not h.flat:
+            assert list(rows) == list(wm.KEYS) and all(rows[k].dtype == WB_DTYPES[k] for k in rows)
+            assert tuple(rows["grid"].shape[1:]) == (h.G, h.G) and tuple(rows["resources"].shape[1:]) == (4,) and tuple(rows["win_steps"].shape[1:]) == (1,)
+    else:
+        full = flags[:, :2 * SEG].reshape(h.k, 2, SEG)
+        assert not full.all(2).any(), "no step ends all lanes of a full wave"
+        assert flags.any(0).all() and flags.any(1).sum() >= 4, "every env ends at least once, on different steps"
+        keys = bm.KEY_SHAPES if h.type == "bus" else rm.KEY_SHAPES
+        assert all(rows[k].dtype == torch.int32 and tuple(rows[k].shape[1:]) == tuple(keys[k]) for k in keys) and list(rows) == list(keys)
+    env.close(); twin.close()
+
+
+# ------------------------------------------------------------------------------------------------------ nothing else is written
+GUARD = 64
+
+
+def register_guarded(env, fill):
+    """Re-register the rows slab inside a larger allocation filled with `fill` bytes: GUARD bytes in front, GUARD behind.  -> the allocation"""
+    rows, index, count, cap = env._fin
+    nbytes = rows.numel() * rows.element_size()
+    big = torch.full((GUARD + nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda")
+    assert big.data_ptr() % 16 == 0
+    inner = big[GUARD:GUARD + nbytes].view(rows.dtype)
+    assert env._fn("rollout_final_obs")(env._h, inner.data_ptr(), index.data_ptr(), cap, count.data_ptr()) == 0
+    env._fin = (inner, index, count, cap)
+    return big
+
+
+@pytest.mark.parametrize("kind", ["wb-3-dict", "restaurant"])
+def test_nothing_but_the_delivered_rows_is_written(cge, kind):
+    """Two identical runs over slabs filled with 0x7F and 0x80: outside the delivered rows of every plane (unused capacity, padding between
+    planes, the bytes around the slab) each keeps its fill; inside, the two agree, so every byte there was written."""
+    h = Hashed(kind)
+    slabs = []
+    for fill in (0x7F, 0x80):
+        env = h.make(cge)
+        env.collect_final_obs(rows_per_env=4)
+        big = register_guarded(env, fill)
+        env.rollout(h.k, action_seed=A_SEED, t0=T0)
+        count, cap, planes = env._fin[2].cpu().numpy(), env._fin[3], env._fin_planes
+        assert env.final_obs_dropped() == 0 and count.min() > 0
+        inside = np.zeros(big.numel(), bool)
+        item = env._fin[0].element_size()
+        for key, shape, dtype, off in planes:
+            row = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            for s in range(NSEG):
+                a = GUARD + off * item + s * cap * row
+                inside[a:a + int(count[s]) * row] = True
+        got = big.cpu().numpy()
+        assert (got[~inside] == fill).all(), (kind, fill, "a byte outside the delivered rows was written", np.flatnonzero((got != fill) & ~inside)[:8])
+        assert inside.sum() > 0 and (~inside[GUARD:-GUARD]).sum() > 0
+        slabs.append((got, inside))
+        env.close()
+    (a, ia), (b, ib) = slabs
+    assert np.array_equal(ia, ib) and np.array_equal(a[ia], b[ib]), (kind, "a byte inside the delivered rows was not written")
+
+
+# ------------------------------------------------------------------------------------------------------------------ capacity
+@pytest.mark.parametrize("kind", ["wb-3-dict", "wb-7-flat"])
+def test_a_full_segment_keeps_its_first_rows_and_counts_the_rest(cge, wb_model_run, kind):
+    h = Hashed(kind)
+    env, twin = h.make(cge), h.make(cge)
+    env.collect_final_obs(rows_per_env=2)
+    cap = env._fin[3]
+    assert cap == 2 * SEG
+    traj, rt, ft, rs, dc = env.rollout(h.k, action_seed=A_SEED, t0=T0, trajectory=True, per_step=True)
+    term = wb_model_run(h.G)[0]
+    surplus = [int(term[:, s:s + SEG].sum()) - cap for s in range(0, N, SEG)]
+    assert min(surplus) > 0, "all three waves overflow"
+    flags = check_against_twin(env, twin, h.actions(h.k), traj, rt, ft, kind, cap=cap)
+    assert np.array_equal(flags, term) and env.final_obs_dropped() == sum(surplus)
+    assert env.final_obs()[1].shape[0] == NSEG * cap
+    env.close(); twin.close()
+
+
+# ------------------------------------------------------------------------------------------------- calls, modes and refusals
+@pytest.mark.parametrize("kind", ["wb-3-dict", "wb-10-flat", "bus", "restaurant"])
+def test_each_call_reports_its_own_rows(cge, kind):
+    h = Hashed(kind)
+    env, twin = h.make(cge), h.make(cge)
+    env.collect_final_obs(rows_per_env=4)
+    cut = 10 if h.type == "wb" else 6
+    first_of_second = None
+    for t_from, t_to in ((0, cut), (cut, h.k)):
+        k = t_to - t_from
+        traj, rt, ft, rs, dc = env.rollout(k, action_seed=A_SEED, t0=T0 + t_from, trajectory=True, per_step=True)
+        assert "rollout_rows_kernel" in env.last_kernel()
+        flags = check_against_twin(env, twin, h.actions(k, t0=T0 + t_from), traj, rt, ft, (kind, t_from))   # steps numbered within the call
+        assert flags.any() and env.final_obs_dropped() == 0
+        first_of_second = flags[0]
+    assert first_of_second.any() and int(env.final_obs()[1][0]) == 0, "an end at step 0 of the second call"
+    env.collect_final_obs(0)                                              # off again: the instance without the side output, and no rows to read
+    traj = env.rollout(3, action_seed=A_SEED, t0=T0 + h.k, trajectory=True)[0]
+    layout = {"wb": f", {str(getattr(h, 'flat', False)).lower()}"}.get(h.type, "")
+    assert env.last_kernel() == f"cge::{h.type}::rollout_kernel<1{layout}, false>"
+    for t, (ob, *_) in enumerate(steps_of_twin(twin, h.actions(3, t0=T0 + h.k))):
+        for key, v in as_dict(traj).items():
+            assert torch.equal(ob[key], v[t]), (kind, t, key, "trajectory without rows")
+    with pytest.raises(RuntimeError, match="collect_final_obs"):
+        env.final_obs()
+    env.close(); twin.close()
+
+
+@pytest.mark.parametrize("kind", ["wb-3-dict", "wb-3-flat", "bus", "restaurant"])
+def test_next_step_delivers_nothing(cge, kind):
+    h = Hashed(kind)
+    env = h.make(cge, "NextStep")
+    env.collect_final_obs(rows_per_env=4)
+    env._fin[2].fill_(7)                                                  # stale counts: the call has to clear them
+    ft = env.rollout(h.k, action_seed=A_SEED, t0=T0, per_step=True)[2]
+    assert ft.any() and "rollout_kernel<0, " in env.last_kernel()
+    rows, step, who = env.final_obs()
+    assert step.shape[0] == 0 and all(v.shape[0] == 0 for v in as_dict(rows).values()) and env.final_obs_dropped() == 0
+    assert not env._fin[2].any()
+    env.close()
+
+
+@pytest.mark.parametrize("kind, ok, bad, text", [("wb-3-dict", 16, 4, "not 16-byte aligned"), ("bus", 16, 4, "not 16-byte aligned"),
+                                                 ("restaurant", 4, 2, "not 4-byte aligned"), ("wb-3-flat", 4, 2, "not 4-byte aligned")])
+def test_misaligned_rows_are_refused(cge, kind, ok, bad, text):
+    """the store pass writes 16-byte pieces (bus, world builder's Dict slab) or whole ints led in one by one (restaurant, flat rows): a rollout
+    refuses registered rows that are not aligned so, and says why"""
+    h = Hashed(kind)
+    env, twin = h.make(cge), h.make(cge)
+    env.collect_final_obs(rows_per_env=4)
+    rows, index, count, cap = env._fin
+    nbytes = rows.numel() * rows.element_size()
+    spare = torch.empty(nbytes + 32, dtype=torch.uint8, device="cuda")
+    register = env._fn("rollout_final_obs")
+    assert spare.data_ptr() % 16 == 0
+    assert register(env._h, spare.data_ptr() + bad, index.data_ptr(), cap, count.data_ptr()) == 0
+    with pytest.raises(cge.NativeLibraryError, match="the registered terminal rows are " + text):
+        env.rollout(3, action_seed=1)
+    assert register(env._h, spare.data_ptr() + ok, index.data_ptr(), cap, count.data_ptr()) == 0
+    env._fin = (spare[ok:ok + nbytes].view(rows.dtype).view(rows.shape), index, count, cap)
+    traj, rt, ft, rs, dc = env.rollout(h.k, action_seed=A_SEED, t0=T0, trajectory=True, per_step=True)
+    assert "rollout_rows_kernel" in env.last_kernel() and env.final_obs_dropped() == 0
+    check_against_twin(env, twin, h.actions(h.k), traj, rt, ft, (kind, "rows at the smallest alignment"))
+    env.close(); twin.close()
+
+
+# -------------------------------------------------------------------------------------------------------------- graph capture
+def test_captured_rows_rollout_replays(cge):
+    """world builder, Dict, G = 3: two rollout calls with rows in one graph, replayed twice, against an eager twin call by call (rows slab,
+    index, counts, trajectories, rewards and flags)."""
+    k, calls = 12, 2
+    h = Hashed("wb-3-dict")
+    env, twin = h.make(cge, reuse_buffers=True), h.make(cge, reuse_buffers=True)
+    for e in (env, twin):
+        e.collect_final_obs(rows_per_env=2)
+
+    def call(e, c):
+        out = e.rollout(k, action_seed=A_SEED, t0=T0 + c * k, trajectory=True, per_step=True)
+        return [out[1], out[2], e._fin[0], e._fin[1], e._fin[2], *out[0].values()]       # per key: the padding between planes is nobody's
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        w = call(env, 0)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    call(twin, 0)
+    hist = [[torch.empty_like(x) for x in w] for _ in range(calls)]
+    for c in range(1, calls):
+        call(env, c); call(twin, c)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for c in range(calls):
+            for dst, src in zip(hist[c], call(env, c)):
+                dst.copy_(src)
+    ends = 0
+    cap, planes = env._fin[3], env._fin_planes
+    for rep in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        for c in range(calls):
+            rt, ft, rows, index, count, *traj = call(twin, c)
+            torch.cuda.synchronize()
+            got = hist[c]
+            assert torch.equal(got[0], rt) and torch.equal(got[1], ft) and len(traj) == 4 and all(torch.equal(a, b) for a, b in zip(got[5:], traj)), (rep, c)
+            assert torch.equal(got[4], count), (rep, c)
+            used = (torch.arange(cap, device="cuda")[None, :] < count.clamp(max=cap)[:, None]).reshape(-1)
+            assert torch.equal(got[3][used], index[used]), (rep, c)
+            a, b = plane_views(got[2], NSEG * cap, planes), plane_views(rows, NSEG * cap, planes)
+            for key in a:
+                assert torch.equal(a[key][used], b[key][used]), (rep, c, key)
+            ends += int(count.sum())
+    assert ends >= N, "episodes end inside the graph"
+    env.close(); twin.close()
