@@ -37,6 +37,7 @@ def is_stale():
 # -DCGE_EMERGENCY_LDS_ROWS: the same for the emergency observation (profiles/emergency_timing.txt).
 # -DCGE_STATION_LANE_ROWS: the space-station observation as per-lane row stores; there the LDS tile is the faster form and is built
 # (profiles/space_station_timing.txt).  The farm observation has the LDS tile only (profiles/farm_timing.txt).
+# These three store-pass variants were last buildable at commit 84dc52e; the sources no longer have them.
 GUARD_FLAGS = ("-DCGE_MFG_GUARD", "-DCGE_GUARD")
 
 

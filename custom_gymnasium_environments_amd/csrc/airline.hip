@@ -19,6 +19,7 @@
 // pieces (160 B, whole 32-byte sectors); the four parts complete every 128-byte line within one observation.  Parking the part in LDS
 // and writing it with consecutive lanes on consecutive pieces, as the other row-major types do, was measured and is 3-23 % SLOWER
 // here (profiles/airline_timing.txt): the kernel waits on dependent loads, not on stores, and the tile's 10.4 KB cost it two waves per CU.
+// That variant, -DCGE_AIRLINE_LDS_ROWS, was last buildable at commit 84dc52e.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -30,12 +31,6 @@ namespace cge {
 namespace airline {
 
 constexpr int BLOCK = 64;        // one wave: the LDS rows are the wave's own, no cross-wave barrier
-#ifdef CGE_AIRLINE_LDS_ROWS
-constexpr int STG_ROW = BLOCK + 1;   // the store pass reads down a column: an odd row length spreads it over the banks
-constexpr int STG_FLOATS = PART_FLOATS * STG_ROW;
-#else
-constexpr int STG_FLOATS = 1;
-#endif
 static_assert(OBS == CGE_AIRLINE_OBS_FLOATS && REC_WORDS * 4 == CGE_AIRLINE_RECORD_BYTES, "cge_amd.h");
 
 struct Params : LaneParams<float> {
@@ -43,19 +38,14 @@ struct Params : LaneParams<float> {
 };
 static_assert(std::is_trivially_copyable<Params>::value, "a kernel argument");
 
-// what a runtime index reaches (airline_env.hpp's accessor): LDS rows of this lane, HBM columns of this env
-struct Mem {
+// what a runtime index reaches (airline_env.hpp's accessor): LDS rows of this lane, HBM columns of this env (LaneCols)
+// The compiler forms a 64-bit per-lane address for every column it touches and keeps what it can reuse: the ~120 addresses of
+// load_env for store_env, the ~70 of the observation's loads across a rollout's step loop — more registers than there are.  Hence
+// fresh() at the top of every step as well as before the stores.
+struct Mem : LaneCols {
     uint32_t *acw, *av;                                              // [k * BLOCK]
     float *sv;
     double *pr;
-    uint32_t *rec;                                                   // the columns (uniform): word w of env i at rec[w * n + i].  A scalar base
-    uint32_t off;                                                    // plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30) addresses
-    int64_t n;                                                       // every column; 64-bit per-lane addresses, one pair of registers per
-                                                                     // column and kept from the loads to the stores of a launch, spilled
-    // The compiler forms a 64-bit per-lane address for every column it touches and keeps what it can reuse: the ~120 addresses of
-    // load_env for store_env, the ~70 of the observation's loads across a rollout's step loop — more registers than there are.
-    // After fresh() the offset is a new value to it: the addresses are formed again where they are used (one add each).
-    __device__ __forceinline__ void fresh() { asm volatile("" : "+v"(off)); }
     __device__ __forceinline__ uint32_t ac(uint32_t a) const { return acw[a * BLOCK]; }
     __device__ __forceinline__ void set_ac(uint32_t a, uint32_t w) { acw[a * BLOCK] = w; }
     __device__ __forceinline__ uint32_t avail(uint32_t p) const { return av[p * BLOCK]; }
@@ -64,20 +54,6 @@ struct Mem {
     __device__ __forceinline__ void set_sev(uint32_t p, float v) { sv[p * BLOCK] = v; }
     __device__ __forceinline__ double price(uint32_t p) const { return pr[p * BLOCK]; }
     __device__ __forceinline__ void set_price(uint32_t p, double v) { pr[p * BLOCK] = v; }
-    __device__ __forceinline__ uint32_t word(int w) const { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rec + (int64_t)w * n) + off); }
-    __device__ __forceinline__ void set_word(int w, uint32_t v) { *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(rec + (int64_t)w * n) + off) = v; }
-    __device__ __forceinline__ double dword(int w) const {
-        const uint64_t u = (uint64_t)word(w) | (uint64_t)word(w + 1) << 32;
-        double d;
-        __builtin_memcpy(&d, &u, 8);
-        return d;
-    }
-    __device__ __forceinline__ void set_dword(int w, double d) {
-        uint64_t u;
-        __builtin_memcpy(&u, &d, 8);
-        set_word(w, (uint32_t)u);
-        set_word(w + 1, (uint32_t)(u >> 32));
-    }
     __device__ __forceinline__ double fuel(int a) const { return dword(W_FUEL + 2 * a); }
     __device__ __forceinline__ void set_fuel(int a, double v) { set_dword(W_FUEL + 2 * a, v); }
     __device__ __forceinline__ double maint0(int a) const { return dword(W_MAINT + 2 * a); }
@@ -87,12 +63,6 @@ struct Mem {
     __device__ __forceinline__ double sched(int f) const { return dword(W_SCHED + 2 * f); }
     __device__ __forceinline__ void set_sched(int f, double s) { set_dword(W_SCHED + 2 * f, s); }
 };
-
-// 4 * (the env of this lane, or the last env for a lane past the end), in 32-bit arithmetic throughout
-__device__ __forceinline__ uint32_t lane_offset(int64_t n) {
-    const uint32_t i = blockIdx.x * (uint32_t)BLOCK + threadIdx.x, last = (uint32_t)n - 1u;
-    return (i < last ? i : last) * 4u;
-}
 
 __device__ __forceinline__ void load_env(Env &e, Mem &m) {
 #pragma unroll
@@ -134,48 +104,32 @@ __device__ __forceinline__ void store_env(const Env &e, Mem &m, bool prices) {
     e.pack_scalars([&](int k, uint32_t v) __attribute__((always_inline)) { m.set_word(W_SCAL + k, v); });
 }
 
-// One part of the wave's rows: `envs` rows from row `first` on, floats [40 * PART, 40 * PART + 40) of each.
+// One part of the wave's rows: floats [40 * PART, 40 * PART + 40) of row `lane` of `rows`.  Every lane stores its own 160 bytes of the
+// part, 64 lanes 640 bytes apart per instruction: whole 32-byte sectors, no tile, no barrier.
 template <int PART>
-__device__ __forceinline__ void observe_rows(const Env &e, Mem &m, float *__restrict__ stg, float *__restrict__ rows, int envs, int lane, bool live) {
-#ifndef CGE_AIRLINE_LDS_ROWS                                             // every lane stores its own 160 bytes of the part, 64 lanes 640 bytes apart
-    if (live) {                                                       // per instruction: whole 32-byte sectors, no tile, no barrier
+__device__ __forceinline__ void observe_rows(const Env &e, Mem &m, float *__restrict__ rows, int lane, bool live) {
+    if (live) {
         float v4[PART_FLOATS];
         observe_part<PART>(e, m, [&](int k, float v) __attribute__((always_inline)) { v4[k] = v; });
 #pragma unroll
         for (int k = 0; k < PART_FLOATS; k += 4)
             *reinterpret_cast<float4 *>(rows + (int64_t)lane * OBS + PART * PART_FLOATS + k) = make_float4(v4[k], v4[k + 1], v4[k + 2], v4[k + 3]);
     }
-#else                                                                 // the variant measured and dropped (profiles/airline_timing.txt): the part
-                                                                      // parked in LDS [element][env], written as ten consecutive pieces per env
-    if (live) observe_part<PART>(e, m, [&](int k, float v) __attribute__((always_inline)) { stg[k * STG_ROW + lane] = v; });
-    __syncthreads();
-    const int pieces = envs * (PART_FLOATS / 4);
-#pragma unroll 2
-    for (int q = lane; q < pieces; q += BLOCK) {
-        const int env = q / (PART_FLOATS / 4), pc = q - env * (PART_FLOATS / 4);
-        const float *s = stg + (4 * pc) * STG_ROW + env;
-        *reinterpret_cast<float4 *>(rows + (int64_t)env * OBS + PART * PART_FLOATS + 4 * pc) = make_float4(s[0], s[STG_ROW], s[2 * STG_ROW], s[3 * STG_ROW]);
-    }
-    __syncthreads();                                                 // the tile is free for the next part
-#endif
 }
-// _get_observation :354-396 of the wave's envs -> their rows of o [n, 160].  Call with every lane of the wave (the LDS variant has barriers).
-__device__ __forceinline__ void observe(const Env &e, Mem &m, float *__restrict__ stg, float *__restrict__ o, int64_t n, bool live) {
+// _get_observation :354-396 of the wave's envs -> their rows of o [n, 160]
+__device__ __forceinline__ void observe(const Env &e, Mem &m, float *__restrict__ o, bool live) {
     const int lane = (int)threadIdx.x;
-    const int64_t first = (int64_t)blockIdx.x * BLOCK;
-    const int envs = (int)(n - first < BLOCK ? n - first : BLOCK);
-    float *rows = o + first * OBS;
-    observe_rows<0>(e, m, stg, rows, envs, lane, live);
-    observe_rows<1>(e, m, stg, rows, envs, lane, live);
-    observe_rows<2>(e, m, stg, rows, envs, lane, live);
-    observe_rows<3>(e, m, stg, rows, envs, lane, live);
+    float *rows = o + (int64_t)blockIdx.x * BLOCK * OBS;
+    observe_rows<0>(e, m, rows, lane, live);
+    observe_rows<1>(e, m, rows, lane, live);
+    observe_rows<2>(e, m, rows, lane, live);
+    observe_rows<3>(e, m, rows, lane, live);
 }
 
 #define CGE_AIRLINE_LDS                                   \
     __shared__ uint32_t s_ac[NA * BLOCK], s_av[NP * BLOCK]; \
     __shared__ float s_sv[NP * BLOCK];                    \
-    __shared__ double s_pr[NP * BLOCK];                   \
-    __shared__ float s_stg[STG_FLOATS];
+    __shared__ double s_pr[NP * BLOCK];
 
 // k steps with the record in registers and LDS.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else
 // the counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 45, 0).
@@ -186,7 +140,7 @@ __device__ __forceinline__ void run(const Params &p) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Mem m{s_ac + lane, s_av + lane, s_sv + lane, s_pr + lane, reinterpret_cast<uint32_t *>(p.state), lane_offset(p.n), p.n};
+    Mem m{{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)}, s_ac + lane, s_av + lane, s_sv + lane, s_pr + lane};
     Env e;
     load_env(e, m);
     MtStream rng(p.mt + li * MT_STRIDE, e.mt_pos, 0u);
@@ -214,10 +168,10 @@ __device__ __forceinline__ void run(const Params &p) {
             }
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal rows: every env of a wave with a terminated one
-            if (p.final_obs && __ballot(term)) observe(e, m, s_stg, p.final_obs, p.n, live);
+            if (p.final_obs && __ballot(term)) observe(e, m, p.final_obs, live);
         }
         if (MODE != CGE_AUTORESET_DISABLED && reset_now) { reset_episode(e, m, rng); prices = true; }
-        if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, m, s_stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, live);
+        if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, m, p.obs + (int64_t)t * p.obs_step_stride, live);
         if (live) {
             if (ROLLOUT) {
                 rsum += (double)reward;
@@ -251,7 +205,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Mem m{s_ac + lane, s_av + lane, s_sv + lane, s_pr + lane, reinterpret_cast<uint32_t *>(p.state), lane_offset(p.n), p.n};
+    Mem m{{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)}, s_ac + lane, s_av + lane, s_sv + lane, s_pr + lane};
     Env e;
     load_env(e, m);
     bool dirty = false;
@@ -269,7 +223,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
         }
         if (dirty) store_env(e, m, true);
     }
-    if (p.obs) observe(e, m, s_stg, p.obs, p.n, live);
+    if (p.obs) observe(e, m, p.obs, live);
 }
 
 __global__ __launch_bounds__(256) void info_kernel(const uint32_t *__restrict__ state, int64_t n, int field, double *__restrict__ out) {
@@ -315,25 +269,10 @@ struct cge_airline : LaneHandle {
         return p;
     }
     int64_t step_elems() const { return n * airline::OBS; }
-    auto reset_kernel() const { return airline::reset_kernel; }
-    template <int MODE>
-    auto kernel(LaneKind kind) const {
-        return kind == LANE_STEP ? airline::step_kernel<MODE>
-               : kind == LANE_ROLLOUT_GIVEN ? airline::rollout_kernel<MODE, true> : airline::rollout_kernel<MODE, false>;
-    }
+    CGE_LANE_KERNELS(airline)
     static int check(const cge_airline_config &c) { return bad_autoreset_mode(c.autoreset_mode) || c.reserved != 0 ? CGE_ERR_INVALID_ARG : CGE_OK; }
-    hipError_t init() {
-        CGE_HIP(alloc(state, (size_t)airline::REC_WORDS * n * sizeof(uint32_t), true, true));
-        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
-        CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
-        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
-        lane_launch_reset(this, params(), 1, 0, nullptr);
-        return hipGetLastError();
-    }
+    hipError_t init() { return lane_init(this, airline::REC_WORDS); }
 };
-
-// observation rows leave as 16-byte pieces
-static bool rows_aligned(const void *a, const void *b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
 
 extern "C" {
 

@@ -6,16 +6,26 @@
 // seed / reset / step / rollout entry points.  The step loops themselves stay with their types: they differ in where the wave
 // acts together (bus resets by drawing under a ballot, world builder's env_step is called by every lane with a `go` flag,
 // restaurant prefetches actions and keeps a run of generator words in registers), and a shared loop would branch on its caller.
+// Airline, emergency, space station and farm (the record-lane types: hundreds of columns a record) share LaneCols, lane_col_offset,
+// LaneRng and the host helpers below, and keep their loops too.  Emergency's, station's and farm's read alike, and one loop over a
+// per-type Lane struct owning Cols, Env and Rng was tried: station's kernels kept registers and instruction counts, farm's did not
+// in any of three forms (members in either order, or references to run()'s locals), by spills and some tens of instructions of
+// 28,000 — nothing that was measured, so nothing that was merged (profiles/record_lane_refactor_resources.txt).  Airline differs in
+// its text as well: fresh() at the top of every step, a `prices` flag into store_env, no ready-ahead and no rows instance.
 //
 // A new lane-per-env type supplies
 //   device  struct Params : LaneParams<Obs> with its own fields and `static constexpr bool terminates` (the flag it raises:
-//           terminated, or truncated), its run() loop calling the lane_* helpers below, and the three __global__ kernels;
+//           terminated, or truncated), its run() loop calling the lane_* helpers below, and the three __global__ kernels; a type
+//           whose record is columns of 32-bit words takes LaneCols, lane_col_offset<BLOCK> and LaneRng (`using Cols = LaneCols;`)
+//           and writes load_env / store_env over them;
 //   host    a handle derived from LaneHandle with Params, abi, kernel_ns, block, seed_kind, params(), step_elems(), reset_kernel(),
-//           kernel<MODE>(kind), and whichever of layout_arg() / actions_refusal() differ from the defaults; for the terminal rows of fused
-//           rollouts (all but airline) RowsParams, rows_ns and launch_rows() as well, and fill_rows() where RowsParams holds more than
-//           `fin` (the Dict types' slab of compacted rows), see LaneHandle;
-//   C ABI   entry points that are one lane_seed / lane_reset / lane_step / lane_rollout call each, with the type's own pointer and
-//           stride predicates and error texts as arguments.
+//           kernel<MODE>(kind) (CGE_LANE_KERNELS(ns) where the kernels have no layout argument), and whichever of layout_arg() /
+//           actions_refusal() differ from the defaults; for the terminal rows of fused rollouts (all but airline) RowsParams, rows_ns
+//           and launch_rows() (CGE_LANE_LAUNCH_ROWS(ns)) as well, and fill_rows() where RowsParams holds more than `fin` (the Dict
+//           types' slab of compacted rows), see LaneHandle; init() is lane_init(this, REC_WORDS) where the arrays are state, mt, err
+//           and no test reads the allocation from the source;
+//   C ABI   entry points that are one lane_seed / lane_reset / lane_step / lane_rollout (/ lane_info) call each, with the type's own
+//           pointer and stride predicates (rows_aligned) and error texts as arguments.
 // Parking's seed / reset have the same shape and use lane_seed / lane_reset (and lane_blocks for its grid); the rest of parking is its own.
 #pragma once
 #include <string>
@@ -133,6 +143,70 @@ __device__ __forceinline__ void lane_store_tile(const float *__restrict__ stg, f
     }
 }
 
+// ------------------------------------------------------------------------------------------- device: the record-lane kit
+// Airline, emergency, space station and farm keep a record of hundreds of 32-bit columns, word w of env i at rec[w * n + i], in
+// registers (and LDS) from the start of a launch to its end.  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
+// addresses every column; 64-bit per-lane addresses, one pair of registers per column and kept from the loads of a launch to its
+// stores, took every register there is and spilled.  After fresh() the offset is a new value to the compiler: the addresses are
+// formed again where they are used (one add each).
+struct LaneCols {
+    uint32_t *rec;                                                   // uniform
+    int64_t n;
+    uint32_t off;
+    __device__ __forceinline__ void fresh() { asm volatile("" : "+v"(off)); }
+    __device__ __forceinline__ uint32_t word(int w) const { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rec + (int64_t)w * n) + off); }
+    __device__ __forceinline__ void set_word(int w, uint32_t v) const { *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(rec + (int64_t)w * n) + off) = v; }
+    __device__ __forceinline__ double dword(int w) const {
+        const uint64_t u = (uint64_t)word(w) | (uint64_t)word(w + 1) << 32;
+        double d;
+        __builtin_memcpy(&d, &u, 8);
+        return d;
+    }
+    __device__ __forceinline__ void set_dword(int w, double d) const {
+        uint64_t u;
+        __builtin_memcpy(&u, &d, 8);
+        set_word(w, (uint32_t)u);
+        set_word(w + 1, (uint32_t)(u >> 32));
+    }
+};
+// LaneCols::off: 4 * (the env of this lane, or the last env for a lane past the end), in 32-bit arithmetic throughout
+template <int BLOCK>
+__device__ __forceinline__ uint32_t lane_col_offset(int64_t n) {
+    const uint32_t i = blockIdx.x * (uint32_t)BLOCK + threadIdx.x, last = (uint32_t)n - 1u;
+    return (i < last ? i : last) * 4u;
+}
+// the generator as the dynamics headers draw from it: single words, and runs of W words the caller consumes in order
+struct LaneRng {
+    MtStream s;
+    __device__ __forceinline__ LaneRng(uint32_t *block, uint32_t pos, uint32_t ready) : s(block, pos, ready) {}
+    __device__ __forceinline__ uint32_t next() { return s.next(); }
+    template <int W>
+    __device__ __forceinline__ void run(uint32_t (&w)[W]) {
+        static_assert(W % 4 == 0 && W <= MT_N, "whole 16-byte pieces");
+        if (s.pos + (uint32_t)W <= s.pretw) {
+            // ready: W / 4 independent loads; a piece that straddles word 623 runs into the mirror of words 0..2, which the twist of the
+            // next generation's first chunk has written
+#pragma unroll
+            for (int q = 0; q < W; q += 4) {
+                uint32_t at = s.pos + (uint32_t)q;
+                at -= at >= (uint32_t)MT_N ? (uint32_t)MT_N : 0u;
+                const MtQuad v = *reinterpret_cast<const MtQuad *>(s.w + at);
+                w[q] = mt_temper(v.a); w[q + 1] = mt_temper(v.b); w[q + 2] = mt_temper(v.c); w[q + 3] = mt_temper(v.d);
+            }
+            mt_advance(s.pos, s.pretw, (uint32_t)W);
+        } else {
+#pragma unroll
+            for (int j = 0; j < W; ++j) w[j] = 0u;
+#pragma unroll 1
+            for (int k = 0; k < W; ++k) {
+                const uint32_t y = s.next();
+#pragma unroll
+                for (int j = 0; j < W; ++j) w[j] = j == k ? y : w[j];   // no indexed register array
+            }
+        }
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------------ host
 enum LaneKind { LANE_STEP, LANE_ROLLOUT_GIVEN, LANE_ROLLOUT_HASHED };   // the kernel of a launch: step(), rollout() with / without actions
 
@@ -170,6 +244,49 @@ unsigned lane_segments(const H *h) { return (unsigned)((h->n + 63) / 64); }
 template <class H, class P>
 void lane_launch_reset(const H *h, const P &p, int init, int rewind, hipStream_t s) {
     hipLaunchKernelGGL(h->reset_kernel(), dim3(lane_blocks(h)), dim3(H::block), 0, s, p, init, rewind);
+}
+
+// The init() of a handle whose device arrays are the record's columns, one generator block per env and the error counter: allocate,
+// seed the streams as a fresh handle has them, construct the envs.  Airline and emergency; station and farm spell theirs out, as
+// tests/test_farm_cpu.py reads from their sources that the record is the first array of a snapshot.
+template <class H>
+hipError_t lane_init(H *h, int rec_words) {
+    CGE_HIP(h->alloc(h->state, (size_t)rec_words * h->n * sizeof(uint32_t), true, true));
+    CGE_HIP(h->alloc(h->mt, (size_t)h->n * MT_STRIDE * sizeof(uint32_t), false, true));
+    CGE_HIP(h->alloc(h->err, sizeof(unsigned long long), true, false));
+    CGE_HIP(launch_mt_seed(h->mt, MT_STRIDE, h->n, nullptr, 0, h->env0, H::seed_kind, nullptr));
+    lane_launch_reset(h, h->params(), 1, 0, nullptr);
+    return hipGetLastError();
+}
+
+// a handle's reset_kernel() and kernel<MODE>(kind) where namespace NS has reset_kernel, step_kernel<MODE> and rollout_kernel<MODE, GIVEN>
+#define CGE_LANE_KERNELS(NS)                                                                                              \
+    auto reset_kernel() const { return NS::reset_kernel; }                                                                \
+    template <int MODE>                                                                                                   \
+    auto kernel(cge::LaneKind kind) const {                                                                               \
+        return kind == cge::LANE_STEP ? NS::step_kernel<MODE>                                                             \
+               : kind == cge::LANE_ROLLOUT_GIVEN ? NS::rollout_kernel<MODE, true> : NS::rollout_kernel<MODE, false>;      \
+    }
+// ... and its launch_rows() where NS has rollout_rows_kernel<GIVEN>
+#define CGE_LANE_LAUNCH_ROWS(NS)                                                                                          \
+    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {                             \
+        hipLaunchKernelGGL(given ? NS::rollout_rows_kernel<true> : NS::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p); \
+    }
+
+// are observation rows that leave as 16-byte (mask 15) or 8-byte (7) pieces aligned at both addresses?  A null one is.
+inline bool rows_aligned(const void *a, const void *b, uintptr_t mask = 15u) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & mask) == 0;
+}
+
+// cge_<env>_info where an info_kernel(Params, field, out) computes the field from the whole record.  `ok` / `what`: the field and
+// pointer check and its error text.
+template <class H, class K>
+int lane_info(H *h, bool ok, const char *what, K info_kernel, int32_t field_id, double *out, void *stream) {
+    if (!h) return CGE_ERR_INVALID_ARG;
+    if (!ok) return h->fail(CGE_ERR_INVALID_ARG, what);
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(info_kernel, dim3(lane_blocks(h)), dim3(H::block), 0, as_stream(stream), h->params(), (int)field_id, out);
+    return launched(h);
 }
 
 template <class H>

@@ -19,8 +19,9 @@
 // words (it takes rejections in randint or a full house of escalations) falls back to twisting word by word (MtStream).
 //
 // Observation: float32 [n, 276] row-major, 69 sixteen-byte pieces a row.  Each lane stores its own row as it computes it, in four
-// groups (incidents, units 0..19, units 20..39, the rest).  -DCGE_EMERGENCY_LDS_ROWS parks a group in LDS and writes it with
-// consecutive lanes on consecutive pieces instead: the other form the rows can leave in, measured in profiles/emergency_timing.txt.
+// groups (incidents, units 0..19, units 20..39, the rest).  Parking a group in LDS and writing it with consecutive lanes on
+// consecutive pieces, the other form the rows can leave in, was measured and dropped (profiles/emergency_timing.txt; that variant,
+// -DCGE_EMERGENCY_LDS_ROWS, was last buildable at commit 84dc52e).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -33,13 +34,6 @@ namespace emergency {
 
 constexpr int BLOCK = 64;        // one wave: the LDS rows are the wave's own, no cross-wave barrier
 constexpr uint32_t READY = 160;  // words made ready at the top of a step
-constexpr int STG_COUNT = 80;    // floats of a row that leave together, at the most
-#ifdef CGE_EMERGENCY_LDS_ROWS
-constexpr int STG_ROW = BLOCK + 1;   // the store pass reads down a column: an odd row length spreads it over the banks
-constexpr int STG_FLOATS = STG_COUNT * STG_ROW;
-#else
-constexpr int STG_FLOATS = 1;
-#endif
 static_assert(OBS == CGE_EMERGENCY_OBS_FLOATS && REC_WORDS * 4 == CGE_EMERGENCY_RECORD_BYTES && ACTIONS == CGE_EMERGENCY_ACTIONS, "cge_amd.h");
 
 struct Params : LaneParams<float> {
@@ -67,68 +61,8 @@ struct Mem {
     __device__ __forceinline__ void set_fatigue(uint32_t u, double v) { fa[u * BLOCK] = v; }
 };
 
-// the env's columns: word w of env i at rec[w * n + i].  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
-// addresses every column; 64-bit per-lane addresses, one pair of registers per column and kept from the loads of a launch to its
-// stores, took every register there is and spilled.  After fresh() the offset is a new value to the compiler: the addresses are
-// formed again where they are used (one add each).
-struct Cols {
-    uint32_t *rec;                                                   // uniform
-    int64_t n;
-    uint32_t off;
-    __device__ __forceinline__ void fresh() { asm volatile("" : "+v"(off)); }
-    __device__ __forceinline__ uint32_t word(int w) const { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rec + (int64_t)w * n) + off); }
-    __device__ __forceinline__ void set_word(int w, uint32_t v) const { *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(rec + (int64_t)w * n) + off) = v; }
-    __device__ __forceinline__ double dword(int w) const {
-        const uint64_t u = (uint64_t)word(w) | (uint64_t)word(w + 1) << 32;
-        double d;
-        __builtin_memcpy(&d, &u, 8);
-        return d;
-    }
-    __device__ __forceinline__ void set_dword(int w, double d) const {
-        uint64_t u;
-        __builtin_memcpy(&u, &d, 8);
-        set_word(w, (uint32_t)u);
-        set_word(w + 1, (uint32_t)(u >> 32));
-    }
-};
-
-// the generator as emergency_env.hpp draws from it: single words, and runs of W words the caller consumes in order
-struct Rng {
-    MtStream s;
-    __device__ __forceinline__ Rng(uint32_t *block, uint32_t pos, uint32_t ready) : s(block, pos, ready) {}
-    __device__ __forceinline__ uint32_t next() { return s.next(); }
-    template <int W>
-    __device__ __forceinline__ void run(uint32_t (&w)[W]) {
-        static_assert(W % 4 == 0 && W <= MT_N, "whole 16-byte pieces");
-        if (s.pos + (uint32_t)W <= s.pretw) {
-            // ready: W / 4 independent loads; a piece that straddles word 623 runs into the mirror of words 0..2, which the twist of the
-            // next generation's first chunk has written
-#pragma unroll
-            for (int q = 0; q < W; q += 4) {
-                uint32_t at = s.pos + (uint32_t)q;
-                at -= at >= (uint32_t)MT_N ? (uint32_t)MT_N : 0u;
-                const MtQuad v = *reinterpret_cast<const MtQuad *>(s.w + at);
-                w[q] = mt_temper(v.a); w[q + 1] = mt_temper(v.b); w[q + 2] = mt_temper(v.c); w[q + 3] = mt_temper(v.d);
-            }
-            mt_advance(s.pos, s.pretw, (uint32_t)W);
-        } else {
-#pragma unroll
-            for (int j = 0; j < W; ++j) w[j] = 0u;
-#pragma unroll 1
-            for (int k = 0; k < W; ++k) {
-                const uint32_t y = s.next();
-#pragma unroll
-                for (int j = 0; j < W; ++j) w[j] = j == k ? y : w[j];   // no indexed register array
-            }
-        }
-    }
-};
-
-// 4 * (the env of this lane, or the last env for a lane past the end), in 32-bit arithmetic throughout
-__device__ __forceinline__ uint32_t lane_offset(int64_t n) {
-    const uint32_t i = blockIdx.x * (uint32_t)BLOCK + threadIdx.x, last = (uint32_t)n - 1u;
-    return (i < last ? i : last) * 4u;
-}
+using Cols = LaneCols;
+using Rng = LaneRng;
 
 __device__ __forceinline__ void load_env(Env &e, Mem &m, const Cols &c) {
 #pragma unroll
@@ -164,87 +98,66 @@ __device__ __forceinline__ void store_env(const Env &e, Mem &m, const Cols &c) {
 }
 
 // One group of the wave's rows: floats [FIRST, FIRST + COUNT) of each, computed by gen(sink) with sink(k, value), k the element's index
-// in the row.  Call with every lane of the wave (the LDS variant has barriers).
+// in the row.  Every lane with `live` stores its own pieces of the group to row `lane`, 64 lanes 1,104 bytes apart.
 template <int FIRST, int COUNT, class G>
-__device__ __forceinline__ void observe_group(float *__restrict__ stg, float *__restrict__ rows, int envs, int lane, bool live, G gen) {
-    static_assert(FIRST % 4 == 0 && COUNT % 4 == 0 && COUNT <= STG_COUNT, "whole 16-byte pieces");
-#ifndef CGE_EMERGENCY_LDS_ROWS                                        // every lane stores its own pieces of the group, 64 lanes 1,104 bytes apart
+__device__ __forceinline__ void observe_group(float *__restrict__ rows, int lane, bool live, G gen) {
+    static_assert(FIRST % 4 == 0 && COUNT % 4 == 0, "whole 16-byte pieces");
     if (live) {
         float v[COUNT];
         gen([&](int k, float x) __attribute__((always_inline)) { v[k - FIRST] = x; });
 #pragma unroll
         for (int q = 0; q < COUNT; q += 4) *reinterpret_cast<float4 *>(rows + (int64_t)lane * OBS + FIRST + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
     }
-#else                                                                 // the variant measured and dropped (profiles/emergency_timing.txt): the group
-                                                                      // parked in LDS [element][env], written as consecutive pieces per env
-    if (live) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + lane] = x; });
-    __syncthreads();
-    const int pieces = envs * (COUNT / 4);
-#pragma unroll 2
-    for (int q = lane; q < pieces; q += BLOCK) {
-        const int env = q / (COUNT / 4), pc = q - env * (COUNT / 4);
-        const float *s = stg + (4 * pc) * STG_ROW + env;
-        *reinterpret_cast<float4 *>(rows + (int64_t)env * OBS + FIRST + 4 * pc) = make_float4(s[0], s[STG_ROW], s[2 * STG_ROW], s[3 * STG_ROW]);
-    }
-    __syncthreads();                                                 // the tile is free for the next group
-#endif
 }
 // _get_observation :524-587 of the wave's envs -> their rows of o [n, 276], 69 sixteen-byte pieces a row: the incidents (20 pieces),
 // the units in two halves (15 pieces each), the rest (19).  Call with every lane of the wave.
-__device__ __forceinline__ void observe(const Env &e, Mem &m, float *__restrict__ stg, float *__restrict__ o, int64_t n, bool live, uint32_t max_t) {
+__device__ __forceinline__ void observe(const Env &e, Mem &m, float *__restrict__ o, int64_t n, bool live, uint32_t max_t) {
     const int lane = (int)threadIdx.x;
     const int64_t first = (int64_t)blockIdx.x * BLOCK;
-    const int envs = (int)(n - first < BLOCK ? n - first : BLOCK);
     float *rows = o + first * OBS;
-    observe_group<0, 80>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) {
+    observe_group<0, 80>(rows, lane, live, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < NI; ++s) observe_incident(e, m, out, s);
     });
-    observe_group<80, 60>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) {
+    observe_group<80, 60>(rows, lane, live, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < 20; ++u) observe_unit(e, m, out, u);
     });
-    observe_group<140, 60>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) {
+    observe_group<140, 60>(rows, lane, live, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 20; u < 40; ++u) observe_unit(e, m, out, u);
     });
-    observe_group<200, 76>(stg, rows, envs, lane, live, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
+    observe_group<200, 76>(rows, lane, live, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
 }
 
-// observe_group for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` store row `rank` of
-// `rows` as they store their own rows everywhere else (there is no tile: the record fills the LDS); the LDS variant parks their group
-// in column `rank` and writes `keep` dense rows.  Call with every lane of the wave.
+// observe_group / observe for the terminal rows of one step of rollout_rows_kernel (lane_final_rows): the lanes with `mine` store row
+// `rank` of `rows` as they store their own rows everywhere else (there is no tile: the record fills the LDS; `keep`, the number of
+// dense rows, is for a store pass and unused).  final_group is a function of its own for its __restrict__: calling observe_group
+// from final_observe directly compiles both rollout_rows_kernel instances to other code
+// (profiles/record_lane_refactor_resources.txt).
 template <int FIRST, int COUNT, class G>
-__device__ __forceinline__ void final_group(float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, G gen) {
-#ifndef CGE_EMERGENCY_LDS_ROWS
-    observe_group<FIRST, COUNT>(stg, rows, keep, rank, mine, gen);
-#else
-    if (mine) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + rank] = x; });
-    __syncthreads();
-    lane_store_tile<FIRST, COUNT, 4, STG_ROW>(stg, rows, OBS, keep);
-    __syncthreads();
-#endif
+__device__ __forceinline__ void final_group(float *__restrict__ rows, int rank, bool mine, G gen) {
+    observe_group<FIRST, COUNT>(rows, rank, mine, gen);
 }
-__device__ __forceinline__ void final_observe(const Env &e, Mem &m, float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, uint32_t max_t) {
-    final_group<0, 80>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+__device__ __forceinline__ void final_observe(const Env &e, Mem &m, float *__restrict__ rows, int keep, int rank, bool mine, uint32_t max_t) {
+    final_group<0, 80>(rows, rank, mine, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < NI; ++s) observe_incident(e, m, out, s);
     });
-    final_group<80, 60>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+    final_group<80, 60>(rows, rank, mine, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < 20; ++u) observe_unit(e, m, out, u);
     });
-    final_group<140, 60>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) {
+    final_group<140, 60>(rows, rank, mine, [&](auto out) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 20; u < 40; ++u) observe_unit(e, m, out, u);
     });
-    final_group<200, 76>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
+    final_group<200, 76>(rows, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_rest(e, m, out, max_t); });
 }
 
 #define CGE_EMERGENCY_LDS                                                               \
     __shared__ uint32_t s_iw[NI * BLOCK], s_im[NI * BLOCK], s_is[NI * BLOCK], s_uw[NU * BLOCK]; \
-    __shared__ double s_fa[NU * BLOCK];                                                 \
-    __shared__ float s_stg[STG_FLOATS];
+    __shared__ double s_fa[NU * BLOCK];
 
 // k steps with the record in registers and LDS.  ROLLOUT: per-step outputs indexed [t, env], sums; GIVEN: the caller's actions, else
 // the counter hash cge_hash_action(action_seed, env_index0 + i, t0 + t, 50, 0).  With RowsParams (ROWS, a SAME_STEP rollout) the terminal rows
@@ -259,7 +172,7 @@ __device__ __forceinline__ void run(const P &p) {
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
     Mem m{s_iw + lane, s_im + lane, s_is + lane, s_uw + lane, s_fa + lane};
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, m, c);
     Rng rng(p.mt + li * MT_STRIDE, e.mt_pos, e.mt_ready);
@@ -287,15 +200,15 @@ __device__ __forceinline__ void run(const P &p) {
             }
         }
         if (MODE == CGE_AUTORESET_SAME_STEP && !ROLLOUT) {           // the terminal rows: every env of a wave with a terminated one
-            if (p.final_obs && __ballot(term)) observe(e, m, s_stg, p.final_obs, p.n, live, p.max_t);
+            if (p.final_obs && __ballot(term)) observe(e, m, p.final_obs, p.n, live, p.max_t);
         }
         if constexpr (ROWS) {                                        // ... of the terminated envs only, compacted: lane_final_rows
             float *dst;
             int keep, rank;
-            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, OBS, dst, keep, rank), false)) final_observe(e, m, s_stg, dst, keep, rank, term && rank < keep, p.max_t);
+            if (__builtin_expect(lane_final_rows(p.fin, fin_used, term, t, i, OBS, dst, keep, rank), false)) final_observe(e, m, dst, keep, rank, term && rank < keep, p.max_t);
         }
         if (live && MODE != CGE_AUTORESET_DISABLED && reset_now) reset_episode(e, m, rng);
-        if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, m, s_stg, p.obs + (int64_t)t * p.obs_step_stride, p.n, live, p.max_t);
+        if (lane_obs_due<ROLLOUT>(p, t, ksteps)) observe(e, m, p.obs + (int64_t)t * p.obs_step_stride, p.n, live, p.max_t);
         if (live) {
             if (ROLLOUT) {
                 rsum += (double)reward;
@@ -338,7 +251,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
     Mem m{s_iw + lane, s_im + lane, s_is + lane, s_uw + lane, s_fa + lane};
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, m, c);
     if (live) {
@@ -357,7 +270,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
         c.fresh();
         if (dirty) store_env(e, m, c);
     }
-    if (p.obs) observe(e, m, s_stg, p.obs, p.n, live, p.max_t);
+    if (p.obs) observe(e, m, p.obs, p.n, live, p.max_t);
 }
 
 __global__ __launch_bounds__(256) void info_kernel(const uint32_t *__restrict__ state, int64_t n, int field, double *__restrict__ out) {
@@ -407,30 +320,13 @@ struct cge_emergency : LaneHandle {
         return p;
     }
     int64_t step_elems() const { return n * emergency::OBS; }
-    auto reset_kernel() const { return emergency::reset_kernel; }
-    template <int MODE>
-    auto kernel(LaneKind kind) const {
-        return kind == LANE_STEP ? emergency::step_kernel<MODE>
-               : kind == LANE_ROLLOUT_GIVEN ? emergency::rollout_kernel<MODE, true> : emergency::rollout_kernel<MODE, false>;
-    }
-    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
-        hipLaunchKernelGGL(given ? emergency::rollout_rows_kernel<true> : emergency::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
-    }
+    CGE_LANE_KERNELS(emergency)
+    CGE_LANE_LAUNCH_ROWS(emergency)
     static int check(const cge_emergency_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_timesteps < 1 || c.max_timesteps > 65535 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
-    hipError_t init() {
-        CGE_HIP(alloc(state, (size_t)emergency::REC_WORDS * n * sizeof(uint32_t), true, true));
-        CGE_HIP(alloc(mt, (size_t)n * MT_STRIDE * sizeof(uint32_t), false, true));
-        CGE_HIP(alloc(err, sizeof(unsigned long long), true, false));
-        CGE_HIP(launch_mt_seed(mt, MT_STRIDE, n, nullptr, 0, env0, 0, nullptr));
-        lane_launch_reset(this, params(), 1, 0, nullptr);
-        return hipGetLastError();
-    }
+    hipError_t init() { return lane_init(this, emergency::REC_WORDS); }
 };
-
-// observation rows leave as 16-byte pieces
-static bool rows_aligned(const void *a, const void *b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
 
 extern "C" {
 

@@ -53,42 +53,8 @@ struct RowsParams : Params {                                         // rollout_
     FinalSeg fin;
 };
 
-// the env's columns: word w of env i at rec[w * n + i].  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
-// addresses every column.  After fresh() the offset is a new value to the compiler: the addresses are formed again where they are
-// used (one add each) instead of being kept in registers from the loads of a launch to its stores.
-struct Cols {
-    uint32_t *rec;                                                   // uniform
-    int64_t n;
-    uint32_t off;
-    __device__ __forceinline__ void fresh() { asm volatile("" : "+v"(off)); }
-    __device__ __forceinline__ uint32_t word(int w) const { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rec + (int64_t)w * n) + off); }
-    __device__ __forceinline__ void set_word(int w, uint32_t v) const { *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(rec + (int64_t)w * n) + off) = v; }
-    __device__ __forceinline__ double dword(int w) const {
-        const uint64_t u = (uint64_t)word(w) | (uint64_t)word(w + 1) << 32;
-        double d;
-        __builtin_memcpy(&d, &u, 8);
-        return d;
-    }
-    __device__ __forceinline__ void set_dword(int w, double d) const {
-        uint64_t u;
-        __builtin_memcpy(&u, &d, 8);
-        set_word(w, (uint32_t)u);
-        set_word(w + 1, (uint32_t)(u >> 32));
-    }
-};
-
-// a generator as farm_env.hpp draws from it: single tempered words
-struct Rng {
-    MtStream s;
-    __device__ __forceinline__ Rng(uint32_t *block, uint32_t pos, uint32_t ready) : s(block, pos, ready) {}
-    __device__ __forceinline__ uint32_t next() { return s.next(); }
-};
-
-// 4 * (the env of this lane, or the last env for a lane past the end), in 32-bit arithmetic throughout
-__device__ __forceinline__ uint32_t lane_offset(int64_t n) {
-    const uint32_t i = blockIdx.x * (uint32_t)BLOCK + threadIdx.x, last = (uint32_t)n - 1u;
-    return (i < last ? i : last) * 4u;
-}
+using Cols = LaneCols;
+using Rng = LaneRng;
 
 __device__ __forceinline__ void load_env(Env &e, const Cols &c) {
     Env::each_double(e, [&](int w, double &v) __attribute__((always_inline)) { v = c.dword(w); });
@@ -200,7 +166,7 @@ __device__ __forceinline__ void run(const P &p) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     Rng rng(p.mt + li * MT_STRIDE, e.mt_pos, e.mt_ready), py(p.py + li * MT_STRIDE, e.py_pos, e.py_ready);
@@ -276,7 +242,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     const bool fresh = init || rewind, draws = live && (fresh || !p.mask || p.mask[li]);
@@ -296,7 +262,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
 __global__ __launch_bounds__(BLOCK) void info_kernel(Params p, int field, double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= p.n) return;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     out[i] = info_value(e, field);
@@ -316,6 +282,7 @@ struct cge_farm : LaneHandle {
     static constexpr const char *abi = "cge_farm", *kernel_ns = "cge::farm::", *rows_ns = kernel_ns;
     static constexpr int block = farm::BLOCK, seed_kind = 1;         // `mt`: np.random.seed; `py` is seeded as random.seed (kind 0)
     int row() const { return cfg.compact_obs ? farm::LIVE : farm::OBS; }
+    uintptr_t piece_mask() const { return cfg.compact_obs ? 7u : 15u; }   // rows leave as 16-byte pieces, compact ones as 8-byte pieces
     Params params() const {
         Params p{};
         fill(p);
@@ -325,15 +292,8 @@ struct cge_farm : LaneHandle {
         return p;
     }
     int64_t step_elems() const { return n * row(); }
-    auto reset_kernel() const { return farm::reset_kernel; }
-    template <int MODE>
-    auto kernel(LaneKind kind) const {
-        return kind == LANE_STEP ? farm::step_kernel<MODE>
-               : kind == LANE_ROLLOUT_GIVEN ? farm::rollout_kernel<MODE, true> : farm::rollout_kernel<MODE, false>;
-    }
-    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
-        hipLaunchKernelGGL(given ? farm::rollout_rows_kernel<true> : farm::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
-    }
+    CGE_LANE_KERNELS(farm)
+    CGE_LANE_LAUNCH_ROWS(farm)
     static int check(const cge_farm_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_years < 1 || c.max_years > 255 || c.compact_obs < 0 || c.compact_obs > 1 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
@@ -352,11 +312,6 @@ struct cge_farm : LaneHandle {
     }
 };
 
-// observation rows leave as 16-byte pieces, compact ones as 8-byte pieces
-static bool rows_aligned(const cge_farm *h, const void *a, const void *b) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & (h->cfg.compact_obs ? 7u : 15u)) == 0;
-}
-
 extern "C" {
 
 CGE_DEFINE_LIFECYCLE(farm)
@@ -370,30 +325,27 @@ int cge_farm_seed(cge_farm *h, const uint64_t *seeds, uint64_t base_seed, void *
 }
 
 int cge_farm_reset(cge_farm *h, const uint8_t *mask, float *obs_out, void *stream) {
-    if (h && !rows_aligned(h, obs_out, nullptr)) return h->fail(CGE_ERR_INVALID_ARG, "cge_farm_reset: obs must be 16-byte aligned (compact_obs: 8-byte)");
+    if (h && !rows_aligned(obs_out, nullptr, h->piece_mask())) return h->fail(CGE_ERR_INVALID_ARG, "cge_farm_reset: obs must be 16-byte aligned (compact_obs: 8-byte)");
     return lane_reset(h, mask, obs_out, stream);
 }
 
 int cge_farm_step(cge_farm *h, const int32_t *actions, float *obs_out, float *reward_out, uint8_t *terminated_out, uint8_t *truncated_out,
                   float *final_obs_out, void *stream) {
-    return lane_step(h, h && actions && obs_out && reward_out && terminated_out && rows_aligned(h, obs_out, final_obs_out),
+    return lane_step(h, h && actions && obs_out && reward_out && terminated_out && rows_aligned(obs_out, final_obs_out, h->piece_mask()),
                      "cge_farm_step: null actions/obs/reward/terminated pointer, or obs / final_obs not 16-byte aligned (compact_obs: 8-byte)", actions,
                      obs_out, reward_out, terminated_out, truncated_out, final_obs_out, stream);
 }
 
 int cge_farm_rollout(cge_farm *h, int32_t k_steps, const int32_t *actions, uint64_t action_seed, int64_t t0, float *obs_out, int64_t obs_step_stride,
                      float *reward_traj_out, uint8_t *terminated_traj_out, double *reward_sum_out, int32_t *done_count_out, void *stream) {
-    return lane_rollout(h, h && obs_step_stride % (h->cfg.compact_obs ? 2 : 4) == 0 && rows_aligned(h, obs_out, h->fin_rows),
+    return lane_rollout(h, h && obs_step_stride % (h->cfg.compact_obs ? 2 : 4) == 0 && rows_aligned(obs_out, h->fin_rows, h->piece_mask()),
                         "cge_farm_rollout: bad k_steps / obs_step_stride, or obs / the registered terminal rows not 16-byte aligned (compact_obs: 8-byte)", k_steps, actions, action_seed, t0, obs_out, obs_step_stride,
                         reward_traj_out, terminated_traj_out, reward_sum_out, done_count_out, stream);
 }
 
 int cge_farm_info(cge_farm *h, int32_t field_id, double *out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!out || field_id < 0 || field_id > CGE_FARM_INFO_WATER_QUALITY) return h->fail(CGE_ERR_INVALID_ARG, "cge_farm_info: bad field / null out");
-    DeviceGuard g(h->device);
-    hipLaunchKernelGGL(farm::info_kernel, dim3(lane_blocks(h)), dim3(farm::BLOCK), 0, as_stream(stream), h->params(), (int)field_id, out);
-    return launched(h);
+    return lane_info(h, out && field_id >= 0 && field_id <= CGE_FARM_INFO_WATER_QUALITY, "cge_farm_info: bad field / null out", farm::info_kernel, field_id, out,
+                     stream);
 }
 
 CGE_DEFINE_ROWS_FINAL_OBS(farm, float, 64)

@@ -7,7 +7,7 @@
 //   registers  the whole record: 83 float64 (modules 32, crew 18, systems 24, resources 5, battery, total power, the two returns),
 //              12 last_maintenance counters and the scalars.  What a runtime index reaches (a system, a module, a crew member) is
 //              written with a compare and a select per element (space_station_env.hpp: set_at), so no array is indexed in memory
-//   LDS        only the tile of the observation's store pass, 9,360 B a wave (none with -DCGE_STATION_LANE_ROWS)
+//   LDS        only the tile of the observation's store pass, 9,360 B a wave
 //   HBM        nothing is read or written per step but the outputs: the whole record is loaded at the start of a launch and stored at
 //              its end
 // Draws: NumPy's legacy random_sample / uniform / normal / choice on the env's own MT19937 stream (np.random.seed(s_i)).  Every step
@@ -19,9 +19,10 @@
 // test and the draws of a reset read their ready words singly.  A draw past the ready words twists word by word (MtStream).
 //
 // Observation: float32 [n, 120] row-major, 30 sixteen-byte pieces a row, in four groups (crew, systems, modules, the rest).  A group is
-// parked in LDS [element][env] and written with consecutive lanes on consecutive pieces of a row.  -DCGE_STATION_LANE_ROWS has each
-// lane store its own row as it computes it instead: the other form the rows can leave in, 2-4 % slower here — the opposite of the
-// airline and emergency types, whose records fill the LDS (profiles/space_station_timing.txt).
+// parked in LDS [element][env] and written with consecutive lanes on consecutive pieces of a row.  Each lane storing its own row as
+// it computes it, the other form the rows can leave in, is 2-4 % slower here — the opposite of the airline and emergency types,
+// whose records fill the LDS (profiles/space_station_timing.txt; that variant, -DCGE_STATION_LANE_ROWS, was last buildable at
+// commit 84dc52e).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -35,12 +36,8 @@ namespace station {
 constexpr int BLOCK = 64;        // one wave
 constexpr uint32_t READY = 192;  // words made ready at the top of a step
 constexpr int STG_COUNT = 36;    // floats of a row that leave together, at the most
-#ifndef CGE_STATION_LANE_ROWS
 constexpr int STG_ROW = BLOCK + 1;   // the store pass reads down a column: an odd row length spreads it over the banks
 constexpr int STG_FLOATS = STG_COUNT * STG_ROW;
-#else
-constexpr int STG_FLOATS = 1;
-#endif
 static_assert(OBS == CGE_SPACE_STATION_OBS_FLOATS && REC_WORDS * 4 == CGE_SPACE_STATION_RECORD_BYTES && ACTIONS == CGE_SPACE_STATION_ACTIONS, "cge_amd.h");
 static_assert(INFO_COUNT - 1 == CGE_SPACE_STATION_INFO_EVACUATED && INFO_AVG_CREW_HEALTH == CGE_SPACE_STATION_INFO_AVG_CREW_HEALTH, "cge_amd.h");
 
@@ -53,67 +50,8 @@ struct RowsParams : Params {                                         // rollout_
     FinalSeg fin;
 };
 
-// the env's columns: word w of env i at rec[w * n + i].  A scalar base plus ONE 32-bit byte offset per lane (4 * i: n_envs < 2^30)
-// addresses every column.  After fresh() the offset is a new value to the compiler: the addresses are formed again where they are
-// used (one add each) instead of being kept in registers from the loads of a launch to its stores.
-struct Cols {
-    uint32_t *rec;                                                   // uniform
-    int64_t n;
-    uint32_t off;
-    __device__ __forceinline__ void fresh() { asm volatile("" : "+v"(off)); }
-    __device__ __forceinline__ uint32_t word(int w) const { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(rec + (int64_t)w * n) + off); }
-    __device__ __forceinline__ void set_word(int w, uint32_t v) const { *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(rec + (int64_t)w * n) + off) = v; }
-    __device__ __forceinline__ double dword(int w) const {
-        const uint64_t u = (uint64_t)word(w) | (uint64_t)word(w + 1) << 32;
-        double d;
-        __builtin_memcpy(&d, &u, 8);
-        return d;
-    }
-    __device__ __forceinline__ void set_dword(int w, double d) const {
-        uint64_t u;
-        __builtin_memcpy(&u, &d, 8);
-        set_word(w, (uint32_t)u);
-        set_word(w + 1, (uint32_t)(u >> 32));
-    }
-};
-
-// the generator as space_station_env.hpp draws from it: single words, and runs of W words the caller consumes in order
-struct Rng {
-    MtStream s;
-    __device__ __forceinline__ Rng(uint32_t *block, uint32_t pos, uint32_t ready) : s(block, pos, ready) {}
-    __device__ __forceinline__ uint32_t next() { return s.next(); }
-    template <int W>
-    __device__ __forceinline__ void run(uint32_t (&w)[W]) {
-        static_assert(W % 4 == 0 && W <= MT_N, "whole 16-byte pieces");
-        if (s.pos + (uint32_t)W <= s.pretw) {
-            // ready: W / 4 independent loads; a piece that straddles word 623 runs into the mirror of words 0..2, which the twist of the
-            // next generation's first chunk has written
-#pragma unroll
-            for (int q = 0; q < W; q += 4) {
-                uint32_t at = s.pos + (uint32_t)q;
-                at -= at >= (uint32_t)MT_N ? (uint32_t)MT_N : 0u;
-                const MtQuad v = *reinterpret_cast<const MtQuad *>(s.w + at);
-                w[q] = mt_temper(v.a); w[q + 1] = mt_temper(v.b); w[q + 2] = mt_temper(v.c); w[q + 3] = mt_temper(v.d);
-            }
-            mt_advance(s.pos, s.pretw, (uint32_t)W);
-        } else {
-#pragma unroll
-            for (int j = 0; j < W; ++j) w[j] = 0u;
-#pragma unroll 1
-            for (int k = 0; k < W; ++k) {
-                const uint32_t y = s.next();
-#pragma unroll
-                for (int j = 0; j < W; ++j) w[j] = j == k ? y : w[j];   // no indexed register array
-            }
-        }
-    }
-};
-
-// 4 * (the env of this lane, or the last env for a lane past the end), in 32-bit arithmetic throughout
-__device__ __forceinline__ uint32_t lane_offset(int64_t n) {
-    const uint32_t i = blockIdx.x * (uint32_t)BLOCK + threadIdx.x, last = (uint32_t)n - 1u;
-    return (i < last ? i : last) * 4u;
-}
+using Cols = LaneCols;
+using Rng = LaneRng;
 
 __device__ __forceinline__ void load_env(Env &e, const Cols &c) {
     Env::each_double(e, [&](int w, double &v) __attribute__((always_inline)) { v = c.dword(w); });
@@ -133,7 +71,6 @@ __device__ __forceinline__ void store_env(const Env &e, const Cols &c) {
 template <int FIRST, int COUNT, class G>
 __device__ __forceinline__ void observe_group(float *__restrict__ stg, float *__restrict__ rows, int envs, int lane, bool live, G gen) {
     static_assert(FIRST % 4 == 0 && COUNT % 4 == 0 && COUNT <= STG_COUNT, "whole 16-byte pieces");
-#ifndef CGE_STATION_LANE_ROWS                                         // the group parked in LDS [element][env], written as consecutive pieces per env
     if (live) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + lane] = x; });
     __syncthreads();
     const int pieces = envs * (COUNT / 4);
@@ -144,15 +81,6 @@ __device__ __forceinline__ void observe_group(float *__restrict__ stg, float *__
         *reinterpret_cast<float4 *>(rows + (int64_t)env * OBS + FIRST + 4 * pc) = make_float4(s[0], s[STG_ROW], s[2 * STG_ROW], s[3 * STG_ROW]);
     }
     __syncthreads();                                                 // the tile is free for the next group
-#else                                                                 // the variant measured and dropped (profiles/space_station_timing.txt): every lane
-                                                                      // stores its own pieces of the group, 64 lanes 480 bytes apart
-    if (live) {
-        float v[COUNT];
-        gen([&](int k, float x) __attribute__((always_inline)) { v[k - FIRST] = x; });
-#pragma unroll
-        for (int q = 0; q < COUNT; q += 4) *reinterpret_cast<float4 *>(rows + (int64_t)lane * OBS + FIRST + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
-    }
-#endif
 }
 // _get_observation :739-783 of the wave's envs -> their rows of o [n, 120], 30 sixteen-byte pieces a row: crew (6 pieces), systems (9),
 // modules (8), the rest (7).  Call with every lane of the wave.
@@ -171,14 +99,10 @@ __device__ __forceinline__ void observe(const Env &e, float *__restrict__ stg, f
 // column `rank`, and the store pass writes `keep` dense rows at `rows`.  Call with every lane of the wave.
 template <int FIRST, int COUNT, class G>
 __device__ __forceinline__ void final_group(float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine, G gen) {
-#ifndef CGE_STATION_LANE_ROWS
     if (mine) gen([&](int k, float x) __attribute__((always_inline)) { stg[(k - FIRST) * STG_ROW + rank] = x; });
     __syncthreads();
     lane_store_tile<FIRST, COUNT, 4, STG_ROW>(stg, rows, OBS, keep);
     __syncthreads();                                                 // the tile is free for the next group
-#else
-    observe_group<FIRST, COUNT>(stg, rows, keep, rank, mine, gen);   // per-lane stores: the lane's row is row `rank`
-#endif
 }
 __device__ __forceinline__ void final_observe(const Env &e, float *__restrict__ stg, float *__restrict__ rows, int keep, int rank, bool mine) {
     final_group<0, 24>(stg, rows, keep, rank, mine, [&](auto out) __attribute__((always_inline)) { observe_crew(e, out); });
@@ -199,7 +123,7 @@ __device__ __forceinline__ void run(const P &p) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     Rng rng(p.mt + li * MT_STRIDE, e.mt_pos, e.mt_ready);
@@ -276,7 +200,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
     const int64_t i = (int64_t)blockIdx.x * BLOCK + lane;
     const bool live = i < p.n;
     const int64_t li = live ? i : p.n - 1;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     const bool fresh = init || rewind, draws = !fresh && live && (!p.mask || p.mask[li]);
@@ -296,7 +220,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Params p, int init, int re
 __global__ __launch_bounds__(BLOCK) void info_kernel(Params p, int field, double *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= p.n) return;
-    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_offset(p.n)};
+    Cols c{reinterpret_cast<uint32_t *>(p.state), p.n, lane_col_offset<BLOCK>(p.n)};
     Env e;
     load_env(e, c);
     out[i] = info_value(e, field);
@@ -321,15 +245,8 @@ struct cge_space_station : LaneHandle {
         return p;
     }
     int64_t step_elems() const { return n * station::OBS; }
-    auto reset_kernel() const { return station::reset_kernel; }
-    template <int MODE>
-    auto kernel(LaneKind kind) const {
-        return kind == LANE_STEP ? station::step_kernel<MODE>
-               : kind == LANE_ROLLOUT_GIVEN ? station::rollout_kernel<MODE, true> : station::rollout_kernel<MODE, false>;
-    }
-    void launch_rows(bool given, unsigned blocks, hipStream_t s, const RowsParams &p) const {
-        hipLaunchKernelGGL(given ? station::rollout_rows_kernel<true> : station::rollout_rows_kernel<false>, dim3(blocks), dim3(block), 0, s, p);
-    }
+    CGE_LANE_KERNELS(station)
+    CGE_LANE_LAUNCH_ROWS(station)
     static int check(const cge_space_station_config &c) {
         return bad_autoreset_mode(c.autoreset_mode) || c.max_steps < 1 || c.max_steps > 65535 ? CGE_ERR_INVALID_ARG : CGE_OK;
     }
@@ -342,9 +259,6 @@ struct cge_space_station : LaneHandle {
         return hipGetLastError();
     }
 };
-
-// observation rows leave as 16-byte pieces
-static bool rows_aligned(const void *a, const void *b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
 
 extern "C" {
 
@@ -374,11 +288,8 @@ int cge_space_station_rollout(cge_space_station *h, int32_t k_steps, const int32
 }
 
 int cge_space_station_info(cge_space_station *h, int32_t field_id, double *out, void *stream) {
-    if (!h) return CGE_ERR_INVALID_ARG;
-    if (!out || field_id < 0 || field_id > CGE_SPACE_STATION_INFO_EVACUATED) return h->fail(CGE_ERR_INVALID_ARG, "cge_space_station_info: bad field / null out");
-    DeviceGuard g(h->device);
-    hipLaunchKernelGGL(station::info_kernel, dim3(lane_blocks(h)), dim3(station::BLOCK), 0, as_stream(stream), h->params(), (int)field_id, out);
-    return launched(h);
+    return lane_info(h, out && field_id >= 0 && field_id <= CGE_SPACE_STATION_INFO_EVACUATED, "cge_space_station_info: bad field / null out", station::info_kernel,
+                     field_id, out, stream);
 }
 
 CGE_DEFINE_ROWS_FINAL_OBS(space_station, float, 64)

@@ -7,7 +7,7 @@
 five runs each after a warm-up run, reported as ranges, with the bytes each path moves per env-step, spelled out from the layout
 (DESIGN.md section 3.17), the time a device-to-device copy of the same bytes takes on this box (measured in this process on 2-GiB torch
 buffers: bytes read + written per second) and the ratio of the kernel time to it.  CGE_AMD_LIBRARY selects the library, so the
--DCGE_STATION_LANE_ROWS variant is timed by a second process of the same call.
+-DCGE_STATION_LANE_ROWS variant is timed by a second process of the same call.  That variant was last buildable at commit 84dc52e.
 
 `--log-caveat N`: no timing; resets N envs with seeds 0..N-1 and counts those whose float64 module state (the 32 values a reset draws
 through log) differs anywhere from `--host-file`, the same values from the host build of the same header
