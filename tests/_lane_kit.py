@@ -1,0 +1,547 @@
+"""The test kit of the four record-lane env types (airline, emergency, space station, farm): the helpers and the test bodies that
+tests/test_<type>_gpu.py and tests/test_<type>_cpu.py share.  A per-type file starts with one table of that type's values, SPEC, and
+keeps every test under its own name as a function of a line that hands SPEC to the body here: a test is found where it always was,
+by pytest and by whoever reads the file.  Where the copies of a body had drifted apart, the body here makes every assertion that any
+copy made.  Every comparison is array_equal on bit patterns or torch.equal and skips no rows.
+
+What a `spec` (a types.SimpleNamespace) holds:
+  m          the type's model module (tests/<type>_model.py)       kind     its name in csrc/ and tools/probes/ ("space_station")
+  env        the vector env's class name                           model    the model's class
+  limit      the constructor's step-limit keyword, or None         short    (fixture, limit): the one fixture recorded under a limit
+  obs        the row's width                                       actions  the number of actions
+  info       the reference's info keys in a fixture's order        clock    the info field that counts the steps
+  live       rows (of `rows` only) as the fixture holds them       bad      the two out-of-range actions next to -1 and the int32 ends
+and the fixture names, seeds, sizes and thresholds of the single tests, named after them."""
+import ctypes
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import _lane_env_pokes as lane_pokes
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP, fixture_obs, fixture_pokes
+from conftest import ROOT, golden
+
+MODES = {"NextStep": NEXT_STEP, "SameStep": SAME_STEP, "Disabled": DISABLED}
+ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
+       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+
+@pytest.fixture(scope="module")
+def cge():
+    import custom_gymnasium_environments_amd as m
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    m.native_lib()
+    return m
+
+
+def bits(x):
+    x = x.cpu().numpy() if isinstance(x, torch.Tensor) else np.ascontiguousarray(x)
+    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize]) if x.dtype.kind == "f" else x
+
+
+def same(a, b, what, rows=None):
+    a, b = bits(a), bits(b)
+    if rows is not None:
+        a, b = a[rows], b[rows]
+    assert a.shape == b.shape and np.array_equal(a, b), what
+
+
+def f32(x):
+    return np.asarray(x, np.float64).astype(np.float32)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
+
+
+def whole(obs, rows=None):
+    """`live` of a type whose fixtures hold the whole row"""
+    o = obs.cpu().numpy() if isinstance(obs, torch.Tensor) else obs
+    return o if rows is None else o[rows]
+
+
+def info_of(spec, env):
+    """float64 [n, columns]: the info fields in the order of a fixture's info row (a field of several columns takes that many)"""
+    return torch.cat([env.info(k).reshape(env.num_envs, -1) for k in spec.info], 1).cpu().numpy()
+
+
+def make(cge, spec, n, limit=None, **kw):
+    if limit is not None:
+        kw[spec.limit] = limit
+    return getattr(cge, spec.env)(n, **kw)
+
+
+def model(spec, seeds, mode, limit=None, **kw):
+    return spec.model(seeds, mode, *(() if limit is None else (limit,)), **kw)
+
+
+def recorded_limit(spec, z):
+    return int(z[spec.limit]) if spec.limit else None
+
+
+def host_check(spec):
+    return os.path.join(ROOT, "tools", "probes", spec.kind + "_host_check.py")
+
+
+def where_reset(z):
+    return {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
+
+
+# ---------------------------------------------------------------------------------------------------------------- fixture replays
+def replay_same_step(cge, spec, name, pokes=None):
+    """the fixture on the device, every step against the recorded reference rows bit for bit; pokes = {step: [(env, field, value)]} are
+    written into the record before that step.  Returns the resets seen and recorded."""
+    z = golden(name)
+    n, T = z["reward"].shape
+    ref = fixture_obs(z)
+    env = make(cge, spec, n, recorded_limit(spec, z), autoreset_mode="SameStep")
+    if spec.limit:
+        assert (name == spec.short[0]) == (getattr(env, spec.limit) == spec.short[1])
+    obs, _ = env.reset(seed=int(z["seed0"]))
+    same(spec.live(obs), z["obs0"], "reset")
+    if "info0" in z:
+        same(info_of(spec, env), z["info0"], "reset info")
+    where = where_reset(z)
+    acts = dev(z["actions"].T)
+    seen = 0
+    for t in range(T):
+        if pokes and t in pokes:
+            lane_pokes.apply(env, n, spec.kind, pokes[t])
+        obs, rew, term, trunc, infos = env.step(acts[t])
+        tm = term.cpu().numpy()
+        same(rew, f32(z["reward"][:, t]), t)
+        assert np.array_equal(tm, z["terminated"][:, t].astype(bool)), t
+        if "truncated" in z:
+            assert np.array_equal(trunc.cpu().numpy(), z["truncated"][:, t].astype(bool)), t
+        else:
+            assert not trunc.any(), t
+        assert np.array_equal(infos["_final_obs"].cpu().numpy(), tm)
+        o = spec.live(obs)
+        same(o, ref[:, t], (t, "obs"), ~tm)                               # the reference's step() returns the terminal observation ...
+        same(info_of(spec, env), z["info"][:, t], (t, "info"), ~tm)
+        if tm.any():
+            same(spec.live(infos["final_obs"], tm), ref[:, t][tm], (t, "final_obs"))   # ... which SAME_STEP hands over as final_obs
+        for i in np.flatnonzero(tm):                                      # and `obs` is what reset() then returned on the same stream(s)
+            seen += 1
+            same(o[i], z["reset_obs"][where[(int(i), t)]], (t, i))
+    assert env.invalid_action_count() == 0
+    env.close()
+    return seen, len(where)
+
+
+def fixtures_same_step(cge, spec, name):
+    seen, recorded = replay_same_step(cge, spec, name)
+    assert seen == recorded and (seen > 0 or name not in spec.ending)
+
+
+def disabled_with_masked_resets(cge, spec):
+    name, enough = spec.disabled
+    z = golden(name)
+    n, T = z["reward"].shape
+    ref = fixture_obs(z)
+    env = make(cge, spec, n, autoreset_mode="Disabled")
+    same(spec.live(env.reset(seed=int(z["seed0"]))[0]), z["obs0"], "reset")
+    where = where_reset(z)
+    acts = dev(z["actions"].T)
+    ends = 0
+    for t in range(T):
+        obs, rew, term, trunc, _ = env.step(acts[t])
+        tm = term.cpu().numpy()
+        same(spec.live(obs), ref[:, t], t); same(rew, f32(z["reward"][:, t]), t); same(info_of(spec, env), z["info"][:, t], (t, "info"))
+        assert np.array_equal(tm, z["terminated"][:, t].astype(bool)) and not trunc.any(), t
+        if tm.any():                                                      # the caller resets the ended envs: the reference's next reset()
+            o = spec.live(env.reset(options={"reset_mask": tm.astype(np.uint8)})[0])
+            for i in np.flatnonzero(tm):
+                ends += 1
+                same(o[i], z["reset_obs"][where[(int(i), t)]], (t, i))
+            same(o, ref[:, t], (t, "the others keep their rows"), ~tm)
+    assert ends == len(where) and enough(ends)
+    env.close()
+
+
+def overrun_fixture_steps_on_past_termination(cge, spec):
+    """Disabled, never reset (what runs nowhere else: the type's own test)"""
+    name, holds = spec.overrun
+    z = golden(name)
+    n, T = z["reward"].shape
+    ref = fixture_obs(z)
+    env = make(cge, spec, n, autoreset_mode="Disabled")
+    same(spec.live(env.reset(seed=int(z["seed0"]))[0]), z["obs0"], "reset")
+    acts = dev(z["actions"].T)
+    for t in range(0, T, 60):                                             # chunks of fused steps, every step compared
+        k = min(60, T - t)
+        traj, rt, tt, rs, dc = env.rollout(k, actions=acts[t:t + k], trajectory=True, per_step=True)
+        same(spec.live(traj), ref[:, t:t + k].transpose(1, 0, 2), t); same(rt, f32(z["reward"][:, t:t + k].T), t)
+        assert np.array_equal(tt.cpu().numpy(), z["terminated"][:, t:t + k].T.astype(bool)), t
+        same(info_of(spec, env), z["info"][:, t + k - 1], (t, "info"))
+    assert (env.info(spec.clock) == T).all() and holds(z)
+    env.close()
+    env = make(cge, spec, n, autoreset_mode="Disabled")                   # and step by step
+    env.reset(seed=int(z["seed0"]))
+    for t in range(T):
+        obs, rew, term, _, _ = env.step(acts[t])
+        same(spec.live(obs), ref[:, t], t); same(rew, f32(z["reward"][:, t]), t)
+        assert np.array_equal(term.cpu().numpy(), z["terminated"][:, t].astype(bool)), t
+    env.close()
+
+
+def hash_fixture_next_step_against_the_model(cge, spec):
+    name, enough = spec.next_step
+    z = golden(name)
+    n, T = z["reward"].shape
+    env = make(cge, spec, n, autoreset_mode="NextStep")
+    m = model(spec, int(z["seed0"]) + np.arange(n), NEXT_STEP)
+    same(env.reset(seed=int(z["seed0"]))[0], m.reset(), "reset")
+    acts = z["actions"].T.astype(np.int32)
+    ends = 0
+    for t in range(T):
+        obs, rew, term, _, _ = env.step(dev(acts[t]))
+        mo, mr, mt, _, _, mi = m.step(acts[t])
+        same(obs, mo, t); same(rew, f32(mr), t); same(info_of(spec, env), mi, (t, "info"))
+        assert np.array_equal(term.cpu().numpy(), mt), t
+        ends += int(mt.sum())
+    assert ends >= enough(n)
+    assert np.array_equal(env.info("needs_reset").cpu().numpy(), np.array([float(e.needs_reset) for e in m.envs]))
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- against the model
+def kernel_equals_the_model(cge, spec, n):
+    """a single lane, a partial wave, exactly one wave, one lane into the next, several waves (what the steps hold: the type's own test)"""
+    T, seed, limit, ends = spec.kernel
+    a_seed = 5
+    env = make(cge, spec, n, limit, autoreset_mode="SameStep", env_index0=1000)
+    m = model(spec, seed + 1000 + np.arange(n), SAME_STEP, limit)
+    same(env.reset(seed=seed)[0], m.reset(), "reset")
+    acts = spec.m.hash_actions(a_seed, T, n, env0=1000)
+    traj, rt, tt, rs, dc = env.rollout(T, action_seed=a_seed, trajectory=True, per_step=True)
+    traj, rt, tt = traj.cpu().numpy(), rt.cpu().numpy(), tt.cpu().numpy()
+    sums = np.zeros(n)
+    for t in range(T):
+        mo, mr, mt = m.step(acts[t])[:3]
+        same(traj[t], mo, t); same(rt[t], f32(mr), t)
+        assert np.array_equal(tt[t], mt), t
+        sums += f32(mr).astype(np.float64)
+    same(rs, sums, "reward_sum")
+    assert np.array_equal(dc.cpu().numpy(), tt.sum(0)) and (tt.sum(0) >= ends).all()
+    same(info_of(spec, env), m.info(), "info")
+    env.close()
+
+
+def out_of_range_and_negative_actions(cge, spec):
+    n = 130
+    env = make(cge, spec, n, autoreset_mode="SameStep")
+    m = model(spec, 2 + np.arange(n), SAME_STEP)
+    env.reset(seed=2); m.reset()
+    acts = spec.m.hash_actions(3, 40, n)
+    for t in range(10):
+        env.step(dev(acts[t])); m.step(acts[t])
+    env.check_actions()                                                   # nothing so far
+    bad_count = 0
+    for t in range(10, 40):
+        bad = acts[t].copy()
+        rows = np.arange(n) % 5 == t % 5
+        bad[rows] = [*spec.bad, -1, -(2 ** 31), 2 ** 31 - 1][t % 5]
+        obs, rew, term, _, _ = env.step(dev(bad))
+        mo, mr, mt = m.step(bad)[:3]                                      # the model takes no branch of the action and runs the rest of the step
+        same(obs, mo, t); same(rew, f32(mr), t)
+        assert np.array_equal(term.cpu().numpy(), mt), t
+        bad_count += int(rows.sum())
+    assert m.invalid == bad_count == 30 * 26 and env.invalid_action_count() == bad_count
+    assert env.invalid_action_count() == 0                                # reading clears it
+    two = acts[0].copy()
+    two[[3, 129]] = [spec.actions, -1]                                    # the last lane of the partial wave among them
+    env.step(dev(two))
+    with pytest.raises(ValueError, match="Invalid action in 2 env-step"):
+        env.check_actions()
+    env.check_actions()
+    env.close()
+
+
+def episode_statistics(cge, spec, mode):
+    T, limit, per_env, longest = spec.statistics
+    n = 66
+    env = make(cge, spec, n, limit, autoreset_mode=mode, record_episode_statistics=True)
+    m = model(spec, 5 + np.arange(n), MODES[mode], limit)
+    env.reset(seed=5); m.reset()
+    acts = spec.m.hash_actions(2, T, n)
+    ends = 0
+    for t in range(T):
+        _, rew, term, trunc, infos = env.step(dev(acts[t]))
+        _, mr, mt, mtr, _, _ = m.step(acts[t])
+        assert torch.equal(infos["_episode"], term) and np.array_equal(term.cpu().numpy(), mt) and np.array_equal(trunc.cpu().numpy(), mtr), t
+        same(infos["episode"]["r"], np.array([e.ep_r for e in m.envs]), t)    # the episode's own return
+        assert np.array_equal(infos["episode"]["l"].cpu().numpy(), np.array([e.ep_l for e in m.envs])), t
+        ends += int(mt.sum())
+    assert ends >= per_env * n and max(e.ep_l for e in m.envs) == longest
+    env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- twin against twin
+def rollout_equals_steps(cge, spec, mode, given):
+    seed, ks, limit, idle, enough = spec.rollout
+    n, a_seed = 130, 12
+    env, twin = (make(cge, spec, n, limit, autoreset_mode=mode) for _ in range(2))
+    env.reset(seed=seed); twin.reset(seed=seed)
+    t0 = ends = 0
+    for k in ks:                                                          # every rollout but the first starts mid-episode
+        acts = spec.m.hash_actions(a_seed, k, n, t0=t0)                   # what rollout(actions=None) stands for
+        if given and idle is not None:
+            acts[:, ::2] = idle                                           # every other env idles
+        acts = dev(acts)
+        traj, rt, tt, rs, dc = env.rollout(k, actions=acts if given else None, action_seed=a_seed, t0=t0, trajectory=True, per_step=True)
+        for t in range(k):
+            o, r, te, _, _ = twin.step(acts[t])
+            assert torch.equal(traj[t], o) and torch.equal(rt[t], r) and torch.equal(tt[t], te), (k, t)
+        assert torch.equal(rs, rt.double().sum(0)) and torch.equal(dc, tt.sum(0).int())
+        t0 += k
+        ends += int(dc.sum())
+    assert ends >= enough(n, given)
+    o1 = env.rollout(5, action_seed=a_seed, t0=t0)[0]                     # without a trajectory: the last step's rows
+    for t in range(5):
+        o2 = twin.step(dev(spec.m.hash_actions(a_seed, 1, n, t0=t0 + t)[0]))[0]
+    assert torch.equal(o1, o2)
+    for f in env.INFO_FIELDS:
+        assert torch.equal(env.info(f), twin.info(f)), f
+    env.close(); twin.close()
+
+
+def action_sampler_matches_host_sampling(cge, spec):
+    n = 130
+    env, twin = (make(cge, spec, n, autoreset_mode="SameStep") for _ in range(2))
+    env.reset(seed=1); twin.reset(seed=1)
+    sampler = env.action_sampler(3)
+    rng = np.random.default_rng(3)                                        # MultiDiscrete([actions] * n).sample() of a space seeded with 3
+    for t in range(spec.sampled_steps):
+        s = sampler.sample()
+        ref = (rng.random(n) * spec.actions).astype(np.int64)
+        assert s.dtype == torch.int32 and np.array_equal(s.cpu().numpy(), ref), t
+        r1, r2 = env.step(s), twin.step(dev(ref))
+        assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1]) and torch.equal(r1[2], r2[2]), t
+    env.close(); twin.close()
+
+
+def snapshot_round_trip_into_a_fresh_handle(cge, spec):
+    limit, mid_episode = spec.snapshot
+    n = 200
+    env = make(cge, spec, n, limit, autoreset_mode="SameStep")
+    env.reset(seed=8)
+    env.rollout(50, action_seed=4)
+    assert mid_episode(env)
+    fresh = make(cge, spec, n, limit, autoreset_mode="SameStep")
+    fresh.restore(env.snapshot())
+    acts = dev(spec.m.hash_actions(6, 40, n, t0=50))
+    ends = 0
+    for t in range(40):
+        r1, r2 = env.step(acts[t]), fresh.step(acts[t])
+        assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1]) and torch.equal(r1[2], r2[2]) and torch.equal(r1[3], r2[3]), t
+        ends += int(r1[2].sum())
+    assert ends > 0
+    for f in env.INFO_FIELDS:
+        assert torch.equal(env.info(f), fresh.info(f)), f
+    other = make(cge, spec, n + 1)
+    with pytest.raises(ValueError):
+        other.restore(env.snapshot())
+    env.close(); fresh.close(); other.close()
+
+
+def sharding_invariance(cge, spec):
+    n, k, limit, shards = spec.sharding
+    whole_batch = make(cge, spec, n, limit, autoreset_mode="SameStep")
+    kw = {spec.limit: limit} if limit is not None else {}
+    parts = [cge.make_sharded(getattr(cge, spec.env), n, rank=j, world_size=len(shards), local_rank=0, autoreset_mode="SameStep", **kw) for j in range(len(shards))]
+    assert [p.shard for p in parts] == shards
+    whole_batch.reset(seed=77)
+    tw, rw, cw, sw, dw = whole_batch.rollout(k, action_seed=9, trajectory=True, per_step=True)
+    for p in parts:
+        s = slice(p.shard[0], p.shard[0] + p.shard[1])
+        p.reset(seed=77)
+        tp, rp, cp, sp, dp = p.rollout(k, action_seed=9, trajectory=True, per_step=True)
+        assert torch.equal(tp, tw[:, s]) and torch.equal(rp, rw[:, s]) and torch.equal(cp, cw[:, s]) and torch.equal(sp, sw[s]) and torch.equal(dp, dw[s])
+        p.close()
+    assert int(dw.min()) >= 1
+    whole_batch.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- graph capture
+# the method of tests/test_graph_capture_gpu.py: reuse_buffers=True, a warm-up on a side stream, the calls captured into one
+# torch.cuda.CUDAGraph, replayed four times, every output compared with an eager twin that makes the same calls one by one
+REPLAYS = 4
+
+
+def _warm_up(fn):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        out = fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    return out
+
+
+def captured_steps_replay_and_match_an_eager_twin(cge, spec):
+    K, n = 32, 333
+    env = make(cge, spec, n, spec.captured_limit, autoreset_mode="SameStep", reuse_buffers=True)
+    twin = make(cge, spec, n, spec.captured_limit, autoreset_mode="SameStep")
+    env.reset(seed=9); twin.reset(seed=9)
+    acts = dev(spec.m.hash_actions(21, K, n))
+    w = _warm_up(lambda: env.step(acts[0]))
+    t0 = twin.step(acts[0])
+    assert torch.equal(w[0], t0[0]) and torch.equal(w[1], t0[1])
+    hist = {"obs": torch.empty((K, n, spec.obs), device="cuda"), "rew": torch.empty((K, n), device="cuda"), "term": torch.empty((K, n), dtype=torch.bool, device="cuda"),
+            "trunc": torch.empty((K, n), dtype=torch.bool, device="cuda")}
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for t in range(K):
+            ob, r, te, tr, _ = env.step(acts[t])
+            hist["obs"][t].copy_(ob); hist["rew"][t].copy_(r); hist["term"][t].copy_(te); hist["trunc"][t].copy_(tr)
+    ends = 0
+    for rep in range(REPLAYS):                                            # the same graph again: the state carries over, the actions repeat
+        g.replay()
+        torch.cuda.synchronize()
+        for t in range(K):
+            ob, r, te, tr, _ = twin.step(acts[t])
+            assert torch.equal(hist["obs"][t], ob) and torch.equal(hist["rew"][t], r) and torch.equal(hist["term"][t], te) and torch.equal(hist["trunc"][t], tr), (rep, t)
+        ends += int(hist["term"].sum())
+    assert ends > 0                                                       # in-kernel resets happened inside the graph
+    r1, r2 = env.step(acts[1]), twin.step(acts[1])
+    assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1])
+    env.close(); twin.close()
+
+
+def captured_rollout_replays_and_matches_an_eager_twin(cge, spec):
+    k, n = 24, 333
+    env = make(cge, spec, n, spec.captured_limit, autoreset_mode="SameStep", reuse_buffers=True)
+    twin = make(cge, spec, n, spec.captured_limit, autoreset_mode="SameStep")
+    env.reset(seed=6); twin.reset(seed=6)
+
+    def call(e):
+        return list(e.rollout(k, action_seed=77, t0=1000, trajectory=True, per_step=True))
+
+    w = _warm_up(lambda: call(env))
+    for x, y in zip(w, call(twin)):
+        assert torch.equal(x, y)
+    hist = [torch.empty_like(x) for x in w]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for dst, src in zip(hist, call(env)):
+            dst.copy_(src)
+    ends = 0
+    for rep in range(REPLAYS):
+        g.replay()
+        torch.cuda.synchronize()
+        for j, (x, y) in enumerate(zip(hist, call(twin))):
+            assert x.dtype == y.dtype and torch.equal(x, y), (rep, j)
+        ends += int(hist[4].sum())
+    assert ends > 0
+    env.close(); twin.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- without a GPU
+def model_reproduces_the_reference(spec, name):
+    z = golden(name)
+    n, T = z["reward"].shape
+    obs_ref = fixture_obs(z)
+    assert obs_ref.shape == (n, T, spec.recorded) and obs_ref.dtype == np.float32 and json.loads(str(z["info_keys"])) == spec.info_keys
+    autoreset = bool(int(z["autoreset"]))
+    m = model(spec, int(z["seed0"]) + np.arange(n), SAME_STEP if autoreset else DISABLED, recorded_limit(spec, z), **spec.model_kw)
+    assert np.array_equal(bits(m.reset()), bits(z["obs0"]))
+    if "info0" in z:
+        assert np.array_equal(bits(m.info()), bits(z["info0"]))
+    where = where_reset(z)
+    seen = 0
+    pokes = fixture_pokes(z)
+    assert bool(pokes) == (name == spec.poked)
+    for t in range(T):
+        for i, field, value in pokes.get(t, ()):                                           # what the generator set on the reference's env object
+            spec.m.poke(m.envs[i], field, value)
+        obs, reward, terminated, truncated, final, info = m.step(z["actions"][:, t])
+        assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
+        assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)), t
+        assert np.array_equal(truncated, z["truncated"][:, t].astype(bool)) if "truncated" in z else not truncated.any(), t
+        assert np.array_equal(bits(final), bits(obs_ref[:, t])), t                         # the reference's step() returns the terminal observation
+        assert np.array_equal(bits(info), bits(z["info"][:, t])), t                        # every info value, those of a terminal step too
+        for i in np.flatnonzero(terminated & autoreset):                                   # then reset() continues the env's stream(s)
+            seen += 1
+            assert np.array_equal(bits(obs[i]), bits(z["reset_obs"][where[(int(i), t)]])), (t, i)
+    assert seen == len(where) and m.invalid == 0
+    if not autoreset:
+        assert z["terminated"].any() and len(where) == 0                                   # stepped on past termination
+
+
+def hash_actions_equal_the_shared_hash(spec):
+    from _hash_actions import common
+    a = spec.m.hash_actions(77, 5, 6, t0=40, env0=1000)
+    assert a.shape == (5, 6) and a.dtype == np.int32
+    for t in range(5):
+        for i in range(6):
+            assert int(a[t, i]) == common.hash_action(77, 1000 + i, 40 + t, spec.actions, 0)
+    z = golden(spec.fixtures[0])                                                          # the type's hash fixture
+    assert np.array_equal(spec.m.hash_actions(int(z["a_seed"]), 30, len(z["actions"])).T, z["actions"][:, :30])
+
+
+def kernel_dynamics_replay_the_fixtures_on_the_host(spec):
+    """csrc/<type>_env.hpp — the record's packing, the draw order and the step logic the kernels run — compiled for the CPU (with glibc's
+    log where the type draws Gaussians) and replayed over every fixture: observations, rewards, flags and the float64 info values bit
+    for bit (tools/probes/<type>_host_check.py, which takes the PATH's host compiler or the clang++ behind hipcc: the test fails, it
+    does not skip, where neither is there)."""
+    out = subprocess.run([sys.executable, host_check(spec)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = [line for line in out.stdout.splitlines() if "mismatching" in line]
+    assert len(lines) == len(spec.fixtures) and all(line.endswith(" 0 mismatching steps") for line in lines), out.stdout
+
+
+def abi_is_declared_exported_and_bound(spec):
+    from custom_gymnasium_environments_amd import _native, build
+    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    prefix = f"cge_{spec.kind}_"
+    declared = set(re.findall(r"\b(" + prefix + r"[a-z0-9_]+)\s*\(", src))
+    assert declared == {prefix + fn for fn in ABI}
+    assert {n for n in _native.SIGNATURES if n.startswith(prefix)} == declared
+    build.build_native()
+    L = ctypes.CDLL(_native.LIB_PATH)
+    assert not [n for n in declared if not hasattr(L, n)]
+    config, size, fields = spec.config
+    config = getattr(_native, config)
+    assert ctypes.sizeof(config) == size and (fields is None or [f[0] for f in config._fields_] == fields)
+
+
+def no_cpu_path(spec):
+    import custom_gymnasium_environments_amd as cge
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(cge.NativeLibraryError):
+        getattr(cge, spec.env)(8)
+    with pytest.raises(cge.NativeLibraryError):
+        getattr(cge, spec.env)(8, device="cpu")
+
+
+def no_kernel_uses_scratch(spec, tmp_path):
+    """the condition of DESIGN.md §3.17 and §3.18: the record stays in registers.  The private-segment size of every kernel of the
+    type's namespace, read from the built library's code-object notes as tests/test_kernel_occupancy.py reads the register counts"""
+    from custom_gymnasium_environments_amd import build
+    lib = os.path.join(str(tmp_path), "lib.so")
+    shutil.copy(build.build_native(), lib)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", lib], cwd=str(tmp_path), check=True, capture_output=True)
+    found = {}
+    for f in sorted(os.listdir(str(tmp_path))):
+        if "amdgcn" not in f:
+            continue
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(str(tmp_path), f)], capture_output=True, text=True).stdout
+        for blk in notes.split("  - .agpr_count:")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", blk)
+            private = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
+            if name and private and spec.mangled in name.group(1):
+                found[name.group(1)] = int(private.group(1))
+    kinds = {k: [n for n in found if k in n] for k in ("11step_kernel", "14rollout_kernel", "12reset_kernel")}
+    assert len(kinds["11step_kernel"]) == 3 and len(kinds["14rollout_kernel"]) == 6 and len(kinds["12reset_kernel"]) == 1, sorted(found)
+    assert all(v == 0 for v in found.values()), found

@@ -22,7 +22,9 @@ import random
 
 import numpy as np
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
+import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP, LaneModel, fixture_obs  # noqa: F401
+
 INFO = ("on_time_performance", "passenger_satisfaction", "daily_revenue", "daily_costs", "current_hour")
 NA, NP, NF, NC = 25, 15, 150, 40
 ARRIVE = 0
@@ -42,16 +44,9 @@ AIRPORT_XY = [(700.0, 500.0), (300.0, 300.0), (1100.0, 300.0), (300.0, 700.0), (
 SCHEDULED, BOARDING, DEPARTED, CANCELLED, DELAYED_ACTION, DELAYED_NO_AIRCRAFT = range(6)
 
 
-def fixture_obs(z):
-    """float32 [n, T, 160] of a fixture (tests/golden/gen/gen_airline.py stores uint32 [n, 160, T] XORed along time)"""
-    return np.ascontiguousarray(np.bitwise_xor.accumulate(z["obs_xor"], axis=2).transpose(0, 2, 1)).view(np.float32)
-
-
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for: hash_action(a_seed, env0 + i, t0 + t, 45, 0)"""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([common.hash_actions_np(a_seed, env, t0 + t, 45, 0) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, 45, t0, env0, envs)
 
 
 class _Env:
@@ -234,47 +229,15 @@ class _Env:
         return [self.otp(), self.sat, 0.0, self.costs, self.h4 * 0.25]
 
 
-class AirlineModel:
-    """n envs, env i on the stream of seeds[i]; step() follows gymnasium's three autoreset modes."""
-
-    def __init__(self, seeds, mode=SAME_STEP):
-        self.envs = [_Env(s) for s in seeds]
-        self.n, self.mode = len(self.envs), mode
-        self.invalid = 0
-
-    def obs(self):
-        return np.stack([e.obs() for e in self.envs])
-
-    def reset(self, mask=None):
-        for i, e in enumerate(self.envs):
-            if mask is None or mask[i]:
-                e.reset()
-        return self.obs()
-
-    def info(self):
-        return np.array([e.info() for e in self.envs], np.float64)
+class AirlineModel(LaneModel):
+    """no truncation, and no other info than info(): step() returns zeros and those rows"""
+    ENV, INFO_COLUMNS, RETURN = _Env, len(INFO), "ret"
 
     def extra(self):
         """timestep, needs_reset, flights_in_air, delay_compensation, fuel_costs per env"""
         return np.array([[e.t, e.needs_reset, sum(e.fly), e.comp, e.fuel_costs] for e in self.envs], np.float64)
 
-    def step(self, actions):
-        """-> (obs, reward float64, terminated, final_obs); final_obs is the observation before any SameStep reset"""
-        reward, term = np.zeros(self.n, np.float64), np.zeros(self.n, bool)
-        final = np.zeros((self.n, 160), np.float32)
-        for i, e in enumerate(self.envs):
-            if self.mode == NEXT_STEP and e.needs_reset:
-                e.reset()
-                final[i] = e.obs()
-                continue
-            reward[i], term[i], bad = e.step(int(actions[i]))
-            self.invalid += bad
-            e.ret += reward[i]
-            final[i] = e.obs()
-            if term[i]:
-                e.ep_r, e.ep_l = e.ret, e.t
-                if self.mode == SAME_STEP:
-                    e.reset()
-                elif self.mode == NEXT_STEP:
-                    e.needs_reset = True
-        return self.obs(), reward, term, final
+    def _step_env(self, e, a):
+        reward, term, bad = e.step(a)
+        e.ret += reward
+        return reward, term, False, bad

@@ -13,6 +13,8 @@ import random
 
 import numpy as np
 
+import _lane_model
+
 NUM_STOPS, NUM_BUSES, BUS_CAPACITY, MAX_PASSENGERS, MAX_TIMESTEPS, MAX_DWELL_TIME, TRAVEL = 4, 4, 20, 150, 500, 10, 5
 NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("bus_stops", "bus_states", "bus_remaining_times", "bus_capacities", "bus_passenger_destinations", "stop_waiting_counts",
@@ -25,9 +27,7 @@ KEY_SHAPES = {"bus_stops": (4,), "bus_states": (4,), "bus_remaining_times": (4,)
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n, 4]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for — bus j of env i at step t takes
     hash_action(a_seed, env0 + i, t0 + t, 11, j).  envs: global env indices instead of env0 .. env0 + n - 1."""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([np.stack([common.hash_actions_np(a_seed, env, t0 + t, MAX_DWELL_TIME + 1, j) for j in range(NUM_BUSES)], axis=-1) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, (MAX_DWELL_TIME + 1,) * NUM_BUSES, t0, env0, envs)
 
 
 class BusModel:

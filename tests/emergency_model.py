@@ -28,7 +28,9 @@ import random
 
 import numpy as np
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
+import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP, LaneModel, fixture_obs  # noqa: F401
+
 INFO = ("active_emergencies", "total_casualties", "lives_saved", "emergencies_resolved", "avg_response_time", "termination_reason")
 OBS, NUM_ACTIONS, MAX_INC, NU = 276, 50, 20, 20
 FIRE, ACCIDENT, CHEMICAL, FLOOD, QUAKE, GAS, MEDICAL, UNREST = range(8)
@@ -43,16 +45,9 @@ ZONE_TYPES = {0: [(FIRE, 0.3), (MEDICAL, 0.4), (GAS, 0.2), (UNREST, 0.1)],      
 CASCADE_TYPE = {FIRE: FIRE, ACCIDENT: ACCIDENT, CHEMICAL: GAS, QUAKE: FIRE, GAS: FIRE}       # :440, the others MEDICAL
 
 
-def fixture_obs(z):
-    """float32 [n, T, 276] of a fixture (tests/golden/gen/gen_emergency.py stores uint32 [n, 276, T] XORed along time)"""
-    return np.ascontiguousarray(np.bitwise_xor.accumulate(z["obs_xor"], axis=2).transpose(0, 2, 1)).view(np.float32)
-
-
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for: hash_action(a_seed, env0 + i, t0 + t, 50, 0)"""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([common.hash_actions_np(a_seed, env, t0 + t, NUM_ACTIONS, 0) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, NUM_ACTIONS, t0, env0, envs)
 
 
 def pairwise_mean25(v):
@@ -327,48 +322,15 @@ class _Env:
         return [len(self.inc), self.casualties, self.lives, self.resolved, self.avg_rt(), self.reason]
 
 
-class EmergencyModel:
-    """n envs, env i on the stream of seeds[i]; step() follows gymnasium's three autoreset modes."""
-
-    def __init__(self, seeds, mode=SAME_STEP, max_timesteps=1440):
-        self.envs = [_Env(s, max_timesteps) for s in seeds]
-        self.n, self.mode = len(self.envs), mode
-        self.invalid = 0
-
-    def obs(self):
-        return np.stack([e.obs() for e in self.envs])
-
-    def reset(self, mask=None):
-        for i, e in enumerate(self.envs):
-            if mask is None or mask[i]:
-                e.reset()
-        return self.obs()
-
-    def info(self):
-        return np.array([e.info() for e in self.envs], np.float64)
+class EmergencyModel(LaneModel):
+    """EmergencyModel(seeds, mode, max_timesteps=1440); no truncation"""
+    ENV, INFO_COLUMNS, RETURN = _Env, len(INFO), "ret"
 
     def extra(self):
         """timestep, needs_reset, busy_units, mutual_aid_requested, national_guard_active, state_of_emergency per env"""
         return np.array([[e.t, e.needs_reset, sum(e.busy), e.mutual, e.guard, e.soe] for e in self.envs], np.float64)
 
-    def step(self, actions):
-        """-> (obs, reward float64, terminated, final_obs, info); final_obs / info are those before any SameStep reset"""
-        reward, term = np.zeros(self.n, np.float64), np.zeros(self.n, bool)
-        final = np.zeros((self.n, OBS), np.float32)
-        info = np.zeros((self.n, 6), np.float64)
-        for i, e in enumerate(self.envs):
-            if self.mode == NEXT_STEP and e.needs_reset:
-                e.reset()
-                final[i], info[i] = e.obs(), e.info()
-                continue
-            reward[i], term[i], bad = e.step(int(actions[i]))
-            self.invalid += bad
-            e.ret += reward[i]
-            final[i], info[i] = e.obs(), e.info()
-            if term[i]:
-                e.ep_r, e.ep_l = e.ret, e.t
-                if self.mode == SAME_STEP:
-                    e.reset()
-                elif self.mode == NEXT_STEP:
-                    e.needs_reset = True
-        return self.obs(), reward, term, final, info
+    def _step_env(self, e, a):
+        reward, term, bad = e.step(a)
+        e.ret += reward
+        return reward, term, False, bad

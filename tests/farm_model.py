@@ -13,12 +13,13 @@ farm_poked.npz, whose `pokes` table poke() applies.
 tests/test_farm_cpu.py pins the model to fixtures recorded from the unmodified reference; the GPU tests use it where the fixtures
 cannot reach.  Test infrastructure only: the product never imports it.
 """
-import json
 import random
 
 import numpy as np
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
+import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP, LaneModel, clip, fixture_obs, fixture_pokes  # noqa: F401
+
 INFO = ("day", "season", "year", "cash_flow", "total_revenue", "total_expenses", "profit_margin", "carbon_sequestered",
         "water_conservation_score", "biodiversity_index", "soil_health_trend")
 FIELD_INFO = ("field_crop", "field_stage", "field_health", "field_yield_potential")
@@ -47,27 +48,14 @@ FIELD_SIZE = (156, 156, 156, 157)
 INITIAL_CROP = (WHEAT, CORN, TOMATOES, -1)
 
 
-def fixture_obs(z):
-    """float32 [n, T, 134] of a fixture (tests/golden/gen/gen_farm.py stores uint32 [n, 134, T] XORed along time)"""
-    return np.ascontiguousarray(np.bitwise_xor.accumulate(z["obs_xor"], axis=2).transpose(0, 2, 1)).view(np.float32)
-
-
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for: hash_action(a_seed, env0 + i, t0 + t, 45, 0)"""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([common.hash_actions_np(a_seed, env, t0 + t, NUM_ACTIONS, 0) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, NUM_ACTIONS, t0, env0, envs)
 
 
 def mean4(v):
     """np.mean of 4 float64: below eight values NumPy's pairwise sum is a plain loop"""
     return (((v[0] + v[1]) + v[2]) + v[3]) / 4.0
-
-
-def clip(x, lo, hi):
-    """np.clip of a scalar: min(max(x, lo), hi) with C's `a > b ? a : b` and `a < b ? a : b`"""
-    t = x if x > lo else float(lo)
-    return t if t < hi else float(hi)
 
 
 def yield_modifier(crop, moisture, ph, npk, temperature, pest, disease):   # crop_data.py:226-282
@@ -443,53 +431,17 @@ def poke(env, name, value):
         setattr(env, attr, float(value))
 
 
-def fixture_pokes(z):
-    """{step: [(env, field name, value)]} of a fixture's `pokes` table (empty for a fixture without one)"""
-    out = {}
-    if "pokes" in z:
-        names = json.loads(str(z["poke_fields"]))
-        for i, t, k, value in z["pokes"]:
-            out.setdefault(int(t), []).append((int(i), names[int(k)], float(value)))
-    return out
-
-
-class FarmModel:
-    """n envs, env i on the two streams of seeds[i]; step() follows gymnasium's three autoreset modes."""
+class FarmModel(LaneModel):
+    """FarmModel(seeds, mode, max_years=1, width=OBS): on the two streams of seeds[i]; rows of `width` columns; no truncation"""
+    ENV, INFO_COLUMNS, LENGTH = _Env, INFO_COLUMNS, "day"
 
     def __init__(self, seeds, mode=SAME_STEP, max_years=1, width=OBS):
-        self.envs = [_Env(s, max_years) for s in seeds]
-        self.n, self.mode, self.width = len(self.envs), mode, width
-        self.invalid = 0
+        super().__init__(seeds, mode, max_years)
+        self.width = width
 
-    def obs(self):
-        return np.stack([e.obs(self.width) for e in self.envs])
+    def _obs(self, e):
+        return e.obs(self.width)
 
-    def reset(self, mask=None):
-        for i, e in enumerate(self.envs):
-            if mask is None or mask[i]:
-                e.reset()
-        return self.obs()
-
-    def info(self):
-        return np.array([e.info() for e in self.envs], np.float64)
-
-    def step(self, actions):
-        """-> (obs, reward float64, terminated, final_obs, info); final_obs / info are those before any SameStep reset"""
-        reward, term = np.zeros(self.n, np.float64), np.zeros(self.n, bool)
-        final = np.zeros((self.n, self.width), np.float32)
-        info = np.zeros((self.n, INFO_COLUMNS), np.float64)
-        for i, e in enumerate(self.envs):
-            if self.mode == NEXT_STEP and e.needs_reset:
-                e.reset()
-                final[i], info[i] = e.obs(self.width), e.info()
-                continue
-            reward[i], term[i], bad = e.step(int(actions[i]))
-            self.invalid += bad
-            final[i], info[i] = e.obs(self.width), e.info()
-            if term[i]:
-                e.ep_r, e.ep_l = e.ep_ret, e.day
-                if self.mode == SAME_STEP:
-                    e.reset()
-                elif self.mode == NEXT_STEP:
-                    e.needs_reset = True
-        return self.obs(), reward, term, final, info
+    def _step_env(self, e, a):
+        reward, term, bad = e.step(a)
+        return reward, term, False, bad

@@ -16,6 +16,8 @@ import random
 
 import numpy as np
 
+import _lane_model
+
 NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("waiting_customers", "waiter_status", "table_occupancy", "table_cleanliness", "kitchen_queue", "ready_orders", "current_timestep")
 KEY_SHAPES = {"waiting_customers": (50, 2), "waiter_status": (10, 3), "table_occupancy": (10,), "table_cleanliness": (10,),
@@ -31,9 +33,7 @@ DURATION = {SEAT: 2, SERVE: 1, CLEAN: 3}
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None, nvec=NVEC):
     """int32 [k, n, 4]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for — column c of env i at step t is
     hash_action(a_seed, env0 + i, t0 + t, nvec[c], c).  envs: global env indices instead of env0 .. env0 + n - 1."""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([np.stack([common.hash_actions_np(a_seed, env, t0 + t, nvec[c], c) for c in range(4)], axis=-1) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, nvec, t0, env0, envs)
 
 
 def busy_actions(a_seed, k, n, t0=0, env0=0):

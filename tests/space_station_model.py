@@ -11,13 +11,14 @@ overwritten before the crew update of the next step) and is kept as written.
 tests/test_space_station_cpu.py pins the model to fixtures recorded from the unmodified reference; the GPU tests use it where the
 fixtures cannot reach.  Test infrastructure only: the product never imports it.
 """
-import json
 import math
 import re
 
 import numpy as np
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
+import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP, LaneModel, clip, fixture_obs, fixture_pokes  # noqa: F401
+
 INFO = ("time_step", "day", "crew_alive", "system_failures", "emergency_count", "mission_success", "episode_reward", "battery_level", "avg_crew_health")
 OBS, NUM_ACTIONS, NM, NC, NS = 120, 40, 8, 6, 12
 POWER_DRAW = (500.0, 300.0, 400.0, 0.0, 600.0, 200.0, 100.0, 350.0, 50.0, 800.0, 250.0, 1000.0)           # :175-244
@@ -31,16 +32,9 @@ SOLAR_EFF = tuple(0.0 if 180 < 20.0 * k < 270 else max(0, COS_PHASE[k]) for k in
 RADIATION = tuple(0.3 + 0.2 * math.sin(math.radians(20.0 * k - 90)) if 90 < 20.0 * k < 270 else 0.2 for k in range(18))
 
 
-def fixture_obs(z):
-    """float32 [n, T, 120] of a fixture (tests/golden/gen/gen_space_station.py stores uint32 [n, 120, T] XORed along time)"""
-    return np.ascontiguousarray(np.bitwise_xor.accumulate(z["obs_xor"], axis=2).transpose(0, 2, 1)).view(np.float32)
-
-
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for: hash_action(a_seed, env0 + i, t0 + t, 40, 0)"""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([common.hash_actions_np(a_seed, env, t0 + t, NUM_ACTIONS, 0) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, NUM_ACTIONS, t0, env0, envs)
 
 
 def mean6(v):
@@ -60,12 +54,6 @@ def mean8(v):
 def mean12(v):
     """np.mean of 12 float64: the tree over the first eight, then the other four in turn"""
     return ((((sum8(v) + v[8]) + v[9]) + v[10]) + v[11]) / 12.0
-
-
-def clip(x, lo, hi):
-    """np.clip of a scalar: min(max(x, lo), hi) with C's `a > b ? a : b` and `a < b ? a : b`"""
-    t = x if x > lo else float(lo)
-    return t if t < hi else float(hi)
 
 
 class _Env:
@@ -331,53 +319,9 @@ def poke(env, name, value):
         setattr(env, name, float(value))
 
 
-def fixture_pokes(z):
-    """{step: [(env, field name, value)]} of a fixture's `pokes` table (empty for a fixture without one)"""
-    out = {}
-    if "pokes" in z:
-        names = json.loads(str(z["poke_fields"]))
-        for i, t, k, value in z["pokes"]:
-            out.setdefault(int(t), []).append((int(i), names[int(k)], float(value)))
-    return out
+class SpaceStationModel(LaneModel):
+    """SpaceStationModel(seeds, mode, max_steps=8640); the info rows are the reference's nine values and the failure mask"""
+    ENV, INFO_COLUMNS = _Env, len(INFO) + 1
 
-
-class SpaceStationModel:
-    """n envs, env i on the stream of seeds[i]; step() follows gymnasium's three autoreset modes."""
-
-    def __init__(self, seeds, mode=SAME_STEP, max_steps=8640):
-        self.envs = [_Env(s, max_steps) for s in seeds]
-        self.n, self.mode = len(self.envs), mode
-        self.invalid = 0
-
-    def obs(self):
-        return np.stack([e.obs() for e in self.envs])
-
-    def reset(self, mask=None):
-        for i, e in enumerate(self.envs):
-            if mask is None or mask[i]:
-                e.reset()
-        return self.obs()
-
-    def info(self):
-        return np.array([e.info() for e in self.envs], np.float64)
-
-    def step(self, actions):
-        """-> (obs, reward float64, terminated, truncated, final_obs, info); final_obs / info are those before any SameStep reset"""
-        reward, term, trunc = np.zeros(self.n, np.float64), np.zeros(self.n, bool), np.zeros(self.n, bool)
-        final = np.zeros((self.n, OBS), np.float32)
-        info = np.zeros((self.n, 10), np.float64)
-        for i, e in enumerate(self.envs):
-            if self.mode == NEXT_STEP and e.needs_reset:
-                e.reset()
-                final[i], info[i] = e.obs(), e.info()
-                continue
-            reward[i], term[i], trunc[i], bad = e.step(int(actions[i]))
-            self.invalid += bad
-            final[i], info[i] = e.obs(), e.info()
-            if term[i]:
-                e.ep_r, e.ep_l = e.ep_ret, e.t
-                if self.mode == SAME_STEP:
-                    e.reset()
-                elif self.mode == NEXT_STEP:
-                    e.needs_reset = True
-        return self.obs(), reward, term, trunc, final, info
+    def _step_env(self, e, a):
+        return e.step(a)

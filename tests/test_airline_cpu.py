@@ -5,52 +5,27 @@ and bound; there is no CPU path; the spaces are the reference's.
 
 The model and the kernels compute a weather system's distance as sqrt(dx*dx + dy*dy), the reference as sqrt(dx**2 + dy**2) through libm
 pow: the stated departure.  It is accepted because every recorded float32 observation below is reproduced."""
-import ctypes
 import json
 import os
-import re
-import subprocess
-import sys
+import types
 
 import numpy as np
 import pytest
 
+import _lane_kit as kit
 import airline_model as am
+from _lane_kit import bits
 from conftest import ROOT, golden
 
 FIXTURES = ["airline_hash.npz", "airline_dispatch.npz", "airline_cancel.npz", "airline_overrun.npz"]
-ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
-       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.uint32 if x.dtype == np.float32 else np.uint64)
+SPEC = types.SimpleNamespace(
+    m=am, kind="airline", env="AirlineVectorEnv", model=am.AirlineModel, model_kw={}, limit=None, actions=45,
+    fixtures=FIXTURES, poked=None, recorded=160, info_keys=list(am.INFO), config=("AirlineConfig", 8, None))
 
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_model_reproduces_the_reference(name):
-    z = golden(name)
-    n, T = z["reward"].shape
-    obs_ref = am.fixture_obs(z)
-    assert obs_ref.shape == (n, T, 160) and obs_ref.dtype == np.float32 and json.loads(str(z["info_keys"])) == list(am.INFO)
-    autoreset = bool(int(z["autoreset"]))
-    m = am.AirlineModel(int(z["seed0"]) + np.arange(n), am.SAME_STEP if autoreset else am.DISABLED)
-    assert np.array_equal(bits(m.reset()), bits(z["obs0"]))
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    seen = 0
-    for t in range(T):
-        obs, reward, terminated, final = m.step(z["actions"][:, t])
-        info = m.info()                                                 # (a terminated env of a SameStep model has been reset already)
-        assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
-        assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)), t
-        assert np.array_equal(bits(final), bits(obs_ref[:, t])), t                         # the reference's step() returns the terminal observation
-        live = ~terminated if autoreset else np.ones(n, bool)
-        assert np.array_equal(bits(info[live]), bits(z["info"][:, t][live])), t
-        for i in np.flatnonzero(terminated & autoreset):                                   # then reset() continues the env's stream
-            seen += 1
-            assert np.array_equal(bits(obs[i]), bits(z["reset_obs"][where[(int(i), t)]])), (t, i)
-    assert seen == len(where) and m.invalid == 0
+    kit.model_reproduces_the_reference(SPEC, name)
 
 
 def test_model_info_at_the_ends():
@@ -61,7 +36,7 @@ def test_model_info_at_the_ends():
     m.reset()
     ends = 0
     for t in range(T):
-        _, _, terminated, _ = m.step(z["actions"][:, t])
+        terminated = m.step(z["actions"][:, t])[2]
         assert np.array_equal(bits(m.info()), bits(z["info"][:, t])), t
         if terminated.any():
             ends += int(terminated.sum())
@@ -89,48 +64,21 @@ def test_fixtures_cover_what_they_are_for():
 
 
 def test_hash_actions_equal_the_shared_hash():
-    from _hash_actions import common
-    a = am.hash_actions(77, 5, 6, t0=40, env0=1000)
-    assert a.shape == (5, 6) and a.dtype == np.int32
-    for t in range(5):
-        for i in range(6):
-            assert int(a[t, i]) == common.hash_action(77, 1000 + i, 40 + t, 45, 0)
-    z = golden("airline_hash.npz")
-    assert np.array_equal(am.hash_actions(int(z["a_seed"]), 30, 16).T, z["actions"][:, :30])
+    kit.hash_actions_equal_the_shared_hash(SPEC)
 
 
 def test_kernel_dynamics_replay_the_fixtures_on_the_host():
-    """csrc/airline_env.hpp — the record's packing, the draw order and the step logic the kernels run — compiled for the CPU and replayed
-    over every fixture: observations, rewards, flags and info values bit for bit (tools/probes/airline_host_check.py, which takes the
-    PATH's host compiler or the clang++ behind hipcc: the test fails, it does not skip, where neither is there)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probes", "airline_host_check.py")], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [line for line in out.stdout.splitlines() if "mismatching" in line]
-    assert len(lines) == len(FIXTURES) and all(line.endswith(" 0 mismatching steps") for line in lines), out.stdout
+    """csrc/<type>_env.hpp compiled for the CPU and replayed over every fixture, bit for bit (tools/probes/<type>_host_check.py): the test
+    fails, it does not skip, where no host compiler is there"""
+    kit.kernel_dynamics_replay_the_fixtures_on_the_host(SPEC)
 
 
 def test_abi_is_declared_exported_and_bound():
-    from custom_gymnasium_environments_amd import _native, build
-    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(cge_airline_[a-z0-9_]+)\s*\(", src))
-    assert declared == {f"cge_airline_{fn}" for fn in ABI}
-    assert {n for n in _native.SIGNATURES if n.startswith("cge_airline_")} == declared
-    build.build_native()
-    L = ctypes.CDLL(_native.LIB_PATH)
-    assert not [n for n in declared if not hasattr(L, n)]
-    assert ctypes.sizeof(_native.AirlineConfig) == 8
+    kit.abi_is_declared_exported_and_bound(SPEC)
 
 
 def test_no_cpu_path():
-    import torch
-    import custom_gymnasium_environments_amd as cge
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    with pytest.raises(cge.NativeLibraryError):
-        cge.AirlineVectorEnv(8)
-    with pytest.raises(cge.NativeLibraryError):
-        cge.AirlineVectorEnv(8, device="cpu")
+    kit.no_cpu_path(SPEC)
 
 
 def test_spaces_equal_the_reference():

@@ -1,49 +1,41 @@
 """AirlineVectorEnv on the device against the unmodified reference (tests/golden/airline_*.npz) and, where the fixtures cannot reach,
 against the model that tests/test_airline_cpu.py pins to them (tests/airline_model.py).  Every comparison is array_equal on bit
 patterns and skips no rows; rewards are the reference's float64 values rounded to the float32 of the output buffer."""
+import types
+
 import numpy as np
 import pytest
 import torch
 
+import _lane_kit as kit
 import airline_model as am
+from _lane_kit import cge, dev, f32, same  # noqa: F401
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"NextStep": am.NEXT_STEP, "SameStep": am.SAME_STEP, "Disabled": am.DISABLED}
 PER_ENV = 1656 + 2560                                                     # the documented device bytes per env: record + generator
-
-
-@pytest.fixture(scope="module")
-def cge():
-    import custom_gymnasium_environments_amd as m
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    m.native_lib()
-    return m
-
-
-def bits(x):
-    x = x.cpu().numpy() if isinstance(x, torch.Tensor) else np.ascontiguousarray(x)
-    return x.view({4: np.uint32, 8: np.uint64}[x.dtype.itemsize]) if x.dtype.kind == "f" else x
-
-
-def same(a, b, what, rows=None):
-    a, b = bits(a), bits(b)
-    if rows is not None:
-        a, b = a[rows], b[rows]
-    assert a.shape == b.shape and np.array_equal(a, b), what
-
-
-def f32(x):
-    return np.asarray(x, np.float64).astype(np.float32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
+SAME_STEP_FIXTURES = ["airline_hash.npz", "airline_dispatch.npz", "airline_cancel.npz"]
+SPEC = types.SimpleNamespace(
+    m=am, kind="airline", env="AirlineVectorEnv", model=am.AirlineModel, limit=None, obs=160, actions=45, info=am.INFO, clock="timestep", live=kit.whole,
+    ending=SAME_STEP_FIXTURES,
+    disabled=("airline_cancel.npz", lambda ends: ends >= 16),
+    overrun=("airline_overrun.npz", lambda z: (z["wraps"] >= 4).all()),
+    next_step=("airline_hash.npz", lambda n: n),
+    kernel=(80, 3, None, 1),                                              # T, seed, limit, ends per env
+    bad=(45, 52),
+    rollout=(4, (7, 1, 80, 7), None, None, lambda n, given: 0),           # seed, k of every rollout, limit, the idling action, ends
+    sampled_steps=20,
+    # snapshot: the 40 steps cross the end on the clock of every env still in its first episode (an env that ended early within the
+    # 50 steps has no end in these 40)
+    snapshot=(None, lambda env: True),
+    statistics=(150, None, 2, 71),                                        # T, limit, ends per env, the longest episode
+    sharding=(333, 80, None, [(0, 167), (167, 166)]),                     # n, k, limit, the shards
+    captured_limit=None)
 
 
 def info5(env):
-    return np.stack([env.info(k).cpu().numpy() for k in am.INFO], 1)
+    return kit.info_of(SPEC, env)
 
 
 def test_surface(cge):
@@ -68,145 +60,34 @@ def test_surface(cge):
     env.close()
 
 
-@pytest.mark.parametrize("name", ["airline_hash.npz", "airline_dispatch.npz", "airline_cancel.npz"])
+@pytest.mark.parametrize("name", SAME_STEP_FIXTURES)
 def test_fixtures_same_step(cge, name):
-    z = golden(name)
-    n, T = z["reward"].shape
-    ref = am.fixture_obs(z)
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    obs, _ = env.reset(seed=int(z["seed0"]))
-    same(obs, z["obs0"], "reset")
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    acts = dev(z["actions"].T)
-    seen = 0
-    for t in range(T):
-        obs, rew, term, trunc, infos = env.step(acts[t])
-        tm = term.cpu().numpy()
-        same(rew, f32(z["reward"][:, t]), t)
-        assert not trunc.any() and np.array_equal(tm, z["terminated"][:, t].astype(bool)), t
-        assert np.array_equal(infos["_final_obs"].cpu().numpy(), tm)
-        same(obs, ref[:, t], (t, "obs"), ~tm)                             # the reference's step() returns the terminal observation ...
-        if tm.any():
-            same(infos["final_obs"], ref[:, t], (t, "final_obs"), tm)     # ... which SAME_STEP hands over as final_obs
-        o = obs.cpu().numpy()
-        for i in np.flatnonzero(tm):                                      # and `obs` is what reset() then returned on the same stream
-            seen += 1
-            same(o[i], z["reset_obs"][where[(int(i), t)]], (t, i))
-    assert seen == len(where) > 0 and env.invalid_action_count() == 0
-    env.close()
+    kit.fixtures_same_step(cge, SPEC, name)
 
 
 def test_cancel_fixture_disabled_with_masked_resets(cge):
-    z = golden("airline_cancel.npz")
-    n, T = z["reward"].shape
-    ref = am.fixture_obs(z)
-    env = cge.AirlineVectorEnv(n, autoreset_mode="Disabled")
-    same(env.reset(seed=int(z["seed0"]))[0], z["obs0"], "reset")
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    acts = dev(z["actions"].T)
-    ends = 0
-    for t in range(T):
-        obs, rew, term, _, _ = env.step(acts[t])
-        tm = term.cpu().numpy()
-        same(obs, ref[:, t], t); same(rew, f32(z["reward"][:, t]), t); same(info5(env), z["info"][:, t], (t, "info"))
-        assert np.array_equal(tm, z["terminated"][:, t].astype(bool)), t
-        if tm.any():                                                      # the caller resets the ended envs: the reference's next reset()
-            o = env.reset(options={"reset_mask": tm.astype(np.uint8)})[0].cpu().numpy()
-            for i in np.flatnonzero(tm):
-                ends += 1
-                same(o[i], z["reset_obs"][where[(int(i), t)]], (t, i))
-            same(o, ref[:, t], (t, "the others keep their rows"), ~tm)
-    assert ends == len(where) >= 16
-    env.close()
+    kit.disabled_with_masked_resets(cge, SPEC)
 
 
 def test_overrun_fixture_steps_on_past_termination(cge):
     """Disabled, never reset: the midnight wrap, maintenance events and the fuel floor run nowhere else."""
-    z = golden("airline_overrun.npz")
-    n, T = z["reward"].shape
-    ref = am.fixture_obs(z)
-    env = cge.AirlineVectorEnv(n, autoreset_mode="Disabled")
-    same(env.reset(seed=int(z["seed0"]))[0], z["obs0"], "reset")
-    acts = dev(z["actions"].T)
-    for t in range(0, T, 60):                                             # chunks of fused steps, every step compared
-        k = min(60, T - t)
-        traj, rt, tt, rs, dc = env.rollout(k, actions=acts[t:t + k], trajectory=True, per_step=True)
-        same(traj, ref[:, t:t + k].transpose(1, 0, 2), t); same(rt, f32(z["reward"][:, t:t + k].T), t)
-        assert np.array_equal(tt.cpu().numpy(), z["terminated"][:, t:t + k].T.astype(bool)), t
-        same(info5(env), z["info"][:, t + k - 1], (t, "info"))
-    assert (env.info("timestep") == T).all() and (z["wraps"] >= 4).all()
-    env.close()
-    env = cge.AirlineVectorEnv(n, autoreset_mode="Disabled")              # and step by step
-    env.reset(seed=int(z["seed0"]))
-    for t in range(T):
-        obs, rew, term, _, _ = env.step(acts[t])
-        same(obs, ref[:, t], t); same(rew, f32(z["reward"][:, t]), t)
-        assert np.array_equal(term.cpu().numpy(), z["terminated"][:, t].astype(bool)), t
-    env.close()
+    kit.overrun_fixture_steps_on_past_termination(cge, SPEC)
 
 
 def test_hash_fixture_next_step_against_the_model(cge):
-    z = golden("airline_hash.npz")
-    n, T = z["reward"].shape
-    env = cge.AirlineVectorEnv(n, autoreset_mode="NextStep")
-    m = am.AirlineModel(int(z["seed0"]) + np.arange(n), am.NEXT_STEP)
-    same(env.reset(seed=int(z["seed0"]))[0], m.reset(), "reset")
-    acts = z["actions"].T.astype(np.int32)
-    ends = 0
-    for t in range(T):
-        obs, rew, term, _, _ = env.step(dev(acts[t]))
-        mo, mr, mt, _ = m.step(acts[t])
-        same(obs, mo, t); same(rew, f32(mr), t)
-        assert np.array_equal(term.cpu().numpy(), mt), t
-        ends += int(mt.sum())
-    assert ends >= n
-    assert np.array_equal(env.info("needs_reset").cpu().numpy(), np.array([float(e.needs_reset) for e in m.envs]))
-    env.close()
+    kit.hash_fixture_next_step_against_the_model(cge, SPEC)
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 200])
 def test_kernel_equals_the_model(cge, n):
     """a single lane, a partial last wave, whole waves; 80 steps hold one end on the clock"""
-    T, a_seed = 80, 5
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep", env_index0=1000)
-    m = am.AirlineModel(3 + 1000 + np.arange(n), am.SAME_STEP)
-    same(env.reset(seed=3)[0], m.reset(), "reset")
-    acts = am.hash_actions(a_seed, T, n, env0=1000)
-    traj, rt, tt, rs, dc = env.rollout(T, action_seed=a_seed, trajectory=True, per_step=True)
-    traj, rt, tt = traj.cpu().numpy(), rt.cpu().numpy(), tt.cpu().numpy()
-    sums = np.zeros(n)
-    for t in range(T):
-        mo, mr, mt, _ = m.step(acts[t])
-        same(traj[t], mo, t); same(rt[t], f32(mr), t)
-        assert np.array_equal(tt[t], mt), t
-        sums += f32(mr).astype(np.float64)
-    same(rs, sums, "reward_sum")
-    assert np.array_equal(dc.cpu().numpy(), tt.sum(0)) and (tt.sum(0) >= 1).all()
-    env.close()
+    kit.kernel_equals_the_model(cge, SPEC, n)
 
 
 @pytest.mark.parametrize("mode", ["SameStep", "NextStep"])
 @pytest.mark.parametrize("given", [False, True])
 def test_rollout_equals_steps(cge, mode, given):
-    n, a_seed = 130, 12
-    env, twin = (cge.AirlineVectorEnv(n, autoreset_mode=mode) for _ in range(2))
-    env.reset(seed=4); twin.reset(seed=4)
-    t0 = 0
-    for k in (7, 1, 80, 7):                                               # every rollout but the first starts mid-episode
-        acts = dev(am.hash_actions(a_seed, k, n, t0=t0))
-        traj, rt, tt, rs, dc = env.rollout(k, actions=acts if given else None, action_seed=a_seed, t0=t0, trajectory=True, per_step=True)
-        for t in range(k):
-            o, r, te, _, _ = twin.step(acts[t])
-            assert torch.equal(traj[t], o) and torch.equal(rt[t], r) and torch.equal(tt[t], te), (k, t)
-        assert torch.equal(rs, rt.double().sum(0)) and torch.equal(dc, tt.sum(0).int())
-        t0 += k
-    o1 = env.rollout(5, action_seed=a_seed, t0=t0)[0]                     # without a trajectory: the last step's rows
-    for t in range(5):
-        o2 = twin.step(dev(am.hash_actions(a_seed, 1, n, t0=t0 + t)[0]))[0]
-    assert torch.equal(o1, o2)
-    for f in env.INFO_FIELDS:
-        assert torch.equal(env.info(f), twin.info(f)), f
-    env.close(); twin.close()
+    kit.rollout_equals_steps(cge, SPEC, mode, given)
 
 
 def test_rollout_replays_dispatch_in_chunks_with_info_parity(cge):
@@ -243,177 +124,33 @@ def test_rollout_replays_dispatch_in_chunks_with_info_parity(cge):
 
 
 def test_out_of_range_and_negative_actions(cge):
-    n = 130
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    m = am.AirlineModel(2 + np.arange(n), am.SAME_STEP)
-    env.reset(seed=2); m.reset()
-    acts = am.hash_actions(3, 40, n)
-    for t in range(10):
-        env.step(dev(acts[t])); m.step(acts[t])
-    env.check_actions()                                                   # nothing so far
-    bad_count = 0
-    for t in range(10, 40):
-        bad = acts[t].copy()
-        rows = np.arange(n) % 5 == t % 5
-        bad[rows] = [45, 52, -1, -(2 ** 31), 2 ** 31 - 1][t % 5]
-        obs, rew, term, _, _ = env.step(dev(bad))
-        mo, mr, mt, _ = m.step(bad)                                       # the model skips _process_action and runs the rest of the step
-        same(obs, mo, t); same(rew, f32(mr), t)
-        assert np.array_equal(term.cpu().numpy(), mt), t
-        bad_count += int(rows.sum())
-    assert m.invalid == bad_count == 30 * 26 and env.invalid_action_count() == bad_count
-    assert env.invalid_action_count() == 0                                # reading clears it
-    two = acts[0].copy()
-    two[[3, 129]] = [45, -1]                                              # the last lane of the partial wave among them
-    env.step(dev(two))
-    with pytest.raises(ValueError, match="Invalid action in 2 env-step"):
-        env.check_actions()
-    env.check_actions()
-    env.close()
+    kit.out_of_range_and_negative_actions(cge, SPEC)
 
 
 def test_action_sampler_matches_host_sampling(cge):
-    n = 130
-    env, twin = (cge.AirlineVectorEnv(n, autoreset_mode="SameStep") for _ in range(2))
-    env.reset(seed=1); twin.reset(seed=1)
-    sampler = env.action_sampler(3)
-    rng = np.random.default_rng(3)                                        # MultiDiscrete([45] * n).sample() of a space seeded with 3
-    for t in range(20):
-        s = sampler.sample()
-        ref = (rng.random(n) * 45).astype(np.int64)
-        assert s.dtype == torch.int32 and np.array_equal(s.cpu().numpy(), ref), t
-        r1, r2 = env.step(s), twin.step(dev(ref))
-        assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1]) and torch.equal(r1[2], r2[2]), t
-    env.close(); twin.close()
+    kit.action_sampler_matches_host_sampling(cge, SPEC)
 
 
 def test_snapshot_round_trip_into_a_fresh_handle(cge):
-    n = 200
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    env.reset(seed=8)
-    env.rollout(50, action_seed=4)
-    fresh = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    fresh.restore(env.snapshot())
-    acts = dev(am.hash_actions(6, 40, n, t0=50))
-    ends = 0
-    for t in range(40):                                                   # crosses the end on the clock of every env still in its first episode
-        r1, r2 = env.step(acts[t]), fresh.step(acts[t])
-        assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1]) and torch.equal(r1[2], r2[2]), t
-        ends += int(r1[2].sum())
-    assert ends > 0 and torch.equal(env.info("daily_costs"), fresh.info("daily_costs"))   # (an env that ended early within the 50 steps has no end in these 40)
-    other = cge.AirlineVectorEnv(n + 1)
-    with pytest.raises(ValueError):
-        other.restore(env.snapshot())
-    env.close(); fresh.close(); other.close()
+    kit.snapshot_round_trip_into_a_fresh_handle(cge, SPEC)
 
 
 @pytest.mark.parametrize("mode", ["SameStep", "NextStep"])
 def test_episode_statistics(cge, mode):
-    n, T = 66, 150
-    env = cge.AirlineVectorEnv(n, autoreset_mode=mode, record_episode_statistics=True)
-    m = am.AirlineModel(5 + np.arange(n), MODES[mode])
-    env.reset(seed=5); m.reset()
-    acts = am.hash_actions(2, T, n)
-    ends = 0
-    for t in range(T):
-        _, rew, term, _, infos = env.step(dev(acts[t]))
-        _, mr, mt, _ = m.step(acts[t])
-        assert torch.equal(infos["_episode"], term) and np.array_equal(term.cpu().numpy(), mt), t
-        same(infos["episode"]["r"], np.array([e.ep_r for e in m.envs]), t)
-        assert np.array_equal(infos["episode"]["l"].cpu().numpy(), np.array([e.ep_l for e in m.envs])), t
-        ends += int(mt.sum())
-    assert ends >= 2 * n and max(e.ep_l for e in m.envs) == 71
-    env.close()
+    kit.episode_statistics(cge, SPEC, mode)
 
 
 def test_sharding_invariance(cge):
-    n, k = 333, 80
-    whole = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    parts = [cge.make_sharded(cge.AirlineVectorEnv, n, rank=j, world_size=2, local_rank=0, autoreset_mode="SameStep") for j in range(2)]
-    assert [p.shard for p in parts] == [(0, 167), (167, 166)]
-    whole.reset(seed=77)
-    tw, rw, cw, sw, dw = whole.rollout(k, action_seed=9, trajectory=True, per_step=True)
-    for p in parts:
-        s = slice(p.shard[0], p.shard[0] + p.shard[1])
-        p.reset(seed=77)
-        tp, rp, cp, sp, dp = p.rollout(k, action_seed=9, trajectory=True, per_step=True)
-        assert torch.equal(tp, tw[:, s]) and torch.equal(rp, rw[:, s]) and torch.equal(cp, cw[:, s]) and torch.equal(sp, sw[s]) and torch.equal(dp, dw[s])
-        p.close()
-    assert int(dw.min()) >= 1
-    whole.close()
+    kit.sharding_invariance(cge, SPEC)
 
 
-# ---------------------------------------------------------------------------------------------------------------- graph capture
-# the method of tests/test_graph_capture_gpu.py: reuse_buffers=True, a warm-up on a side stream, the calls captured into one
-# torch.cuda.CUDAGraph, replayed four times, every output compared with an eager twin that makes the same calls one by one
-REPLAYS = 4
-
-
-def _warm_up(fn):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        out = fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    return out
-
-
+# graph capture: the method of tests/test_graph_capture_gpu.py (tests/_lane_kit.py)
 def test_captured_steps_replay_and_match_an_eager_twin(cge):
-    K, n = 32, 333
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
-    twin = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    env.reset(seed=9); twin.reset(seed=9)
-    acts = dev(am.hash_actions(21, K, n))
-    w = _warm_up(lambda: env.step(acts[0]))
-    t0 = twin.step(acts[0])
-    assert torch.equal(w[0], t0[0]) and torch.equal(w[1], t0[1])
-    hist = {"obs": torch.empty((K, n, 160), device="cuda"), "rew": torch.empty((K, n), device="cuda"), "term": torch.empty((K, n), dtype=torch.bool, device="cuda")}
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for t in range(K):
-            ob, r, te, _, _ = env.step(acts[t])
-            hist["obs"][t].copy_(ob); hist["rew"][t].copy_(r); hist["term"][t].copy_(te)
-    ends = 0
-    for rep in range(REPLAYS):                                            # the same graph again: the state carries over, the actions repeat
-        g.replay()
-        torch.cuda.synchronize()
-        for t in range(K):
-            ob, r, te, _, _ = twin.step(acts[t])
-            assert torch.equal(hist["obs"][t], ob) and torch.equal(hist["rew"][t], r) and torch.equal(hist["term"][t], te), (rep, t)
-        ends += int(hist["term"].sum())
-    assert ends > 0                                                       # in-kernel resets happened inside the graph
-    r1, r2 = env.step(acts[1]), twin.step(acts[1])
-    assert torch.equal(r1[0], r2[0]) and torch.equal(r1[1], r2[1])
-    env.close(); twin.close()
+    kit.captured_steps_replay_and_match_an_eager_twin(cge, SPEC)
 
 
 def test_captured_rollout_replays_and_matches_an_eager_twin(cge):
-    k, n = 24, 333
-    env = cge.AirlineVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
-    twin = cge.AirlineVectorEnv(n, autoreset_mode="SameStep")
-    env.reset(seed=6); twin.reset(seed=6)
-
-    def call(e):
-        return list(e.rollout(k, action_seed=77, t0=1000, trajectory=True, per_step=True))
-
-    w = _warm_up(lambda: call(env))
-    for x, y in zip(w, call(twin)):
-        assert torch.equal(x, y)
-    hist = [torch.empty_like(x) for x in w]
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for dst, src in zip(hist, call(env)):
-            dst.copy_(src)
-    ends = 0
-    for rep in range(REPLAYS):
-        g.replay()
-        torch.cuda.synchronize()
-        for j, (x, y) in enumerate(zip(hist, call(twin))):
-            assert x.dtype == y.dtype and torch.equal(x, y), (rep, j)
-        ends += int(hist[4].sum())
-    assert ends > 0
-    env.close(); twin.close()
+    kit.captured_rollout_replays_and_matches_an_eager_twin(cge, SPEC)
 
 
 def test_refusals(cge):
@@ -464,7 +201,7 @@ def test_one_million_envs(cge):
     assert not tt.any() and bool((traj[:, :, 152] == hours[:, None]).all())
     sub, rsub = traj[:, sidx].cpu().numpy(), rt[:, sidx].cpu().numpy()
     for j in range(T):
-        mo, mr, mt, _ = m.step(acts[j])
+        mo, mr, mt = m.step(acts[j])[:3]
         same(sub[j], mo, j); same(rsub[j], f32(mr), j)
         assert not mt.any()
     env.close()

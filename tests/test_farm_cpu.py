@@ -3,62 +3,35 @@ recorded (tests/golden/farm_*.npz, written by tests/golden/gen/gen_farm.py), the
 termination included; the kernels' own dynamics code, built for the host, does too, sums its means in NumPy's order, carries Python's
 stage durations and draws the two streams as NumPy and CPython do; the C ABI is declared, exported and bound; there is no CPU path;
 the spaces are the reference's; no kernel of the type uses scratch."""
-import ctypes
 import json
 import os
 import random
 import re
-import shutil
 import subprocess
 import sys
+import types
 
 import numpy as np
 import pytest
 
+import _lane_kit as kit
 import farm_model as fm
+from _lane_kit import bits
 from conftest import ROOT, golden
 
 OLD_FIXTURES = ["farm_hash.npz", "farm_bankrupt.npz", "farm_orchard.npz", "farm_chores.npz", "farm_overrun.npz", "farm_two_years.npz"]
 FIXTURES = OLD_FIXTURES + ["farm_soil.npz", "farm_poked.npz"]
-ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
-       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
-HOST_CHECK = os.path.join(ROOT, "tools", "probes", "farm_host_check.py")
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.uint32 if x.dtype == np.float32 else np.uint64)
+SPEC = types.SimpleNamespace(
+    m=fm, kind="farm", env="AgriculturalFarmVectorEnv", model=fm.FarmModel, model_kw=dict(width=fm.LIVE), limit="max_years", actions=45,
+    fixtures=FIXTURES, poked="farm_poked.npz", recorded=fm.LIVE,
+    info_keys=list(fm.INFO) + [f"{k}_{f}" for k in fm.FIELD_INFO for f in range(4)],      # the eleven values and field_status
+    config=("FarmConfig", 16, ["autoreset_mode", "max_years", "compact_obs", "reserved"]), mangled="3cge4farm")
+HOST_CHECK = kit.host_check(SPEC)
 
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_model_reproduces_the_reference(name):
-    z = golden(name)
-    n, T = z["reward"].shape
-    obs_ref = fm.fixture_obs(z)
-    assert obs_ref.shape == (n, T, fm.LIVE) and obs_ref.dtype == np.float32
-    assert json.loads(str(z["info_keys"])) == list(fm.INFO) + [f"{k}_{f}" for k in fm.FIELD_INFO for f in range(4)]
-    autoreset = bool(int(z["autoreset"]))
-    m = fm.FarmModel(int(z["seed0"]) + np.arange(n), fm.SAME_STEP if autoreset else fm.DISABLED, int(z["max_years"]), width=fm.LIVE)
-    assert np.array_equal(bits(m.reset()), bits(z["obs0"])) and np.array_equal(bits(m.info()), bits(z["info0"]))
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    seen = 0
-    pokes = fm.fixture_pokes(z)
-    assert bool(pokes) == (name == "farm_poked.npz")
-    for t in range(T):
-        for i, field, value in pokes.get(t, ()):                                           # what the generator set on the reference's env object
-            fm.poke(m.envs[i], field, value)
-        obs, reward, terminated, final, info = m.step(z["actions"][:, t])
-        assert np.array_equal(bits(reward), bits(z["reward"][:, t])), t                    # float64, bit for bit
-        assert np.array_equal(terminated, z["terminated"][:, t].astype(bool)), t
-        assert np.array_equal(bits(final), bits(obs_ref[:, t])), t                         # the reference's step() returns the terminal observation
-        assert np.array_equal(bits(info), bits(z["info"][:, t])), t                        # the eleven values and field_status
-        for i in np.flatnonzero(terminated & autoreset):                                   # then reset() continues the env's streams
-            seen += 1
-            assert np.array_equal(bits(obs[i]), bits(z["reset_obs"][where[(int(i), t)]])), (t, i)
-    assert seen == len(where) and m.invalid == 0
-    if not autoreset:
-        assert z["terminated"].any() and len(where) == 0                                   # stepped on past termination
+    kit.model_reproduces_the_reference(SPEC, name)
 
 
 def test_model_pads_the_row_with_zeros():
@@ -147,25 +120,13 @@ def test_fixtures_cover_what_they_are_for():
 
 
 def test_hash_actions_equal_the_shared_hash():
-    from _hash_actions import common
-    a = fm.hash_actions(77, 5, 6, t0=40, env0=1000)
-    assert a.shape == (5, 6) and a.dtype == np.int32
-    for t in range(5):
-        for i in range(6):
-            assert int(a[t, i]) == common.hash_action(77, 1000 + i, 40 + t, 45, 0)
-    z = golden("farm_hash.npz")
-    assert np.array_equal(fm.hash_actions(int(z["a_seed"]), 30, 8).T, z["actions"][:, :30])
+    kit.hash_actions_equal_the_shared_hash(SPEC)
 
 
 def test_kernel_dynamics_replay_the_fixtures_on_the_host():
-    """csrc/farm_env.hpp — the record's packing, the draw order of both streams and the step logic the kernels run — compiled for the
-    CPU (with glibc's log) and replayed over every fixture: observations, rewards, the flag and the float64 info values bit for bit
-    (tools/probes/farm_host_check.py, which takes the PATH's host compiler or the clang++ behind hipcc: the test fails, it does not
-    skip, where neither is there)."""
-    out = subprocess.run([sys.executable, HOST_CHECK], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [line for line in out.stdout.splitlines() if "mismatching" in line]
-    assert len(lines) == len(FIXTURES) and all(line.endswith(" 0 mismatching steps") for line in lines), out.stdout
+    """csrc/<type>_env.hpp compiled for the CPU and replayed over every fixture, bit for bit (tools/probes/<type>_host_check.py): the test
+    fails, it does not skip, where no host compiler is there"""
+    kit.kernel_dynamics_replay_the_fixtures_on_the_host(SPEC)
 
 
 def test_mean_of_four_is_summed_in_numpys_order():
@@ -277,27 +238,11 @@ def test_poke_helper_changes_exactly_the_named_field():
 
 
 def test_abi_is_declared_exported_and_bound():
-    from custom_gymnasium_environments_amd import _native, build
-    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(cge_farm_[a-z0-9_]+)\s*\(", src))
-    assert declared == {f"cge_farm_{fn}" for fn in ABI}
-    assert {n for n in _native.SIGNATURES if n.startswith("cge_farm_")} == declared
-    build.build_native()
-    L = ctypes.CDLL(_native.LIB_PATH)
-    assert not [n for n in declared if not hasattr(L, n)]
-    assert ctypes.sizeof(_native.FarmConfig) == 16 and [f[0] for f in _native.FarmConfig._fields_] == ["autoreset_mode", "max_years", "compact_obs", "reserved"]
+    kit.abi_is_declared_exported_and_bound(SPEC)
 
 
 def test_no_cpu_path():
-    import torch
-    import custom_gymnasium_environments_amd as cge
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    with pytest.raises(cge.NativeLibraryError):
-        cge.AgriculturalFarmVectorEnv(8)
-    with pytest.raises(cge.NativeLibraryError):
-        cge.AgriculturalFarmVectorEnv(8, device="cpu")
+    kit.no_cpu_path(SPEC)
 
 
 def test_spaces_equal_the_reference():
@@ -316,22 +261,6 @@ def test_spaces_equal_the_reference():
 
 
 def test_no_kernel_uses_scratch(tmp_path):
-    """the condition of DESIGN.md §3.18: the record stays in registers.  The private-segment size of every cge::farm kernel, read from
-    the built library's code-object notes as tests/test_kernel_occupancy.py reads the register counts"""
-    from custom_gymnasium_environments_amd import build
-    lib = os.path.join(str(tmp_path), "lib.so")
-    shutil.copy(build.build_native(), lib)
-    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", lib], cwd=str(tmp_path), check=True, capture_output=True)
-    found = {}
-    for f in sorted(os.listdir(str(tmp_path))):
-        if "amdgcn" not in f:
-            continue
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(str(tmp_path), f)], capture_output=True, text=True).stdout
-        for blk in notes.split("  - .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", blk)
-            private = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
-            if name and private and "3cge4farm" in name.group(1):
-                found[name.group(1)] = int(private.group(1))
-    kinds = {k: [n for n in found if k in n] for k in ("11step_kernel", "14rollout_kernel", "12reset_kernel")}
-    assert len(kinds["11step_kernel"]) == 3 and len(kinds["14rollout_kernel"]) == 6 and len(kinds["12reset_kernel"]) == 1, sorted(found)
-    assert all(v == 0 for v in found.values()), found
+    """the condition of DESIGN.md §3.18: the record stays in registers.  The private-segment size of every cge::farm kernel, read from the
+    built library's code-object notes as tests/test_kernel_occupancy.py reads the register counts"""
+    kit.no_kernel_uses_scratch(SPEC, tmp_path)

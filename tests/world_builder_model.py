@@ -9,6 +9,8 @@ Env i draws from `np.random.RandomState(seeds[i])`: the legacy stream `np.random
 """
 import numpy as np
 
+import _lane_model
+
 NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("grid", "resources", "population_capacity", "win_steps")
 MAX_POPULATION, WIN_STEPS = 20, 50                                         # world_builder_env.py:45-46
@@ -35,9 +37,7 @@ def pack_state(header, grid, key):
 
 def hash_actions(a_seed, k, n, t0=0, env0=0, envs=None):
     """int32 [k, n]: the actions `rollout(k, action_seed=a_seed, t0=t0)` stands for: hash_action(a_seed, env0 + i, t0 + t, 5, 0)."""
-    from _hash_actions import common
-    env = np.arange(env0, env0 + n, dtype=np.uint64) if envs is None else np.asarray(envs, dtype=np.uint64)
-    return np.stack([common.hash_actions_np(a_seed, env, t0 + t, 5) for t in range(k)])
+    return _lane_model.hash_actions(a_seed, k, n, 5, t0, env0, envs)
 
 
 def flatten(obs):

@@ -1,41 +1,19 @@
 """Replays every restaurant fixture through the kernels' own dynamics code compiled for the CPU (csrc/restaurant_env.hpp, driven by
 restaurant_host_check.cpp): the check of the record and of the step logic that needs no GPU.  `-fsanitize` on the host build finds an
-index out of range in the record's arrays before a kernel could.  Usage: python tools/probes/restaurant_host_check.py [--sanitize]"""
+index out of range in the record's arrays before a kernel could.  The build and the driver are those of the record-lane types
+(tools/probes/lane_host_check.py); the binary file is the type's own.  Usage: python tools/probes/restaurant_host_check.py [--sanitize]"""
 import os
 import random
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lane_host_check  # noqa: E402
+from lane_host_check import ROOT  # noqa: E402
+
 KEYS = ("waiting_customers", "waiter_status", "table_occupancy", "table_cleanliness", "kitchen_queue", "ready_orders")
 FIXTURES = ("restaurant_hash", "restaurant_busy", "restaurant_short", "restaurant_short40", "restaurant_long")
-
-
-def host_compiler():
-    """g++ / c++ / clang++ from the PATH, else the clang++ that hipcc itself drives (the build needs ROCm anyway)."""
-    for cc in ("g++", "c++", "clang++"):
-        if shutil.which(cc):
-            return cc
-    rocm = os.path.join(os.path.dirname(os.path.dirname(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))), "llvm", "bin", "clang++")
-    if os.path.exists(rocm):
-        return rocm
-    raise RuntimeError("no host C++ compiler found (g++, c++, clang++, ROCm's clang++)")
-
-
-OPT = ["-O1"]
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-
-
-def build(outdir, flags=OPT, compiler=None):
-    """the host program, built into outdir with the given compiler flags; returns its path"""
-    exe = os.path.join(outdir, "check")
-    subprocess.run([compiler or host_compiler(), *flags, "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tools", "probes", "restaurant_host_check.cpp"), "-o", exe],
-                   check=True)
-    return exe
 
 
 def write_fixture(name, outdir):
@@ -57,12 +35,7 @@ def write_fixture(name, outdir):
     return path
 
 
-def main():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp, OPT + (SANITIZE if "--sanitize" in sys.argv else []))
-        for name in FIXTURES:
-            subprocess.run([exe, write_fixture(name, tmp)], check=True)
-
+build, write_fixture, main = lane_host_check.bind("restaurant", FIXTURES, writer=write_fixture)
 
 if __name__ == "__main__":
     main()
