@@ -29,6 +29,7 @@ class CryptoVectorEnv(DeviceVectorEnv):
     """
 
     _abi = "cge_crypto"
+    _seed_bits = 32   # np.random.seed(s_i)
     INFO_FIELDS = INFO_FIELDS
     metadata = {"render_modes": []}
 

@@ -128,6 +128,24 @@ int launched(H *h) {
     return CGE_OK;
 }
 
+// Head of cge_<env>_seed on the base path (seeds == NULL): the last env's seed is base_seed + env0 + n - 1, which must not pass the
+// limit of the type's generator — 2**32 - 1 where a NumPy legacy stream is seeded (np.random.seed raises above it), 2**64 - 1
+// elsewhere (the kernels form the sum in uint64_t; a third 32-bit limb is not implemented).  Host arithmetic, before any launch: a
+// refused call seeds nothing.  A `seeds` array lives on the device and stays the caller's duty.  Returns CGE_OK or the failure.
+template <class H>
+int seed_base_check(H *h, const char *fn, const uint64_t *seeds, uint64_t base_seed, bool numpy_legacy) {
+    if (seeds) return CGE_OK;
+    const uint64_t limit = numpy_legacy ? 0xFFFFFFFFull : ~0ull;
+    const uint64_t last = (uint64_t)h->env0 + (uint64_t)h->n - 1;      // create_handle: env0 >= 0, n >= 1
+    if (last < (uint64_t)h->env0 || last > limit || base_seed > limit - last) {
+        char buf[256];
+        snprintf(buf, sizeof buf, numpy_legacy ? "%s: base_seed + env_index0 + n_envs - 1 must be between 0 and 2**32 - 1 (np.random.seed raises above it)"
+                                               : "%s: base_seed + env_index0 + n_envs - 1 must be between 0 and 2**64 - 1", fn);
+        return h->fail(CGE_ERR_INVALID_ARG, buf);
+    }
+    return CGE_OK;
+}
+
 // cge_<env>_create / _destroy.  An env type's handle H supplies what is its own:
 //   static int check(const config &)   the status of a config it cannot run (CGE_OK: fine); runs before the device is looked at
 //   hipError_t init()                  defaults, derived fields, alloc() of every device array, initial seed and reset launches

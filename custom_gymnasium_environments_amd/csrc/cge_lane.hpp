@@ -306,6 +306,7 @@ int lane_refuse_actions(H *h, const char *fn, const char *why) {
 template <class H>
 int lane_seed(H *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, (std::string(H::abi) + "_seed").c_str(), seeds, base_seed, H::seed_kind == 1)) return st;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, H::seed_kind, as_stream(stream)));
     lane_launch_reset(h, h->params(), 0, 1, as_stream(stream));

@@ -302,6 +302,7 @@ CGE_DEFINE_LIFECYCLE(climate)
 
 int cge_climate_seed(cge_climate *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_climate_seed", seeds, base_seed, false)) return st;
     DeviceGuard g(h->device);
     climate::Params p = h->params();
     p.seeds = seeds; p.base_seed = base_seed;

@@ -1237,9 +1237,8 @@ CGE_DEFINE_LIFECYCLE(crypto)
 
 int cge_crypto_seed(cge_crypto *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_crypto_seed", seeds, base_seed, true)) return st;
     DeviceGuard g(h->device);
-    if (!seeds && base_seed + (uint64_t)(h->env0 + h->n) > 0x100000000ull)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_crypto_seed: np.random.seed needs seeds < 2**32");
     CGE_TRY(h, launch_mt_seed(h->mtP, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     CGE_TRY(h, launch_mt_seed(h->mtL, MT_STRIDE, h->n, seeds, base_seed, h->env0, 1, as_stream(stream)));
     hipLaunchKernelGGL(crypto::init_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->scal, h->n, h->cfg.initial_balance, 1);

@@ -318,6 +318,7 @@ CGE_DEFINE_LIFECYCLE(farm)
 
 int cge_farm_seed(cge_farm *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_farm_seed", seeds, base_seed, true)) return st;
     DeviceGuard g(h->device);
     CGE_TRY(h, h->seed_streams(seeds, base_seed, as_stream(stream)));
     lane_launch_reset(h, h->params(), 0, 1, as_stream(stream));

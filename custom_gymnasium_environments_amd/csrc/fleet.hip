@@ -836,9 +836,8 @@ CGE_DEFINE_LIFECYCLE(fleet)
 
 int cge_fleet_seed(cge_fleet *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_fleet_seed", seeds, base_seed, true)) return st;
     DeviceGuard g(h->device);
-    if (!seeds && base_seed + (uint64_t)(h->env0 + h->n) > 0x100000000ull)
-        return h->fail(CGE_ERR_INVALID_ARG, "cge_fleet_seed: np.random.seed needs seeds < 2**32");
     CGE_TRY(h, launch_mt_seed(h->mtP, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     CGE_TRY(h, launch_mt_seed(h->mtL, MT_STRIDE, h->n, seeds, base_seed, h->env0, 1, as_stream(stream)));
     fleet::Params p = h->params();

@@ -1070,6 +1070,7 @@ CGE_DEFINE_LIFECYCLE(hospital)
 
 int cge_hospital_seed(cge_hospital *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_hospital_seed", seeds, base_seed, false)) return st;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     hipLaunchKernelGGL(hosp::reset_kernel, dim3(h->blocks()), dim3(hosp::BLOCK), 0, as_stream(stream), h->params(), 1);

@@ -905,6 +905,7 @@ CGE_DEFINE_LIFECYCLE(manufacturing)
 
 int cge_manufacturing_seed(cge_manufacturing *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_manufacturing_seed", seeds, base_seed, false)) return st;
     DeviceGuard g(h->device);
     mfg::Params p = h->params();
     p.seeds = seeds; p.base_seed = base_seed;

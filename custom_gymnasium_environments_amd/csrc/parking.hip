@@ -456,6 +456,7 @@ struct cge_parking : HandleBase {
         return p;
     }
     // what lane_seed / lane_reset (cge_lane.hpp) ask of a handle
+    static constexpr const char *abi = "cge_parking";
     static constexpr int block = parking::BLOCK, seed_kind = 0;
     auto reset_kernel() const { return parking::reset_kernel; }
     static int check(const cge_parking_config &c) {

@@ -1206,6 +1206,7 @@ CGE_DEFINE_LIFECYCLE(snake)
 
 int cge_snake_seed(cge_snake *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_snake_seed", seeds, base_seed, false)) return st;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     h->ops.rewind(h->state, h->n, as_stream(stream));   // stream cursors back to word 0

@@ -1036,6 +1036,7 @@ CGE_DEFINE_LIFECYCLE(traffic)
 
 int cge_traffic_seed(cge_traffic *h, const uint64_t *seeds, uint64_t base_seed, void *stream) {
     if (!h) return CGE_ERR_INVALID_ARG;
+    if (int st = seed_base_check(h, "cge_traffic_seed", seeds, base_seed, false)) return st;
     DeviceGuard g(h->device);
     CGE_TRY(h, launch_mt_seed(h->mt, MT_STRIDE, h->n, seeds, base_seed, h->env0, 0, as_stream(stream)));
     hipLaunchKernelGGL(traffic::rewind_kernel, dim3(grid256(h->n)), dim3(256), 0, as_stream(stream), h->state, h->n, h->recw);

@@ -62,6 +62,7 @@ class AgriculturalFarmVectorEnv(DeviceVectorEnv):
     canonical get_state / set_state records (`snapshot()` / `restore()` checkpoint the whole batch)."""
 
     _abi = "cge_farm"
+    _seed_bits = 32   # np.random.seed(s_i)
     INFO_FIELDS = INFO_FIELDS
     _invalid_action_text = "Invalid action in {n} env-step(s): must be an integer 0-44"
     metadata = {"render_modes": []}

@@ -17,6 +17,7 @@ class FleetVectorEnv(DeviceVectorEnv):
     NumPy-legacy and CPython streams with s + env_index0 + i (:187-189).  Bit-exact with the reference."""
 
     _abi = "cge_fleet"
+    _seed_bits = 32   # np.random.seed(s_i)
     _action_shape = (3,)
     INFO_FIELDS = INFO_FIELDS
     _flags = BOTH

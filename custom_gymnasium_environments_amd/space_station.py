@@ -58,6 +58,7 @@ class SpaceStationVectorEnv(DeviceVectorEnv):
     records (`snapshot()` / `restore()` checkpoint the whole batch)."""
 
     _abi = "cge_space_station"
+    _seed_bits = 32   # np.random.seed(s_i)
     INFO_FIELDS = INFO_FIELDS
     _flags = TERMINATED_AT_LIMIT
     _invalid_action_text = "Invalid action in {n} env-step(s): must be an integer 0-39"

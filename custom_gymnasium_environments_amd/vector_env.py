@@ -45,6 +45,41 @@ def _batch(space, n):
     return {k: batch_space(v, n) for k, v in space.items()} if isinstance(space, dict) else batch_space(space, n)
 
 
+def checked_seed(seed, num_envs, env_index0, bits):
+    """What reset(seed=...) hands to the C ABI: a Python int (the base: env i gets seed + env_index0 + i) or a uint64 array of
+    `num_envs` per-env seeds.  `bits` is the width of the type's generator seed: 32 where a NumPy legacy stream is seeded
+    (np.random.seed raises "Seed must be between 0 and 2**32 - 1" above it), 64 elsewhere (CPython's random.seed and NumPy's
+    SeedSequence take a third 32-bit limb from 2**64 on, which the kernels do not implement).  Every env's seed must lie in
+    [0, 2**bits - 1]: ValueError otherwise, for a base through its LAST env, with the reference's words for 32 bits.  A sequence
+    must hold integers: an array of float or bool dtype, or a list holding a float or a bool, is a TypeError, never a cast."""
+    limit = (1 << bits) - 1
+    text = f"Seed must be between 0 and 2**{bits} - 1"
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, (bool, np.bool_)):
+        seed = int(seed)
+        last = seed + int(env_index0) + int(num_envs) - 1
+        if seed < 0 or last > limit:
+            raise ValueError(f"{text}: seed {seed} gives env {int(num_envs) - 1} of this batch (env_index0 {int(env_index0)}) the seed {last}")
+        return seed
+    if isinstance(seed, torch.Tensor):
+        seed = seed.cpu().numpy()
+    if isinstance(seed, np.ndarray) and seed.dtype != object:
+        if seed.dtype.kind not in "iu":
+            raise TypeError(f"seed sequence must hold integers, not {seed.dtype}")
+        arr = seed
+    else:
+        arr = np.empty(len(seed), dtype=object)
+        for i, s in enumerate(seed):
+            if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)):
+                raise TypeError(f"seed sequence must hold integers, not {type(s).__name__} (item {i})")
+            arr[i] = int(s)
+    if arr.shape != (int(num_envs),):
+        raise ValueError(f"seed sequence must hold {int(num_envs)} ints, got shape {arr.shape}")
+    lo, hi = int(arr.min()), int(arr.max())
+    if lo < 0 or hi > limit:
+        raise ValueError(f"{text}: the seed sequence holds {lo if lo < 0 else hi}")
+    return np.ascontiguousarray(arr.astype(np.uint64))
+
+
 TERMINATED, TRUNCATED, BOTH, TERMINATED_AT_LIMIT = "terminated", "truncated", "both", "terminated_at_limit"
 
 
@@ -59,6 +94,7 @@ class DeviceVectorEnv(VectorEnvBase):
     with `terminated`, so done = terminated and a rollout's per-step flags are the bool `terminated`)."""
 
     _abi = None  # e.g. "cge_snake"
+    _seed_bits = 64   # the width of a per-env seed (checked_seed): 32 for the types that seed a NumPy legacy stream
     INFO_FIELDS = {}
     INFO64_FIELDS = {}
     _obs_dtype = torch.float32
@@ -164,18 +200,15 @@ class DeviceVectorEnv(VectorEnvBase):
         return t.contiguous()
 
     def _seed_native(self, seed):
-        """seed: None (streams continue), int (env i gets seed + env_index0 + i) or a per-env sequence."""
+        """seed: None (streams continue), int (env i gets seed + env_index0 + i) or a per-env sequence.  `checked_seed` refuses
+        what the reference's generator refuses before anything native is called: a refused seed changes nothing."""
         if seed is None:
             return
-        if isinstance(seed, (int, np.integer)):
-            if seed < 0:
-                raise ValueError("seed must be non-negative")
-            self._check(self._c_seed(self._h, None, int(seed), self._stream()), "seed")
+        seed = checked_seed(seed, self.num_envs, self.env_index0, self._seed_bits)
+        if isinstance(seed, int):
+            self._check(self._c_seed(self._h, None, seed, self._stream()), "seed")
             return
-        arr = np.asarray(seed)
-        if arr.shape != (self.num_envs,) or np.any(arr < 0):
-            raise ValueError(f"seed sequence must hold {self.num_envs} non-negative ints")
-        t = torch.from_numpy(arr.astype(np.uint64).view(np.int64)).to(self.device)
+        t = torch.from_numpy(seed.view(np.int64)).to(self.device)
         self._check(self._c_seed(self._h, t.data_ptr(), 0, self._stream()), "seed")
         self._keepalive = t
 

@@ -74,6 +74,7 @@ class WorldBuilderVectorEnv(SlabVectorEnv):
     (include/cge_amd.h)."""
 
     _abi = "cge_world_builder"
+    _seed_bits = 32   # np.random.seed(s_i)
     INFO_FIELDS = INFO_FIELDS
     _action_shape = ()
     _flags = TERMINATED

@@ -63,6 +63,13 @@
  *   - `env_index0` is the global index of the handle's first env: per-env seeds and the synthetic
  *     action hash are functions of the GLOBAL index so results do not depend on how a batch is
  *     sharded over GPUs.
+ *   - <env>_seed with seeds == NULL refuses, before it launches anything, a base_seed whose LAST env
+ *     (base_seed + env_index0 + n_envs - 1) passes the limit of the type's generator: 2**32 - 1 where
+ *     np.random.seed is among the calls it stands for (crypto, fleet, world builder, space station,
+ *     farm), 2**64 - 1 elsewhere (the sum must not wrap uint64_t; seeds of three 32-bit limbs are not
+ *     implemented).  It returns CGE_ERR_INVALID_ARG, last_error names the limit, and the streams
+ *     are as they were.  A `seeds` array is device memory and is not read back: its values are the
+ *     caller's duty.
  */
 #ifndef CGE_AMD_H
 #define CGE_AMD_H
@@ -788,7 +795,7 @@ enum { /* cge_airline_info float64 fields: the reference's five info values (:43
 /* AirlineOperationsEnv.__init__ :132-190 on the stream random.seed(env_index0 + i) */
 int cge_airline_create(const cge_airline_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_airline **out);
 int cge_airline_destroy(cge_airline *h);
-/* random.seed(s_i); AirlineOperationsEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+/* random.seed(s_i); AirlineOperationsEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Call reset next. */
 int cge_airline_seed(cge_airline *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
 /* reset :274-336 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
 int cge_airline_reset(cge_airline *h, const uint8_t *mask, float *obs_out, void *stream);
@@ -862,7 +869,7 @@ enum { /* cge_emergency_info float64 fields: the reference's six info values (:9
 /* EmergencyResponseEnv.__init__ :116-157 on the stream random.seed(env_index0 + i) */
 int cge_emergency_create(const cge_emergency_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_emergency **out);
 int cge_emergency_destroy(cge_emergency *h);
-/* random.seed(s_i); EmergencyResponseEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+/* random.seed(s_i); EmergencyResponseEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Call reset next. */
 int cge_emergency_seed(cge_emergency *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
 /* reset :829-881 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
 int cge_emergency_reset(cge_emergency *h, const uint8_t *mask, float *obs_out, void *stream);
@@ -945,7 +952,8 @@ enum { /* cge_space_station_info float64 fields: the reference's nine info value
 /* SpaceStationEnv.__init__ :56-135 on the stream np.random.seed(env_index0 + i) */
 int cge_space_station_create(const cge_space_station_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_space_station **out);
 int cge_space_station_destroy(cge_space_station *h);
-/* np.random.seed(s_i); SpaceStationEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).  Call reset next. */
+/* np.random.seed(s_i); SpaceStationEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i; s_i must be < 2**32
+ * (np.random.seed raises otherwise).  Call reset next. */
 int cge_space_station_seed(cge_space_station *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
 /* reset :247-308 for envs with mask[i] != 0 (all if NULL), continuing each env's stream; writes every row if obs_out != NULL */
 int cge_space_station_reset(cge_space_station *h, const uint8_t *mask, float *obs_out, void *stream);
@@ -1038,8 +1046,8 @@ enum { /* cge_farm_info float64 fields: the reference's eleven scalar info value
 /* AgriculturalFarmEnv.__init__ :127-192 on the streams random.seed / np.random.seed(env_index0 + i) */
 int cge_farm_create(const cge_farm_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_farm **out);
 int cge_farm_destroy(cge_farm *h);
-/* random.seed(s_i); np.random.seed(s_i); AgriculturalFarmEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i (below 2^32).
- * Call reset next. */
+/* random.seed(s_i); np.random.seed(s_i); AgriculturalFarmEnv() for env i; s_i = seeds[i] or base_seed + env_index0 + i; s_i must
+ * be < 2**32 (np.random.seed raises otherwise).  Call reset next. */
 int cge_farm_seed(cge_farm *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
 /* reset :520-566 for envs with mask[i] != 0 (all if NULL), continuing each env's streams; writes every row if obs_out != NULL */
 int cge_farm_reset(cge_farm *h, const uint8_t *mask, float *obs_out, void *stream);
@@ -1130,7 +1138,8 @@ enum { /* cge_world_builder_info int32 fields — the values behind _get_info (:
 /* WorldBuilderEnv.__init__ :39-97; a grid_size outside 2..10 is CGE_ERR_INVALID_ARG */
 int cge_world_builder_create(const cge_world_builder_config *cfg, int64_t n_envs, int device, int64_t env_index0, cge_world_builder **out);
 int cge_world_builder_destroy(cge_world_builder *h);
-/* np.random.seed(s_i) for env i; s_i = seeds[i] or base_seed + env_index0 + i.  Does not reset the envs. */
+/* np.random.seed(s_i) for env i; s_i = seeds[i] or base_seed + env_index0 + i; s_i must be < 2**32 (np.random.seed raises
+ * otherwise).  Does not reset the envs. */
 int cge_world_builder_seed(cge_world_builder *h, const uint64_t *seeds, uint64_t base_seed, void *stream);
 /* reset :99-121 (game_logic.py:31-54) for envs with mask[i] != 0 (all if NULL); writes the whole observation if obs_out != NULL */
 int cge_world_builder_reset(cge_world_builder *h, const uint8_t *mask, void *obs_out, void *stream);

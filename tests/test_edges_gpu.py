@@ -224,7 +224,7 @@ def test_partial_reset_mask_matches_oracle(oracle, name, kw, oname, oargs):
 
 @pytest.mark.parametrize("name,kw,oname,oargs,big", [
     ("Snake", dict(grid_size=10), "SnakeOracle", (10,), True), ("Traffic", {}, "TrafficOracle", (), True),
-    ("Crypto", dict(action_type="discrete"), "CryptoOracle", ("discrete",), False),      # np.random.seed takes 32 bits
+    ("Crypto", dict(action_type="discrete"), "CryptoOracle", ("discrete",), False),      # np.random.seed takes 32 bits: test_seed_edges_gpu.py::test_refused_seeds_leave_the_handle_as_it_was
     ("Parking", {}, "ParkingOracle", (), True), ("Hospital", {}, "HospitalOracle", (), True),
     ("Climate", {}, "ClimateOracle", (), True), ("Manufacturing", {}, "ManufacturingOracle", (), True),
     ("Fleet", {}, "FleetOracle", (), False)])
