@@ -19,6 +19,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import custom_gymnasium_environments_amd as cge  # noqa: E402
+from lane_timing import copy_bandwidth, timed  # noqa: E402
 
 LIMIT, K = 500, 125
 # obliged bytes per env-step: what the call must read and write at least once
@@ -26,32 +27,6 @@ STATE = 3 * 16                                   # the record: three uint4 colum
 OBS = 56 * 4                                     # one slab piece
 STEP_BYTES = STATE + 16 + STATE + OBS + 4 + 1 + 1              # record in, actions in, record out, obs, reward, terminated, truncated
 ROLL_BYTES = OBS + 4 + 1 + (2 * STATE + 8 + 4) / K            # obs + reward + truncated per step; record, reward_sum, done_count per launch
-
-
-def copy_bandwidth(dev):
-    x = torch.empty(1 << 29, dtype=torch.float32, device=dev)
-    y = torch.empty_like(x)
-    y.copy_(x)
-    torch.cuda.synchronize(dev)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(8):
-        y.copy_(x)
-    b.record()
-    torch.cuda.synchronize(dev)
-    gbs = 2 * x.numel() * 4 / 1e9 / (a.elapsed_time(b) / 8 * 1e-3)
-    del x, y
-    torch.cuda.empty_cache()
-    return gbs
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3            # us
 
 
 def run(n, episodes, copy_gbs):

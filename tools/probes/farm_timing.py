@@ -1,4 +1,4 @@
-"""AgriculturalFarmVectorEnv timing from a reset, at 131,072 and 1,048,576 envs, SAME_STEP, modelled on space_station_timing.py:
+"""AgriculturalFarmVectorEnv timing from a reset, at 131,072 and 1,048,576 envs, SAME_STEP (loop, header and options: lane_timing.py):
 
   reset()      on its own (54 uniforms and 16 bounded integers, about 125 generator words per env)
   step()       k calls with device-resident actions (uniform over 0..44), device events around them -> us per step
@@ -15,7 +15,6 @@ reset(seed) and 64 hashed steps (a_seed 1) for seeds 0..N-1, N from --log-caveat
 from snapshot() bytes: the size of the `log` caveat.
 
   python tools/probes/farm_timing.py [--runs 5] [--sizes ...] [--k 32] [--log-caveat N (--host-record F | --host-file F)]"""
-import argparse
 import os
 import subprocess
 import sys
@@ -26,6 +25,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden", "gen"))
 import numpy as np  # noqa: E402
 
 import common  # noqa: E402  (the counter hash of the synthetic actions)
+import lane_timing  # noqa: E402
+from lane_timing import rng  # noqa: E402
 
 OBS, COMPACT = 620 * 4, 134 * 4
 RECORD = 832                                     # loaded by every launch and stored by it: the whole record
@@ -44,31 +45,13 @@ def roll_bytes(k, obs):
     return obs + 4 + 1 + 4 + DRAWN + TWIST + (2 * RECORD + 12) / k
 
 
-def rng(v):
-    return f"{min(v):9.2f} - {max(v):9.2f}"
-
-
 def run(n, runs, copy_gbs, k, compact):
-    import torch
     import custom_gymnasium_environments_amd as cge
-    from bus_timing import timed
     obs = COMPACT if compact else OBS
-    env = cge.AgriculturalFarmVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True, compact_obs=compact)
-    g = torch.Generator(device="cuda").manual_seed(0)
-    acts = (torch.rand((k, n), generator=g, device="cuda") * 45).to(torch.int32)
-    rows = {"reset": [], "step": [], "roll": []}
-    for ep in range(runs + 1):                                   # the first run warms up (buffers, code objects)
-        env.reset(seed=ep)
-        r = timed(lambda: env.reset())
-        steps = timed(lambda: [env.step(acts[t]) for t in range(k)])
-        step_kernel = env.last_kernel()
-        env.reset()
-        roll = timed(lambda: env.rollout(k, actions=acts, trajectory=True, per_step=True))
-        if ep:
-            rows["reset"].append(r); rows["step"].append(steps / k); rows["roll"].append(roll / k)
+    make = lambda: cge.AgriculturalFarmVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True, compact_obs=compact)   # noqa: E731
+    rows = lane_timing.measure(make, n, k, 45, runs, label=f"  compact_obs {compact}")
     copy_us = lambda b: b * n / (copy_gbs * 1e9) * 1e6           # noqa: E731
     sb, rb = step_bytes(obs), roll_bytes(k, obs)
-    print(f"n_envs {n}  compact_obs {compact}  (kernels: {step_kernel}, {env.last_kernel()}; device bytes {env.device_bytes() / 2**20:.0f} MiB; ranges over {runs} runs)")
     print(f"  reset()                {rng(rows['reset'])} us   writes {obs + RECORD} B/env; as a copy: {copy_us(obs + RECORD):.1f} us")
     print(f"  step()   {k} calls      {rng(rows['step'])} us/step   moves {sb} B/env-step (obs {obs} + reward 4 + flag 1 + action 4 + record in {RECORD} "
           f"+ out {RECORD} + generator words drawn {DRAWN} + twisted {TWIST}); the same bytes as a copy: {copy_us(sb):.1f} us; ratio "
@@ -76,9 +59,6 @@ def run(n, runs, copy_gbs, k, compact):
     print(f"  rollout({k}, trajectory) {rng(rows['roll'])} us/step   moves {rb:.1f} B/env-step (obs {obs} + reward 4 + flag 1 + action 4 + generator {DRAWN + TWIST} + "
           f"(record in + out + 12) / {k}); as a copy: {copy_us(rb):.1f} us; ratio {min(rows['roll']) / copy_us(rb):.2f} - {max(rows['roll']) / copy_us(rb):.2f};  "
           f"{n / min(rows['roll']) * 1e6:.3g} env-steps/s;  trajectory buffer {k * n * obs / 2**30:.1f} GiB")
-    env.close()
-    del env, acts
-    torch.cuda.empty_cache()
 
 
 def caveat_actions(n):
@@ -100,9 +80,7 @@ def log_caveat(n, host_file):
     env = cge.AgriculturalFarmVectorEnv(n, autoreset_mode="SameStep")
     env.reset(seed=0)
     env.rollout(STEPS, action_seed=A_SEED)                                   # the same hashed actions as caveat_actions()
-    snap = env.snapshot()
-    rec = snap[32:32 + RECORD * n].view(np.uint32).reshape(208, n)          # the record's columns [word][env] behind the 32-byte header
-    dev = (rec[0:178:2].astype(np.uint64) | rec[1:178:2].astype(np.uint64) << np.uint64(32)).T   # the 89 float64 of each env
+    dev = lane_timing.float64_columns(env.snapshot(), n, RECORD, 89)        # the 89 float64 of each env
     diff = dev != host
     ulp = np.abs(dev.astype(np.int64) - host.astype(np.int64))[diff]
     prices = diff[:, 65:75]
@@ -117,10 +95,7 @@ def log_caveat(n, host_file):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--sizes", type=int, nargs="+", default=[131072, 1048576])
-    ap.add_argument("--k", type=int, default=32)
+    ap = lane_timing.parser(32)
     ap.add_argument("--log-caveat", type=int, default=0)
     ap.add_argument("--host-file", default=None)
     ap.add_argument("--host-record", default=None)
@@ -128,17 +103,12 @@ if __name__ == "__main__":
     if args.host_record:
         host_record(args.log_caveat or 4096, args.host_record)
         sys.exit(0)
-    import torch
-    assert torch.cuda.is_available(), "needs an MI355X"
     if args.log_caveat:
+        import torch
+        assert torch.cuda.is_available(), "needs an MI355X"
         log_caveat(args.log_caveat, args.host_file)
         sys.exit(0)
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from bus_timing import copy_bandwidth
-    copy_gbs = copy_bandwidth(torch.device("cuda:0"))
-    print(f"box: {torch.cuda.get_device_name(0)}, torch {torch.__version__}; library {os.environ.get('CGE_AMD_LIBRARY', 'libcge_amd.so')}; "
-          f"device-to-device copy (2-GiB buffers, read + written): {copy_gbs:.0f} GB/s")
-    print("times: device events around work that ends in a synchronise; device-resident int32 actions, reuse_buffers=True, SameStep")
+    copy_gbs = lane_timing.header(library=True)
     for n in args.sizes:
         run(n, args.runs, copy_gbs, args.k, False)
     run(max(args.sizes), args.runs, copy_gbs, args.k, True)

@@ -34,7 +34,7 @@ TYPES = {   # name -> (class, number of actions, steps of a rollout)
 def child(n, runs, types):
     import torch
     import custom_gymnasium_environments_amd as cge
-    from bus_timing import timed
+    from lane_timing import timed
     assert torch.cuda.is_available(), "needs an MI355X"
     for name in types:
         cls, nact, k = TYPES[name]

@@ -1,5 +1,6 @@
 """The driver of tools/probes/<type>_host_check.py: the kernels' own dynamics code (csrc/<type>_env.hpp) compiled for the CPU with
-<type>_host_check.cpp and run over every fixture of the type, the check of the record's packing, the draw order and the step logic
+<type>_host_check.cpp (the four record-lane programs share their reader, replay loop and generator in lane_host_check.hpp, whose Sim
+description mirrors what bind() takes here) and run over every fixture of the type, the check of the record's packing, the draw order and the step logic
 that needs no GPU.  The host programs check every runtime index themselves, and `--sanitize` builds the stand-alone program with
 -fsanitize=address,undefined and runs it directly.  A type's entry point binds build(), write_fixture() and main() to its kind with
 bind(), which takes what differs between the types as data.  Not a program of its own."""
@@ -39,11 +40,14 @@ def build(kind, outdir, flags=OPT, compiler=None):
     return exe
 
 
-def write_fixture(kind, name, outdir):
-    """the fixture as the binary file that the kind's host program reads; returns its path"""
+def write_fixture(kind, name, outdir, edit=None):
+    """the fixture as the binary file that the kind's host program reads; returns its path.  edit(arrays) may change the fixture's
+    arrays first (tests/test_host_check_detects_cpu.py writes files that the program must refuse)"""
     spec = TYPES[kind]
     with np.load(os.path.join(ROOT, "tests", "golden", name + ".npz")) as z:
         z = {k: z[k] for k in z.files}
+    if edit:
+        edit(z)
     n, T = z["reward"].shape
     obs = np.ascontiguousarray(np.bitwise_xor.accumulate(z["obs_xor"], axis=2).transpose(0, 2, 1))      # uint32 [n, T, width]
     reset_at = np.full((n, T), -1, np.int32)

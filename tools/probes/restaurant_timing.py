@@ -21,7 +21,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import custom_gymnasium_environments_amd as cge  # noqa: E402
-from bus_timing import copy_bandwidth, timed  # noqa: E402
+from lane_timing import copy_bandwidth, timed  # noqa: E402
 
 LIMIT = 500
 RECORD = 11 * 16                                 # the record: eleven uint4 columns

@@ -43,7 +43,7 @@ NOTES = {"bus": ("3cge3bus", ""), "restaurant": ("3cge10restaurant", ""), "wb_di
 def child(sizes, runs, types):
     import torch
     import custom_gymnasium_environments_amd as cge
-    from bus_timing import timed
+    from lane_timing import timed
     assert torch.cuda.is_available(), "needs an MI355X"
     for name in types:
         cls, kw, limit, per_env = TYPES[name]

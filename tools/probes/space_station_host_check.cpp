@@ -13,134 +13,66 @@
 // autoreset in the same step, and writes the 89 float64 slots of each record below W_SCAL in column order (the six slots of the
 // last_maintenance integers as zeros).
 // `--layout`: prints `name word-offset f64|u32` for every field a poke can name, the offsets found through the record's own packer.
-// The generator is MT19937 seeded as NumPy's legacy np.random.seed(int) does (init_genrand).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+// The generator is MT19937 seeded as NumPy's legacy np.random.seed(int) does.  The reader, the replay loop, the poke table, --layout,
+// --record and the generator are those of lane_host_check.hpp.
+#include "lane_host_check.hpp"
 
 #include "../../custom_gymnasium_environments_amd/csrc/space_station_env.hpp"
 
 using namespace cge::station;
+using lane_check::Mt;
 
-struct Mt {
-    uint32_t mt[624];
-    int idx = 624;
-    void seed(uint32_t s) {                                          // init_genrand
-        mt[0] = s;
-        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-        idx = 624;
-    }
-    uint32_t next() {
-        if (idx >= 624) {
-            for (int k = 0; k < 624; ++k) {
-                const uint32_t y = (mt[k] & 0x80000000u) | (mt[(k + 1) % 624] & 0x7fffffffu);
-                mt[k] = mt[(k + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-            }
-            idx = 0;
-        }
-        uint32_t y = mt[idx++];
-        y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
-        return y;
-    }
-    template <int W>
-    void run(uint32_t (&w)[W]) { for (int k = 0; k < W; ++k) w[k] = next(); }
-};
-
-static void observe(const Env &e, float *o) {
-    auto out = [&](int k, float v) { if (k < 0 || k >= OBS) { printf("element %d\n", k); exit(3); } o[k] = v; };
-    observe_crew(e, out);
-    observe_systems(e, out);
-    observe_modules(e, out);
-    observe_rest(e, out);
-}
-
-// through the packed record, as every launch does
-static void repack(Env &e) {
-    uint32_t w[REC_WORDS] = {};
-    Env::each_double(e, [&](int k, const double &v) { memcpy(&w[k], &v, 8); });
-    for (int s = 0; s < NS; ++s) w[W_LM + s] = e.last_maint[s];
-    e.pack_scalars([&](int k, uint32_t v) { w[W_SCAL + k] = v; });
-    Env f{};
-    Env::each_double(f, [&](int k, double &v) { memcpy(&v, &w[k], 8); });
-    for (int s = 0; s < NS; ++s) f.last_maint[s] = w[W_LM + s];
-    f.unpack_scalars([&](int k) { return w[W_SCAL + k]; });
-    e = f;
-}
-
-// every field a poke can name, as the header names it: f(name, the double)
-template <class F>
-static void each_named(Env &e, F f) {
-    char name[24];
-    for (int m = 0; m < NM; ++m) {
-        snprintf(name, sizeof name, "o2%d", m); f(name, &e.o2[m]);
-        snprintf(name, sizeof name, "co2%d", m); f(name, &e.co2[m]);
-        snprintf(name, sizeof name, "pres%d", m); f(name, &e.pres[m]);
-        snprintf(name, sizeof name, "temp%d", m); f(name, &e.temp[m]);
-    }
-    for (int c = 0; c < NC; ++c) {
-        snprintf(name, sizeof name, "health%d", c); f(name, &e.health[c]);
-        snprintf(name, sizeof name, "oxy%d", c); f(name, &e.oxy[c]);
-        snprintf(name, sizeof name, "fatigue%d", c); f(name, &e.fatigue[c]);
-    }
-    for (int s = 0; s < NS; ++s) {
-        snprintf(name, sizeof name, "eff%d", s); f(name, &e.eff[s]);
-        snprintf(name, sizeof name, "maint%d", s); f(name, &e.maint[s]);
-    }
-    f("water", &e.water); f("food", &e.food); f("tanks", &e.tanks); f("spare", &e.spare); f("waste", &e.waste); f("battery", &e.battery);
-}
-
-static bool poke(Env &e, const char *name, double value) {
-    bool found = false;
-    each_named(e, [&](const char *nm, double *d) { if (!strcmp(nm, name)) { found = true; *d = value; } });
-    return found;
-}
-
-// the word of the record that holds each named field: by its address in each_double()
-static int layout() {
+struct Sim {
+    static constexpr int WIDTH = OBS, NINFO = 10, EXTRA = 1;          // extra: max_steps
+    static constexpr bool INFO0 = true, TRUNCATED = true, POKES = true;
+    static constexpr int REC_WORDS = cge::station::REC_WORDS, REC_DOUBLES = W_SCAL / 2;
+    static constexpr int32_t RECORD_EXTRA[EXTRA] = {8640};
     Env e{};
-    int bad = 0;
-    each_named(e, [&](const char *nm, double *d) {
-        int at = -1;
-        Env::each_double(e, [&](int w, double &v) { if (&v == d) at = w; });
-        if (at < 0 || at + 1 >= REC_WORDS) { ++bad; return; }
-        printf("%s %d f64\n", nm, at);
-    });
-    return bad ? 1 : 0;
-}
-
-struct Poke { int32_t env, step; char name[24]; double value; };
-static_assert(sizeof(Poke) == 40, "as space_station_host_check.py writes it");
-
-static void info10(const Env &e, double *gi) {
-    for (int k = 0; k < 10; ++k) gi[k] = info_value(e, k);
-}
+    Mt rng;
+    uint32_t max_t;
+    Sim(uint64_t seed, const int32_t *extra) : max_t((uint32_t)extra[0]) {
+        rng.seed_numpy((uint32_t)seed);
+        construct(e);
+        reset_episode(e, rng);
+    }
+    double step(int32_t a, bool &term, bool &trunc) { return env_step(e, rng, a, a >= 0 && a < ACTIONS, max_t, term, trunc); }
+    void reset() { reset_episode(e, rng); }
+    void observe(float *o) const {
+        auto out = [&](int k, float v) { o[lane_check::element(k, OBS)] = v; };
+        observe_crew(e, out);
+        observe_systems(e, out);
+        observe_modules(e, out);
+        observe_rest(e, out);
+    }
+    void info(double *gi) const {
+        for (int k = 0; k < NINFO; ++k) gi[k] = info_value(e, k);
+    }
+    void repack() {                                                  // through the packed record, as every launch does
+        uint32_t w[REC_WORDS] = {};
+        Env::each_double(e, [&](int k, const double &v) { memcpy(&w[k], &v, 8); });
+        for (int s = 0; s < NS; ++s) w[W_LM + s] = e.last_maint[s];
+        e.pack_scalars([&](int k, uint32_t v) { w[W_SCAL + k] = v; });
+        Env f{};
+        Env::each_double(f, [&](int k, double &v) { memcpy(&v, &w[k], 8); });
+        for (int s = 0; s < NS; ++s) f.last_maint[s] = w[W_LM + s];
+        f.unpack_scalars([&](int k) { return w[W_SCAL + k]; });
+        e = f;
+    }
+    // every field a poke can name, as the header names it: f(name, the double, no integer)
+    template <class F>
+    static void each_named(Env &e, F f) {
+        char name[24];
+        auto d = [&](const char *fmt, int k, double *v) { snprintf(name, sizeof name, fmt, k); f(name, v, (uint32_t *)nullptr); };
+        for (int m = 0; m < NM; ++m) { d("o2%d", m, &e.o2[m]); d("co2%d", m, &e.co2[m]); d("pres%d", m, &e.pres[m]); d("temp%d", m, &e.temp[m]); }
+        for (int c = 0; c < NC; ++c) { d("health%d", c, &e.health[c]); d("oxy%d", c, &e.oxy[c]); d("fatigue%d", c, &e.fatigue[c]); }
+        for (int s = 0; s < NS; ++s) { d("eff%d", s, &e.eff[s]); d("maint%d", s, &e.maint[s]); }
+        d("water", 0, &e.water); d("food", 0, &e.food); d("tanks", 0, &e.tanks); d("spare", 0, &e.spare); d("waste", 0, &e.waste); d("battery", 0, &e.battery);
+    }
+    static int int_word(Env &, uint32_t *) { return -1; }             // no integer has a name
+};
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
-    if (!strcmp(argv[1], "--layout")) return layout();
-    if (!strcmp(argv[1], "--record") && argc > 4) {
-        const long s0 = atol(argv[2]), n = atol(argv[3]), K = atol(argv[4]);
-        std::vector<int32_t> a((size_t)n * K);
-        if (fread(a.data(), 4, a.size(), stdin) != a.size()) return 2;
-        for (long i = 0; i < n; ++i) {
-            Mt rng;
-            rng.seed((uint32_t)(s0 + i));
-            Env e{};
-            construct(e);
-            reset_episode(e, rng);
-            for (long t = 0; t < K; ++t) {
-                bool term, trunc;
-                const int32_t act = a[(size_t)t * n + i];
-                env_step(e, rng, act, act >= 0 && act < ACTIONS, 8640u, term, trunc);
-                if (term) reset_episode(e, rng);
-            }
-            double rec[W_SCAL / 2] = {};
-            Env::each_double(e, [&](int w, const double &v) { rec[w / 2] = v; });
-            fwrite(rec, 8, W_SCAL / 2, stdout);
-        }
-        return 0;
-    }
     if (!strcmp(argv[1], "--mean") && argc > 2) {
         const int n = atoi(argv[2]);
         double v[NS];
@@ -165,71 +97,11 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "--reset") && argc > 3) {
         const long s0 = atol(argv[2]), n = atol(argv[3]);
         for (long s = s0; s < s0 + n; ++s) {
-            Mt rng;
-            rng.seed((uint32_t)s);
-            Env e{};
-            construct(e);
-            reset_episode(e, rng);
+            const Sim sim((uint64_t)s, Sim::RECORD_EXTRA);
+            const Env &e = sim.e;
             fwrite(e.o2, 8, NM, stdout); fwrite(e.co2, 8, NM, stdout); fwrite(e.pres, 8, NM, stdout); fwrite(e.temp, 8, NM, stdout);
         }
         return 0;
     }
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return 2;
-    int32_t hd[6];
-    if (fread(hd, 4, 6, f) != 6) return 2;
-    const int n = hd[0], T = hd[1], autoreset = hd[2], nres = hd[3];
-    const uint32_t max_t = (uint32_t)hd[4];
-    std::vector<float> robs((size_t)nres * OBS);
-    if (fread(robs.data(), 4, robs.size(), f) != robs.size()) return 2;
-    std::vector<Poke> pokes((size_t)hd[5]);
-    if (fread(pokes.data(), sizeof(Poke), pokes.size(), f) != pokes.size()) return 2;
-    long bad = 0;
-    for (int i = 0; i < n; ++i) {
-        int32_t seed;
-        std::vector<int32_t> a(T), at(T);
-        std::vector<float> obs0(OBS), obs((size_t)T * OBS);
-        std::vector<double> r(T), info((size_t)T * 10), info0(10);
-        std::vector<uint8_t> tm(T), tr(T);
-        if (fread(&seed, 4, 1, f) != 1 || fread(a.data(), 4, T, f) != (size_t)T || fread(at.data(), 4, T, f) != (size_t)T ||
-            fread(obs0.data(), 4, OBS, f) != OBS || fread(info0.data(), 8, 10, f) != 10 || fread(obs.data(), 4, obs.size(), f) != obs.size() ||
-            fread(r.data(), 8, T, f) != (size_t)T || fread(tm.data(), 1, T, f) != (size_t)T || fread(tr.data(), 1, T, f) != (size_t)T ||
-            fread(info.data(), 8, info.size(), f) != info.size()) return 2;
-        Mt rng;
-        rng.seed((uint32_t)seed);
-        Env e{};
-        construct(e);
-        reset_episode(e, rng);
-        float got[OBS];
-        double gi[10];
-        observe(e, got);
-        info10(e, gi);
-        if ((memcmp(got, obs0.data(), sizeof got) || memcmp(gi, info0.data(), sizeof gi)) && bad++ < 5) printf("env %d: reset observation or info differs\n", i);
-        for (int t = 0; t < T; ++t) {
-            for (Poke &p : pokes) {
-                p.name[sizeof p.name - 1] = 0;
-                if (p.env == i && p.step == t && !poke(e, p.name, p.value)) { printf("no field %s\n", p.name); return 2; }
-            }
-            repack(e);
-            bool term, trunc;
-            const double rew = env_step(e, rng, a[t], a[t] >= 0 && a[t] < ACTIONS, max_t, term, trunc);
-            observe(e, got);
-            info10(e, gi);
-            bool ok = !memcmp(&rew, &r[t], 8) && term == (tm[t] != 0) && trunc == (tr[t] != 0) && !memcmp(gi, &info[10 * (size_t)t], sizeof gi) &&
-                      !memcmp(got, &obs[(size_t)OBS * t], sizeof got);
-            if (!ok && bad++ < 5) {
-                printf("env %d step %d action %d: reward %.17g / %.17g terminated %d / %d truncated %d / %d\n", i, t, a[t], rew, r[t], (int)term, (int)tm[t], (int)trunc, (int)tr[t]);
-                for (int k = 0; k < 10; ++k) if (memcmp(&gi[k], &info[10 * (size_t)t + k], 8)) printf("  info %d: %.17g / %.17g\n", k, gi[k], info[10 * (size_t)t + k]);
-                for (int k = 0; k < OBS; ++k) if (memcmp(&got[k], &obs[(size_t)OBS * t + k], 4)) printf("  obs %d: %.9g / %.9g\n", k, got[k], obs[(size_t)OBS * t + k]);
-            }
-            if (term && autoreset) {
-                reset_episode(e, rng);
-                observe(e, got);
-                if (!(at[t] >= 0 && !memcmp(got, &robs[(size_t)OBS * at[t]], sizeof got)) && bad++ < 5) printf("env %d step %d: reset observation differs\n", i, t);
-            }
-        }
-    }
-    fclose(f);
-    printf("%s: %d envs x %d steps, %ld mismatching steps\n", argv[1], n, T, bad);
-    return bad ? 1 : 0;
+    return lane_check::run<Sim>(argc, argv);
 }

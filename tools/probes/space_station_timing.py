@@ -1,4 +1,4 @@
-"""SpaceStationVectorEnv timing from a reset, at 131,072 and 1,048,576 envs, SAME_STEP, modelled on emergency_timing.py:
+"""SpaceStationVectorEnv timing from a reset, at 131,072 and 1,048,576 envs, SAME_STEP (loop, header and options: lane_timing.py):
 
   reset()      on its own (32 Gaussians and 24 uniforms, about 130 generator words per env)
   step()       k calls with device-resident actions (uniform over 0..39), device events around them -> us per step
@@ -14,7 +14,6 @@ through log) differs anywhere from `--host-file`, the same values from the host 
 (tools/probes/space_station_host_check.py --reset 0 N > file), read from snapshot() bytes.
 
   python tools/probes/space_station_timing.py [--runs 5] [--sizes ...] [--k 32] [--log-caveat N --host-file F]"""
-import argparse
 import os
 import sys
 
@@ -23,7 +22,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import custom_gymnasium_environments_amd as cge  # noqa: E402
-from bus_timing import copy_bandwidth, timed  # noqa: E402
+import lane_timing  # noqa: E402
+from lane_timing import rng  # noqa: E402
 
 OBS = 120 * 4
 RECORD = 752                                     # loaded by every launch and stored by it: the whole record
@@ -38,27 +38,11 @@ def roll_bytes(k):
     return OBS + 4 + 1 + 4 + DRAWN + TWIST + (2 * RECORD + 12) / k
 
 
-def rng(v):
-    return f"{min(v):9.2f} - {max(v):9.2f}"
-
-
 def run(n, runs, copy_gbs, k):
-    env = cge.SpaceStationVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
-    g = torch.Generator(device="cuda").manual_seed(0)
-    acts = (torch.rand((k, n), generator=g, device="cuda") * 40).to(torch.int32)
-    rows = {"reset": [], "step": [], "roll": []}
-    for ep in range(runs + 1):                                   # the first run warms up (buffers, code objects)
-        env.reset(seed=ep)
-        r = timed(lambda: env.reset())
-        steps = timed(lambda: [env.step(acts[t]) for t in range(k)])
-        step_kernel = env.last_kernel()
-        env.reset()
-        roll = timed(lambda: env.rollout(k, actions=acts, trajectory=True, per_step=True))
-        if ep:
-            rows["reset"].append(r); rows["step"].append(steps / k); rows["roll"].append(roll / k)
+    make = lambda: cge.SpaceStationVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)   # noqa: E731
+    rows = lane_timing.measure(make, n, k, 40, runs)
     copy_us = lambda b: b * n / (copy_gbs * 1e9) * 1e6           # noqa: E731
     rb = roll_bytes(k)
-    print(f"n_envs {n}  (kernels: {step_kernel}, {env.last_kernel()}; device bytes {env.device_bytes() / 2**20:.0f} MiB; ranges over {runs} runs)")
     print(f"  reset()                {rng(rows['reset'])} us")
     print(f"  step()   {k} calls      {rng(rows['step'])} us/step   moves {STEP_BYTES} B/env-step (obs {OBS} + reward 4 + flags 2 + action 4 + record in {RECORD} "
           f"+ out {RECORD} + generator words drawn {DRAWN} + twisted {TWIST}); the same bytes as a copy: {copy_us(STEP_BYTES):.1f} us; ratio "
@@ -66,18 +50,13 @@ def run(n, runs, copy_gbs, k):
     print(f"  rollout({k}, trajectory) {rng(rows['roll'])} us/step   moves {rb:.1f} B/env-step (obs {OBS} + reward 4 + flag 1 + action 4 + generator {DRAWN + TWIST} + "
           f"(record in + out + 12) / {k}); as a copy: {copy_us(rb):.1f} us; ratio {min(rows['roll']) / copy_us(rb):.2f} - {max(rows['roll']) / copy_us(rb):.2f};  "
           f"{n / min(rows['roll']) * 1e6:.3g} env-steps/s;  trajectory buffer {k * n * OBS / 2**30:.1f} GiB")
-    env.close()
-    del env, acts
-    torch.cuda.empty_cache()
 
 
 def log_caveat(n, host_file):
     host = np.fromfile(host_file, np.uint64).reshape(n, 32)
     env = cge.SpaceStationVectorEnv(n, autoreset_mode="SameStep")
     env.reset(seed=0)
-    snap = env.snapshot()
-    rec = snap[32:32 + 752 * n].view(np.uint32).reshape(188, n)             # the record's columns [word][env] behind the 32-byte header
-    dev = (rec[0:64:2].astype(np.uint64) | rec[1:64:2].astype(np.uint64) << np.uint64(32)).T   # the 32 module float64 of each env
+    dev = lane_timing.float64_columns(env.snapshot(), n, RECORD, 32)        # the 32 module float64 of each env
     diff = dev != host
     envs = np.flatnonzero(diff.any(1))
     print(f"log caveat: {len(envs)} of {n} envs (seeds 0..{n - 1}) hold a float64 module value after reset(seed) that differs from the host build's "
@@ -89,10 +68,7 @@ def log_caveat(n, host_file):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--sizes", type=int, nargs="+", default=[131072, 1048576])
-    ap.add_argument("--k", type=int, default=32)
+    ap = lane_timing.parser(32)
     ap.add_argument("--log-caveat", type=int, default=0)
     ap.add_argument("--host-file", default=None)
     args = ap.parse_args()
@@ -100,9 +76,6 @@ if __name__ == "__main__":
     if args.log_caveat:
         log_caveat(args.log_caveat, args.host_file)
         sys.exit(0)
-    copy_gbs = copy_bandwidth(torch.device("cuda:0"))
-    print(f"box: {torch.cuda.get_device_name(0)}, torch {torch.__version__}; library {os.environ.get('CGE_AMD_LIBRARY', 'libcge_amd.so')}; "
-          f"device-to-device copy (2-GiB buffers, read + written): {copy_gbs:.0f} GB/s")
-    print("times: device events around work that ends in a synchronise; device-resident int32 actions, reuse_buffers=True, SameStep")
+    copy_gbs = lane_timing.header(library=True)
     for n in args.sizes:
         run(n, args.runs, copy_gbs, args.k)

@@ -18,35 +18,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import custom_gymnasium_environments_amd as cge  # noqa: E402
+from lane_timing import copy_bandwidth, timed  # noqa: E402
 
 K, WARMUP = 50, 200
 STATE = 5 * 16 + 4                               # the record: five uint4 columns + the running return
-
-
-def copy_bandwidth(dev):
-    x = torch.empty(1 << 29, dtype=torch.float32, device=dev)
-    y = torch.empty_like(x)
-    y.copy_(x)
-    torch.cuda.synchronize(dev)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(8):
-        y.copy_(x)
-    b.record()
-    torch.cuda.synchronize(dev)
-    gbs = 2 * x.numel() * 4 / 1e9 / (a.elapsed_time(b) / 8 * 1e-3)
-    del x, y
-    torch.cuda.empty_cache()
-    return gbs
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3            # us
 
 
 def run(n, flat, steps, copy_gbs):
