@@ -813,9 +813,12 @@ __device__ __forceinline__ double gbcast_f64(double x) {
     return x;
 }
 
-// Streams `bytes` (a multiple of 8) of the wave's LDS image to `dst` (16-byte aligned, the image's place in HBM): lane l of the
-// `nact` active lanes (the first nact of the wave) moves the 16-byte pieces l, l + nact, ... — one store instruction = nact x 16
-// CONTIGUOUS bytes, whole 128-byte lines.  (Pieces stored from registers where they arise — 64 contiguous bytes per quad and
+// Streams `bytes` (a multiple of 4) of the wave's LDS image to `dst`, the image's place in HBM: lane l of the `nact` active lanes
+// (the first nact of the wave) moves the 16-byte pieces l, l + nact, ... — one store instruction = nact x 16 CONTIGUOUS bytes, whole
+// 128-byte lines where `dst` is 16-byte aligned.  `dst` is only guaranteed 4-byte alignment: a step of an odd number of envs, or a
+// trajectory stride that is no multiple of 4 floats, starts a wave's rows at any multiple of 4 bytes, and the 16- and 8-byte store
+// forms then run at dword-aligned addresses, which gfx950's global stores take (tests/test_output_bounds_gpu.py pins values and
+// bounds at such addresses).  Writes [dst, dst + bytes) and nothing else.  (Pieces stored from registers where they arise — 64 contiguous bytes per quad and
 // instruction, every line completed by several instructions — cost 1.38x the bytes at the memory side (PMC WRITE_SIZE) and
 // 40 of the 54 us of a 262,144-env rollout step; round 4, profiles/r04_traffic_store_pattern_ab.txt.)
 template <int MAXW>                    // MAXW: words of the largest image (compile time): a full wave's pieces are read in one batch

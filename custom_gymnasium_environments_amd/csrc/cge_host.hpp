@@ -30,7 +30,9 @@ struct HandleBase {
     int32_t *fin_count = nullptr;  // [n_segments]: rows the last rollout delivered for the segment (may exceed fin_cap: the surplus was dropped)
 
     // The handle's device arrays.  alloc() is the only place one is created; free_all(), device_bytes and the snapshot's blobs()
-    // all follow from what it recorded, in registration order.  snap: the array is part of a whole-handle snapshot.
+    // all follow from what it recorded, in registration order.  snap: the array is part of a whole-handle snapshot, and is zeroed
+    // here whatever `zero` says: a snapshot copies the array whole, entries no kernel has written yet included, and must not carry
+    // what hipMalloc happened to hand out (two snapshots of the same state are the same bytes).
     struct Array { void *ptr; size_t bytes; bool snap; };
     std::vector<Array> arrays;
     template <class T>
@@ -39,7 +41,7 @@ struct HandleBase {
         if (e != hipSuccess) return e;
         arrays.push_back({slot, bytes, snap});
         device_bytes += bytes;
-        return zero ? hipMemset(slot, 0, bytes) : hipSuccess;
+        return zero || snap ? hipMemset(slot, 0, bytes) : hipSuccess;
     }
     void free_all() {
         for (const Array &a : arrays) (void)hipFree(a.ptr);

@@ -1183,6 +1183,8 @@ struct cge_snake : HandleBase {
         int32_t idx = 0;
         mt_export_cpython(st.at<uint32_t>(A_MT, j), pos, pretw, (uint32_t *)(p + 32), &idx);
         hdr[7] = idx - (int32_t)left;
+        const size_t used = 32 + (size_t)MT_N * 4 + (size_t)ops.cells * 2;     // odd G: the record's last two bytes are padding, written as zero
+        memset(p + used, 0, record_bytes() - used);
         return CGE_OK;
     }
     void from_record(const uint8_t *p, RecordStage &st, int64_t j) const {

@@ -227,7 +227,7 @@ __device__ __forceinline__ void write_obs(const Env &e, const Params &p, void *b
     } else {
         uint8_t *slab = static_cast<uint8_t *>(base);
         uint32_t *dst = reinterpret_cast<uint32_t *>(slab + row0 * (int64_t)GG);      // row0 is a multiple of 64: 16-byte aligned
-        const uint32_t nbytes = nrows * GG, ndw = (nbytes + 3u) >> 2;                   // a last partial dword ends in the plane's padding
+        const uint32_t nbytes = nrows * GG, ndw = (nbytes + 3u) >> 2;
         if ((GG & 3u) == 0u) {                                                         // rows are whole dwords: the tile is the image
             const uint32_t n16 = ndw >> 2;
 #pragma unroll 2
@@ -235,17 +235,19 @@ __device__ __forceinline__ void write_obs(const Env &e, const Params &p, void *b
             const uint32_t q = 4u * n16 + lane;
             if (q < ndw) dst[q] = tile[q];
         } else {
+            const uint32_t nfull = nbytes >> 2;                                        // whole dwords; the plane's padding is never written
 #pragma unroll 1
-            for (uint32_t q = lane; q < ndw; q += 64u) {
+            for (uint32_t q = lane; q < nfull; q += 64u) {
                 uint32_t v = 0;
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; ++j) {
-                    const uint32_t b = 4u * q + j, bb = b < nbytes ? b : 0u;
-                    const uint32_t r = __umulhi(bb, p.magic_gg), c = bb - r * GG;
-                    v |= (b < nbytes ? (uint32_t)tb[r * RSB + c] : 0u) << (8u * j);
+                    const uint32_t b = 4u * q + j, r = __umulhi(b, p.magic_gg), c = b - r * GG;
+                    v |= (uint32_t)tb[r * RSB + c] << (8u * j);
                 }
                 dst[q] = v;
             }
+            const uint32_t b = 4u * nfull + lane;                                      // the ragged wave's last one to three bytes
+            if (b < nbytes) slab[row0 * (int64_t)GG + b] = tb[__umulhi(b, p.magic_gg) * RSB + (b - __umulhi(b, p.magic_gg) * GG)];
         }
         if (live) {
             const int64_t i = row0 + lane;

@@ -60,6 +60,16 @@
  *     device and is not thread-safe; different handles are independent.
  *   - observations are written row-major as (n_envs, *single_obs_shape), exactly the layout
  *     gymnasium.vector.VectorEnv returns.
+ *   - trajectory strides of the eight types whose rollout states no multiple (snake, crypto, traffic, parking, climate,
+ *     fleet, manufacturing, hospital): obs_step_stride is any number of elements >= one step's n_envs * row — except that
+ *     a snake grid whose G*G is a multiple of 4 takes strides that are multiples of 4 only (cge_snake_rollout refuses
+ *     others).  With a 16-byte-aligned obs_out, steps 1 .. k-1 of such a trajectory then begin at addresses with the
+ *     alignment of the element and no more (float rows 4 bytes, the int8 cells of a snake grid with an odd G*G 1 byte);
+ *     the kernels store their 16- and 8-byte pieces there all the same (an odd n_envs already puts a wave's rows at such
+ *     addresses), write the rows and nothing else, and never write the padding between steps.  Strides that are multiples
+ *     of 4 floats store whole 128-byte lines and are the fast case.  An obs_out that is itself less than 16-byte aligned
+ *     is not a tested configuration.  The types added later state their own multiples at their rollout.  World builder's
+ *     Dict slab: the bytes between its planes are never written either.
  *   - `env_index0` is the global index of the handle's first env: per-env seeds and the synthetic
  *     action hash are functions of the GLOBAL index so results do not depend on how a batch is
  *     sharded over GPUs.
@@ -163,7 +173,8 @@ int cge_snake_info(cge_snake *h, int32_t field_id, int32_t *out, void *stream);
 int cge_snake_render_rgb(cge_snake *h, uint8_t *rgb_out, void *stream);
 /* canonical per-env state record (host memory), identical to the oracle's: 8 int32 {len, dir, food_r,
  * food_c, score, steps, needs_reset, mt_idx}, uint32 mt[624] (CPython layout: words >= mt_idx are
- * generated-but-unconsumed), uint16 body[G*G] head first (0xFFFF unused), padded to 4 bytes. */
+ * generated-but-unconsumed), uint16 body[G*G] head first (0xFFFF unused), zero-padded to 4 bytes
+ * (get_state writes the padding too: every byte of host_buf is written). */
 size_t cge_snake_state_bytes(const cge_snake *h);
 int cge_snake_get_state(cge_snake *h, void *host_buf, void *stream);
 int cge_snake_set_state(cge_snake *h, const void *host_buf, void *stream);
