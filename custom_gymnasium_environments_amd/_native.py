@@ -118,6 +118,8 @@ _EXTRAS = {
     "final_obs_rows": {},    # the same two under cge_rows_<env>_* (_env_signatures): beside a surface cge_<env>_* that stays as it is
     "state": {"state_bytes": (_sz, [_vp]), "get_state": _host_buf, "set_state": _host_buf},
     "snapshot": {"snapshot_bytes": (_sz, [_vp]), "snapshot_get": _host_buf, "snapshot_set": _host_buf},
+    # canonical records packed on the device, under cge_records_<env>_* (_env_signatures): the four record-lane types, beside their snapshots
+    "records": {},
     "done_mask": {"done_mask": (C.c_int, [_vp, _vp])},
     "info": {"info": (C.c_int, [_vp, _i32, _vp, _vp])},
     "info_indexed": {"info": (C.c_int, [_vp, _i32, _i32, _vp, _vp])},
@@ -140,11 +142,12 @@ _ENV_TYPES = {
     "bus": (BusConfig, "final_obs_rows info_indexed error_count snapshot"),
     "world_builder": (WorldBuilderConfig, "final_obs_rows info_indexed error_count state"),
     "restaurant": (RestaurantConfig, "final_obs_rows info error_count snapshot"),
-    "airline": (AirlineConfig, "info error_count snapshot"),
-    "emergency": (EmergencyConfig, "final_obs_rows info error_count snapshot"),
-    "space_station": (SpaceStationConfig, "final_obs_rows info error_count snapshot"),
-    "farm": (FarmConfig, "final_obs_rows info error_count snapshot"),
+    "airline": (AirlineConfig, "info error_count snapshot records"),
+    "emergency": (EmergencyConfig, "final_obs_rows info error_count snapshot records"),
+    "space_station": (SpaceStationConfig, "final_obs_rows info error_count snapshot records"),
+    "farm": (FarmConfig, "final_obs_rows info error_count snapshot records"),
 }
+_RECORDS = dict(_EXTRAS["state"], pack=(C.c_int, [_vp, _i64, _i64, _vp, _vp]), unpack=(C.c_int, [_vp, _i64, _i64, _vp, _vp]))
 _HAVE_DEFAULT_CONFIG = ("crypto", "traffic")         # the two config structs the library fills with the reference's defaults
 
 
@@ -157,6 +160,8 @@ def _env_signatures(env, config, extras):
     out = {f"cge_{env}_{name}": proto for name, proto in sig.items()}
     if "final_obs_rows" in extras.split():
         out.update({f"cge_rows_{env}_{name}": proto for name, proto in _EXTRAS["final_obs"].items()})
+    if "records" in extras.split():
+        out.update({f"cge_records_{env}_{name}": proto for name, proto in _RECORDS.items()})
     return out
 
 

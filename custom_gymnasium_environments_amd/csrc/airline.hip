@@ -311,5 +311,6 @@ int cge_airline_info(cge_airline *h, int32_t field_id, double *out, void *stream
 
 CGE_DEFINE_ERROR_COUNT(airline)
 CGE_DEFINE_SNAPSHOT(airline)
+CGE_DEFINE_LANE_RECORDS(airline, LANE_RECORDS_AIRLINE, nullptr)
 
 }  // extern "C"

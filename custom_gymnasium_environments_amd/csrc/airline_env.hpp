@@ -422,5 +422,34 @@ CGE_HD void observe_part(const Env &e, M &m, F out) {
     }
 }
 
+
+// Canonical records (cge_records_airline_*, lane_records.hip): what a record's body must satisfy before it may become an env, so that
+// no kernel of the type reads or writes out of range.  get(w) is word w of the body.  The fields a kernel uses as an index or a bound:
+//   airport, destination (aircraft word, 4 bits each)   the airport rows (masks of grounded aircraft, fuel prices): 0..NP-1
+//   origin, destination (flight word, 4 bits each)      the airport rows; the destination becomes an aircraft's: 0..NP-1
+//   aircraft (flight word, 5 bits)                      a boarding flight indexes the aircraft rows by it: 0..NA-1
+// The number of weather systems (2 bits) is compared with compile-time indices only, the hour wraps by comparison, the flight an
+// action picks is drawn below 51.  No kernel calls this.
+enum { RECORD_OK = 0, RECORD_AIRCRAFT_AIRPORT = 16, RECORD_FLIGHT_AIRPORT = 17, RECORD_FLIGHT_AIRCRAFT = 18 };
+template <class G>
+CGE_HD int record_refusal(G get) {
+    for (int a = 0; a < NA; ++a) {
+        const uint32_t w = get(W_AC + a);
+        if (ac_airport(w) >= (uint32_t)NP || ac_dest(w) >= (uint32_t)NP) return RECORD_AIRCRAFT_AIRPORT;
+    }
+    for (int f = 0; f < NF; ++f) {
+        const uint32_t w = get(W_FLIGHT + f);
+        if (fl_origin(w) >= (uint32_t)NP || fl_dest(w) >= (uint32_t)NP) return RECORD_FLIGHT_AIRPORT;
+        if (fl_aircraft(w) >= (uint32_t)NA) return RECORD_FLIGHT_AIRCRAFT;
+    }
+    return RECORD_OK;
+}
+inline const char *record_refusal_text(int code) {
+    return code == RECORD_AIRCRAFT_AIRPORT ? "an aircraft's airport or destination is above 14"
+           : code == RECORD_FLIGHT_AIRPORT ? "a flight's origin or destination is above 14"
+           : code == RECORD_FLIGHT_AIRCRAFT ? "a flight's aircraft is above 24" : "bad record";
+}
+constexpr int RECORD_CURSOR_FIRST = W_SCAL + 13, RECORD_CURSOR_WORDS = 1;   // mt_pos; the type keeps no ready mark
+
 }  // namespace airline
 }  // namespace cge

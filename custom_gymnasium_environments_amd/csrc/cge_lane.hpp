@@ -372,4 +372,41 @@ int lane_rollout(H *h, bool env_ok, const char *what, int32_t k_steps, const int
     return launched(h);
 }
 
+// ----------------------------------------------------------------------------------- host: canonical records (lane_records.hip)
+// cge_records_<env>_* of the four record-lane types: per-env records packed and unpacked on the device (include/cge_amd.h has the
+// layout, lane_records.hip the kernels and the drivers).  A handle shows the drivers what they need of it as a LaneRecords: its
+// type's number, the columns, and the generator blocks of its streams in the record's order.  The staging buffer of the host forms
+// and the status block of a check are transient, allocated and freed inside the call: device_bytes and the snapshot do not move.
+enum { LANE_RECORDS_AIRLINE = 1, LANE_RECORDS_EMERGENCY = 2, LANE_RECORDS_STATION = 3, LANE_RECORDS_FARM = 4 };
+struct LaneRecords {
+    HandleBase *h;
+    const char *abi;               // "cge_records_<env>", the prefix of the error texts
+    int type;
+    uint32_t *state, *mt[2];
+};
+size_t lane_records_bytes(int type);
+int lane_records_pack(const LaneRecords &v, int64_t first, int64_t count, void *dev_records, hipStream_t s);
+int lane_records_unpack(const LaneRecords &v, int64_t first, int64_t count, const void *dev_records, hipStream_t s);
+int lane_records_get(const LaneRecords &v, void *host_buf, hipStream_t s);
+int lane_records_set(const LaneRecords &v, const void *host_buf, hipStream_t s);
+
+// the five entry points (inside extern "C"); SECOND: the handle's second stream (farm's `py`), or nullptr
+#define CGE_DEFINE_LANE_RECORDS(ENV, TYPE, SECOND)                                                                                          \
+    static cge::LaneRecords records_of(cge_##ENV *h) {                                                                                      \
+        return cge::LaneRecords{h, "cge_records_" #ENV, TYPE, reinterpret_cast<uint32_t *>(h->state), {h->mt, SECOND}};                     \
+    }                                                                                                                                       \
+    size_t cge_records_##ENV##_state_bytes(const cge_##ENV *h) { return h ? cge::lane_records_bytes(TYPE) : 0; }                            \
+    int cge_records_##ENV##_get_state(cge_##ENV *h, void *host_buf, void *stream) {                                                         \
+        return h ? cge::lane_records_get(records_of(h), host_buf, cge::as_stream(stream)) : CGE_ERR_INVALID_ARG;                            \
+    }                                                                                                                                       \
+    int cge_records_##ENV##_set_state(cge_##ENV *h, const void *host_buf, void *stream) {                                                   \
+        return h ? cge::lane_records_set(records_of(h), host_buf, cge::as_stream(stream)) : CGE_ERR_INVALID_ARG;                            \
+    }                                                                                                                                       \
+    int cge_records_##ENV##_pack(cge_##ENV *h, int64_t first, int64_t count, void *dev_records, void *stream) {                             \
+        return h ? cge::lane_records_pack(records_of(h), first, count, dev_records, cge::as_stream(stream)) : CGE_ERR_INVALID_ARG;          \
+    }                                                                                                                                       \
+    int cge_records_##ENV##_unpack(cge_##ENV *h, int64_t first, int64_t count, const void *dev_records, void *stream) {                     \
+        return h ? cge::lane_records_unpack(records_of(h), first, count, dev_records, cge::as_stream(stream)) : CGE_ERR_INVALID_ARG;        \
+    }
+
 }  // namespace cge

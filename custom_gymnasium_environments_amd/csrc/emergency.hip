@@ -367,5 +367,6 @@ int cge_emergency_info(cge_emergency *h, int32_t field_id, double *out, void *st
 CGE_DEFINE_ROWS_FINAL_OBS(emergency, float, 64)
 CGE_DEFINE_ERROR_COUNT(emergency)
 CGE_DEFINE_SNAPSHOT(emergency)
+CGE_DEFINE_LANE_RECORDS(emergency, LANE_RECORDS_EMERGENCY, nullptr)
 
 }  // extern "C"

@@ -480,5 +480,30 @@ CGE_HD void observe_rest(const Env &e, M &m, F &out, uint32_t max_timesteps) {
     out(275, (float)((double)e.t / (double)max_timesteps));
 }
 
+
+// Canonical records (cge_records_emergency_*, lane_records.hip): what a record's body must satisfy before it may become an env, so that
+// no kernel of the type reads or writes out of range.  get(w) is word w of the body.  The fields a kernel uses as an index or a bound:
+//   ninc (scalar word 24, 5 bits)   every walk over the incidents, add_incident's slot: rows 0..NI-1 of the incident words
+//   mask (incident word 1)          the release walk of a contained incident indexes the unit rows by every set bit: bits 0..NU-1
+//   slot (unit word, 5 bits)        a working unit indexes the incident rows by it: 0..NI-1
+// Every slot of the twenty is checked, used or not: a stale one holds what a valid one held.  Nothing else in the record reaches an
+// address: coordinates, kinds, severities and counters enter arithmetic only, the stations are indexed at compile time.  No kernel
+// calls this.
+enum { RECORD_OK = 0, RECORD_NINC = 16, RECORD_MASK = 17, RECORD_SLOT = 18 };
+template <class G>
+CGE_HD int record_refusal(G get) {
+    if ((get(W_SCAL + 24) & 31u) > (uint32_t)NI) return RECORD_NINC;
+    for (int s = 0; s < NI; ++s)
+        if (get(W_INC + 3 * s + 1) >> NU) return RECORD_MASK;
+    for (int u = 0; u < NU; ++u)
+        if (un_slot(get(W_UNIT + u)) >= (uint32_t)NI) return RECORD_SLOT;
+    return RECORD_OK;
+}
+inline const char *record_refusal_text(int code) {
+    return code == RECORD_NINC ? "more than 20 active incidents" : code == RECORD_MASK ? "an incident's unit mask names a unit above 19"
+           : code == RECORD_SLOT ? "a unit's incident slot is above 19" : "bad record";
+}
+constexpr int RECORD_CURSOR_FIRST = W_SCAL + 29, RECORD_CURSOR_WORDS = 2;   // mt_pos, mt_ready
+
 }  // namespace emergency
 }  // namespace cge

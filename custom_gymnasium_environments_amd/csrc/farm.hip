@@ -352,5 +352,6 @@ int cge_farm_info(cge_farm *h, int32_t field_id, double *out, void *stream) {
 CGE_DEFINE_ROWS_FINAL_OBS(farm, float, 64)
 CGE_DEFINE_ERROR_COUNT(farm)
 CGE_DEFINE_SNAPSHOT(farm)
+CGE_DEFINE_LANE_RECORDS(farm, LANE_RECORDS_FARM, h->py)
 
 }  // extern "C"

@@ -631,5 +631,26 @@ CGE_HD double info_value(const Env &e, int field) {
     return 0.0;
 }
 
+
+// Canonical records (cge_records_farm_*, lane_records.hip): what a record's body must satisfy before it may become an env.  get(w) is
+// word w of the body.  No field of a farm record reaches an address (crops, stages and seasons select among constants), but
+//   stage (field word 0, 4 bits)                picks a byte of stage_days' 64-bit table, the divisor of `since % stage_days`: 0..7
+//   crop, last_crop (field word 0, 4 bits each, stored + 1)   -1..4, the five crops and "none"
+// has_gauss is one bit of integer word 21 and cannot be anything but 0 or 1.  No kernel calls this.
+enum { RECORD_OK = 0, RECORD_STAGE = 16, RECORD_CROP = 17 };
+template <class G>
+CGE_HD int record_refusal(G get) {
+    for (int k = 0; k < NF; ++k) {
+        const uint32_t w = get(W_INT + 4 * k);
+        if (((w >> 4) & 15u) > (uint32_t)DORMANT) return RECORD_STAGE;
+        if ((w & 15u) > (uint32_t)NCROP || ((w >> 8) & 15u) > (uint32_t)NCROP) return RECORD_CROP;
+    }
+    return RECORD_OK;
+}
+inline const char *record_refusal_text(int code) {
+    return code == RECORD_STAGE ? "a field's growth stage is above 7" : code == RECORD_CROP ? "a field's crop or last crop is not one of the five" : "bad record";
+}
+constexpr int RECORD_CURSOR_FIRST = W_INT + 24, RECORD_CURSOR_WORDS = 4;   // mt_pos, mt_ready, py_pos, py_ready
+
 }  // namespace farm
 }  // namespace cge

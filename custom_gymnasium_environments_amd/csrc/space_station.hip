@@ -295,5 +295,6 @@ int cge_space_station_info(cge_space_station *h, int32_t field_id, double *out, 
 CGE_DEFINE_ROWS_FINAL_OBS(space_station, float, 64)
 CGE_DEFINE_ERROR_COUNT(space_station)
 CGE_DEFINE_SNAPSHOT(space_station)
+CGE_DEFINE_LANE_RECORDS(space_station, LANE_RECORDS_STATION, nullptr)
 
 }  // extern "C"

@@ -462,5 +462,20 @@ CGE_HD double info_value(const Env &e, int field) {
     return 0.0;
 }
 
+
+// Canonical records (cge_records_space_station_*, lane_records.hip): what a record's body must satisfy before it may become an env, so
+// that no kernel of the type reads out of range.  get(w) is word w of the body.  The fields a kernel uses as an index:
+//   phase, angle (scalar word 6, 5 bits each)   the three tables of eighteen orbit positions: 0..17
+// Modules, crew and systems are indexed at compile time or by a draw below their count.  The type keeps no cached Gaussian: a
+// reset's sixteen polar pairs leave none.  No kernel calls this.
+enum { RECORD_OK = 0, RECORD_PHASE = 16 };
+template <class G>
+CGE_HD int record_refusal(G get) {
+    const uint32_t o = get(W_SCAL + 6);
+    return (o & 31u) >= 18u || ((o >> 5) & 31u) >= 18u ? RECORD_PHASE : RECORD_OK;
+}
+inline const char *record_refusal_text(int code) { return code == RECORD_PHASE ? "orbit phase or angle is above 17" : "bad record"; }
+constexpr int RECORD_CURSOR_FIRST = W_SCAL + 7, RECORD_CURSOR_WORDS = 2;   // mt_pos, mt_ready
+
 }  // namespace station
 }  // namespace cge

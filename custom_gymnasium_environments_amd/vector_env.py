@@ -81,6 +81,7 @@ def checked_seed(seed, num_envs, env_index0, bits):
 
 
 TERMINATED, TRUNCATED, BOTH, TERMINATED_AT_LIMIT = "terminated", "truncated", "both", "terminated_at_limit"
+_RECORD_CALLS = ("state_bytes", "get_state", "set_state", "pack", "unpack")
 
 
 class DeviceVectorEnv(VectorEnvBase):
@@ -164,6 +165,8 @@ class DeviceVectorEnv(VectorEnvBase):
     def _fn(self, name):
         if name in ("rollout_final_obs", "final_obs_segment") and not hasattr(self._lib, f"{self._abi}_{name}"):
             return getattr(self._lib, f"cge_rows_{self._abi[4:]}_{name}")      # the lane-per-env types but airline: cge_rows_<env>_* (cge_amd.h)
+        if name in _RECORD_CALLS and not hasattr(self._lib, f"{self._abi}_{name}"):
+            return getattr(self._lib, f"cge_records_{self._abi[4:]}_{name}")   # the record-lane types: cge_records_<env>_* (cge_amd.h)
         return getattr(self._lib, f"{self._abi}_{name}")
 
     def _check(self, status, what):
@@ -361,19 +364,82 @@ class DeviceVectorEnv(VectorEnvBase):
         """The reference's own `info` dict (its keys, its derived expressions) as tensors; subclasses define it."""
         raise NotImplementedError
 
-    def get_state(self):
-        """Canonical per-env state records, uint8 [N, state_bytes] on the host (snake, crypto, traffic, world builder; the others:
-        `snapshot()`).  `set_state` checks every record before it writes one: a refused buffer leaves the batch as it was."""
-        buf = np.zeros((self.num_envs, int(self._fn("state_bytes")(self._h))), np.uint8)
-        self._check(self._fn("get_state")(self._h, buf.ctypes.data, self._stream()), "get_state")
-        return buf
+    def _device_records(self):
+        """Does the type pack its records on the device (airline, emergency, space station, farm: cge_records_<env>_*)?"""
+        return hasattr(self._lib, f"cge_records_{self._abi[4:]}_pack")
 
-    def set_state(self, buf):
+    def _record_range(self, first, count):
+        first = int(first)
+        if first < 0 or first + count > self.num_envs:
+            raise ValueError(f"envs [{first}, {first + count}) are not within [0, {self.num_envs})")
+        return first
+
+    def _record_call(self, name, fn, *args):
+        """A records call whose refusal of its input (CGE_ERR_INVALID_ARG: a record the check refuses) is a ValueError with the
+        library's text, which names the env."""
+        status = fn(self._h, *args, self._stream())
+        if status == -1 and self._device_records():
+            raw = self._c_last_error(self._h)
+            raise ValueError(raw.decode() if raw else f"{self._abi}_{name}: invalid argument")
+        self._check(status, name)
+
+    def get_state(self, out=None, first=0):
+        """Canonical per-env state records, uint8 [N, state_bytes] on the host (snake, crypto, traffic, world builder, and airline,
+        emergency, space station, farm; the others: `snapshot()`).  The last four pack their records on the device: with `out` a
+        contiguous CUDA uint8 tensor [M, state_bytes] the records of envs [first, first + M) are packed into it, with
+        `out="device"` into a new tensor of envs [first, N), and that tensor is returned — nothing passes through the host.
+        `set_state` checks every record before it writes one: a refused buffer leaves the batch as it was."""
         rec = int(self._fn("state_bytes")(self._h))
+        if out is None and not first:
+            buf = np.zeros((self.num_envs, rec), np.uint8)
+            self._check(self._fn("get_state")(self._h, buf.ctypes.data, self._stream()), "get_state")
+            return buf
+        if not self._device_records():
+            raise NotImplementedError(f"{self._abi}: records on the device and sub-ranges are for the types that pack them there")
+        if isinstance(out, torch.Tensor):
+            t = out
+        elif out is None or out == "device":                       # None with `first`: envs [first, N) on the host
+            first = self._record_range(first, 0)
+            t = torch.empty((self.num_envs - first, rec), dtype=torch.uint8, device=self.device)
+        else:
+            raise ValueError('out must be a CUDA uint8 tensor, "device" or None')
+        self._check_records(t, rec)
+        first = self._record_range(first, t.shape[0])
+        self._record_call("pack", self._fn("pack"), first, t.shape[0], t.data_ptr())
+        return t if out is not None else t.cpu().numpy()
+
+    def _check_records(self, t, rec):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] == rec):
+            raise ValueError(f"records must be a uint8 tensor [M, {rec}]")
+        if t.device != self.device:
+            raise ValueError(f"records must be on {self.device}, got {t.device}")
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("records must be contiguous and 16-byte aligned")
+
+    def set_state(self, buf, first=0):
+        """Takes what `get_state` returns: a host array of all N records, or (the four types that pack on the device) a CUDA uint8
+        tensor [M, state_bytes] for envs [first, first + M); a host array with `first` goes through such a tensor."""
+        rec = int(self._fn("state_bytes")(self._h))
+        if isinstance(buf, torch.Tensor) and buf.device.type == "cuda" or first:
+            if not self._device_records():
+                raise NotImplementedError(f"{self._abi}: records on the device and sub-ranges are for the types that pack them there")
+            if not (isinstance(buf, torch.Tensor) and buf.device.type == "cuda"):
+                host = np.ascontiguousarray(buf, dtype=np.uint8)
+                if host.ndim != 2 or host.shape[1] != rec:
+                    raise ValueError(f"state buffer must be uint8 [M, {rec}]")
+                buf = torch.from_numpy(host).to(self.device)
+            self._check_records(buf, rec)
+            first = self._record_range(first, buf.shape[0])
+            self._record_call("unpack", self._fn("unpack"), first, buf.shape[0], buf.data_ptr())
+            return
+        if isinstance(buf, torch.Tensor):
+            buf = buf.numpy()
+        if not (isinstance(buf, np.ndarray) and buf.dtype == np.uint8) and self._device_records():
+            raise ValueError(f"state buffer must be uint8 {(self.num_envs, rec)}")
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         if buf.shape != (self.num_envs, rec):
             raise ValueError(f"state buffer must be uint8 {(self.num_envs, rec)}")
-        self._check(self._fn("set_state")(self._h, buf.ctypes.data, self._stream()), "set_state")
+        self._record_call("set_state", self._fn("set_state"), buf.ctypes.data)
 
     # ------------------------------------------------------------------ episode statistics
     def record_episode_statistics(self, enable=True):

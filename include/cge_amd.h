@@ -1191,6 +1191,84 @@ const char *cge_world_builder_last_error(const cge_world_builder *h);
 const char *cge_world_builder_last_kernel(const cge_world_builder *h);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Canonical per-env records of airline, emergency, space station and farm: cge_records_<env>_*  */
+/*   They stand beside the types' surfaces cge_<env>_*, which are as they were (snapshots        */
+/*   included).  The records are packed and unpacked by kernels, so they can stay on the device: */
+/*   copy the best envs over the worst, branch many envs from one, move a sub-range between       */
+/*   handles of any size and env_index0.                                                          */
+/*                                                                                                */
+/*   One layout rule for the four.  A record is state_bytes contiguous bytes; every section is    */
+/*   padded with zero bytes to a multiple of 16:                                                  */
+/*     header  int32[8]: {0x4C520100 | type (1 airline, 2 emergency, 3 space station, 4 farm),    */
+/*             the number of body words (CGE_<ENV>_RECORD_BYTES / 4), the number of generator     */
+/*             streams, stream 0's index, stream 1's index (farm; otherwise 0), 0, 0, 0}.  An     */
+/*             index is the reference's, 0..624: CPython's getstate()[1][624], NumPy's `pos`.     */
+/*     body    the type's CGE_<ENV>_RECORD_BYTES / 4 32-bit words in column order, exactly as the */
+/*             device holds them (DESIGN.md has each type's columns), except that the words that  */
+/*             hold the device's stream cursors and ready marks read zero: airline word 243;      */
+/*             emergency 199-200; space station 185-186; farm 202-205.  What a cursor means is    */
+/*             in the header; a ready mark is not state.  Farm's cached legacy Gaussian and its   */
+/*             flag (one bit) are body words and untouched: they belong to the stream.  The space */
+/*             station keeps none (a reset's sixteen polar pairs leave the cache empty).          */
+/*     streams 624 uint32 words of ONE generation each, such that with the header's index         */
+/*             random.setstate((3, tuple(words) + (index,), None)) — for a NumPy legacy stream    */
+/*             np.random.set_state(('MT19937', words, index, has_gauss, cached)) — continues the  */
+/*             env's stream.  Airline, emergency: one CPython stream.  Space station: one NumPy   */
+/*             legacy stream.  Farm: the NumPy legacy stream, then the CPython one.  Words of the */
+/*             next generation that the device twisted ahead are taken back, the rest of the      */
+/*             current generation is twisted.  THE LOW 31 BITS OF WORD 0 ALWAYS READ ZERO: taking */
+/*             words back cannot recover them, the records keep no saved copy, and no future      */
+/*             output of MT19937 depends on them once the generation is complete (word 0 enters   */
+/*             the next generation through its top bit only).  unpack ignores them.               */
+/*   state_bytes: airline 4192, emergency 3344, space station 3280, farm 5856.                    */
+/*   Two envs in the same logical state have the same bytes, whatever launches got them there.    */
+/*                                                                                                */
+/*   unpack and set_state check every record before anything is written and refuse: a wrong tag,  */
+/*   word count or stream count; an index above 624; a non-zero reserved header word, cursor word */
+/*   or padding byte; and every field that a step, reset or info kernel uses as an index or a     */
+/*   bound (the predicate is record_refusal in the type's <env>_env.hpp):                         */
+/*     airline        aircraft airport / destination > 14; flight origin / destination > 14;      */
+/*                    flight aircraft > 24                                                         */
+/*     emergency      more than 20 incidents; an incident's unit mask with a bit above 19; a      */
+/*                    unit's incident slot > 19                                                    */
+/*     space station  orbit phase or angle > 17                                                    */
+/*     farm           a field's stage > 7 (it selects the divisor of a modulo); a crop or last    */
+/*                    crop outside -1..4.  has_gauss is one bit and cannot be out of {0, 1}.      */
+/*   A record that passes cannot make a kernel of its type read or write out of range.  A refusal */
+/*   is CGE_ERR_INVALID_ARG with last_error "cge_records_<env>_unpack: env I: reason" (or         */
+/*   _set_state), I the lowest refused env, and every env is as it was.                            */
+/*                                                                                                */
+/*   pack / unpack: envs [first, first + count) <-> count records at dev_records, a DEVICE buffer */
+/*   of count * state_bytes bytes, 16-byte aligned.  A range outside [0, n_envs], a null or a     */
+/*   misaligned pointer is CGE_ERR_INVALID_ARG.  pack reads the handle and writes the records     */
+/*   only.  Both wait for `stream` before they return (unpack reads the check's verdict): they    */
+/*   are not for graph capture.  get_state / set_state: host memory, n_envs * state_bytes, moved  */
+/*   in rounds of 4,096 envs through a transient device staging buffer of one round; set_state    */
+/*   checks every round before it unpacks any.  The staging buffer and the status block are       */
+/*   allocated and freed inside the call: device_bytes and snapshot_bytes are as they were.       */
+/* ------------------------------------------------------------------------------------------ */
+size_t cge_records_airline_state_bytes(const cge_airline *h);
+int cge_records_airline_get_state(cge_airline *h, void *host_buf, void *stream);
+int cge_records_airline_set_state(cge_airline *h, const void *host_buf, void *stream);
+int cge_records_airline_pack(cge_airline *h, int64_t first, int64_t count, void *dev_records, void *stream);
+int cge_records_airline_unpack(cge_airline *h, int64_t first, int64_t count, const void *dev_records, void *stream);
+size_t cge_records_emergency_state_bytes(const cge_emergency *h);
+int cge_records_emergency_get_state(cge_emergency *h, void *host_buf, void *stream);
+int cge_records_emergency_set_state(cge_emergency *h, const void *host_buf, void *stream);
+int cge_records_emergency_pack(cge_emergency *h, int64_t first, int64_t count, void *dev_records, void *stream);
+int cge_records_emergency_unpack(cge_emergency *h, int64_t first, int64_t count, const void *dev_records, void *stream);
+size_t cge_records_space_station_state_bytes(const cge_space_station *h);
+int cge_records_space_station_get_state(cge_space_station *h, void *host_buf, void *stream);
+int cge_records_space_station_set_state(cge_space_station *h, const void *host_buf, void *stream);
+int cge_records_space_station_pack(cge_space_station *h, int64_t first, int64_t count, void *dev_records, void *stream);
+int cge_records_space_station_unpack(cge_space_station *h, int64_t first, int64_t count, const void *dev_records, void *stream);
+size_t cge_records_farm_state_bytes(const cge_farm *h);
+int cge_records_farm_get_state(cge_farm *h, void *host_buf, void *stream);
+int cge_records_farm_set_state(cge_farm *h, const void *host_buf, void *stream);
+int cge_records_farm_pack(cge_farm *h, int64_t first, int64_t count, void *dev_records, void *stream);
+int cge_records_farm_unpack(cge_farm *h, int64_t first, int64_t count, const void *dev_records, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Action-space sampler: `action_space.sample()` of a batched space on the device               */
 /*   Every reference script drives its env with env.action_space.sample() (snake_env_classic/    */
 /*   example.py:23, smart_parking_env/examples/test_env.py:52, traffic_management_env/demo.py:49, */
