@@ -88,7 +88,7 @@ class WorldBuilderVectorEnv(SlabVectorEnv):
         self._init_common(num_envs, device, autoreset_mode, env_index0, reuse_buffers)
         self.grid_size, self.flatten_obs = int(grid_size), bool(flatten_obs)
         self.single_observation_space, self.single_action_space = make_spaces(self.grid_size, self.flatten_obs)
-        self._offsets = slab_layout(self.num_envs, self.grid_size)[0]          # read by tests/test_world_builder_gpu.py only
+        self._offsets = slab_layout(self.num_envs, self.grid_size)[0]          # {key: byte offset}; nothing in the package or in tests/ reads it any more
         if self.flatten_obs:                                                    # plain float32 rows: no slab, no dict of views
             self._obs_dtype, self._obs_shape, self._wrap_obs = torch.float32, (self.num_envs, self.grid_size * self.grid_size + 6), None
         else:

@@ -2,7 +2,8 @@
 tests/test_<type>_gpu.py and tests/test_<type>_cpu.py share.  A per-type file starts with one table of that type's values, SPEC, and
 keeps every test under its own name as a function of a line that hands SPEC to the body here: a test is found where it always was,
 by pytest and by whoever reads the file.  Where the copies of a body had drifted apart, the body here makes every assertion that any
-copy made.  Every comparison is array_equal on bit patterns or torch.equal and skips no rows.
+copy made.  Every comparison is array_equal on bit patterns or torch.equal and skips no rows.  The three slab types (bus, world builder,
+restaurant; tests/_slab_kit.py) take `cge`, `dev`, `f32`, `make`, the warm-up of a capture and the two CPU checks of the C ABI from here.
 
 What a `spec` (a types.SimpleNamespace) holds:
   m          the type's model module (tests/<type>_model.py)       kind     its name in csrc/ and tools/probes/ ("space_station")
@@ -11,6 +12,7 @@ What a `spec` (a types.SimpleNamespace) holds:
   obs        the row's width                                       actions  the number of actions
   info       the reference's info keys in a fixture's order        clock    the info field that counts the steps
   live       rows (of `rows` only) as the fixture holds them       bad      the two out-of-range actions next to -1 and the int32 ends
+  abi        the functions of the type's C ABI (ABI below for all but world builder)
 and the fixture names, seeds, sizes and thresholds of the single tests, named after them."""
 import ctypes
 import json
@@ -505,7 +507,7 @@ def abi_is_declared_exported_and_bound(spec):
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     prefix = f"cge_{spec.kind}_"
     declared = set(re.findall(r"\b(" + prefix + r"[a-z0-9_]+)\s*\(", src))
-    assert declared == {prefix + fn for fn in ABI}
+    assert declared == {prefix + fn for fn in spec.abi}                   # ABI, or world builder's list with canonical records for snapshots
     assert {n for n in _native.SIGNATURES if n.startswith(prefix)} == declared
     build.build_native()
     L = ctypes.CDLL(_native.LIB_PATH)

@@ -188,11 +188,8 @@ def make_env(cge, name, n, env_index0=0, **kw):
 def _host(env, name, obs):
     """a device observation (or trajectory) as the reference side holds it"""
     if name in ("Bus", "Restaurant"):
-        import bus_model, restaurant_model
-        mod = bus_model if name == "Bus" else restaurant_model
-        off = np.cumsum([0] + [int(np.prod(mod.KEY_SHAPES[key])) for key in mod.KEYS])
-        slab, n = env.obs_slab(obs).cpu().numpy(), env.num_envs                # ONE copy of the slab behind the dict of views
-        return {key: slab[..., off[j] * n:off[j + 1] * n].reshape(slab.shape[:-1] + (n,) + mod.KEY_SHAPES[key]) for j, key in enumerate(mod.KEYS)}
+        from _slab_kit import host
+        return host(env, obs)                                                  # ONE copy of the slab behind the dict of views
     return obs.cpu().numpy()
 
 

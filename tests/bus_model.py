@@ -14,9 +14,9 @@ import random
 import numpy as np
 
 import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP  # noqa: F401
 
 NUM_STOPS, NUM_BUSES, BUS_CAPACITY, MAX_PASSENGERS, MAX_TIMESTEPS, MAX_DWELL_TIME, TRAVEL = 4, 4, 20, 150, 500, 10, 5
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("bus_stops", "bus_states", "bus_remaining_times", "bus_capacities", "bus_passenger_destinations", "stop_waiting_counts",
         "stop_destination_distributions", "timestep", "total_delivered", "total_waiting", "total_onboard")
 KEY_SHAPES = {"bus_stops": (4,), "bus_states": (4,), "bus_remaining_times": (4,), "bus_capacities": (4,), "bus_passenger_destinations": (4, 4),

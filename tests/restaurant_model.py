@@ -17,8 +17,8 @@ import random
 import numpy as np
 
 import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP  # noqa: F401
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("waiting_customers", "waiter_status", "table_occupancy", "table_cleanliness", "kitchen_queue", "ready_orders", "current_timestep")
 KEY_SHAPES = {"waiting_customers": (50, 2), "waiter_status": (10, 3), "table_occupancy": (10,), "table_cleanliness": (10,),
               "kitchen_queue": (50, 3), "ready_orders": (20, 2), "current_timestep": (1,)}
@@ -190,6 +190,7 @@ class RestaurantModel:
     def total_reward(self):
         return np.array([e.total for e in self.envs], np.float64)
 
+    @property
     def needs_reset(self):
         return np.array([e.needs_reset for e in self.envs])
 

@@ -20,7 +20,7 @@ from conftest import ROOT, golden
 FIXTURES = ["airline_hash.npz", "airline_dispatch.npz", "airline_cancel.npz", "airline_overrun.npz"]
 SPEC = types.SimpleNamespace(
     m=am, kind="airline", env="AirlineVectorEnv", model=am.AirlineModel, model_kw={}, limit=None, actions=45,
-    fixtures=FIXTURES, poked=None, recorded=160, info_keys=list(am.INFO), config=("AirlineConfig", 8, None))
+    fixtures=FIXTURES, poked=None, recorded=160, info_keys=list(am.INFO), config=("AirlineConfig", 8, None), abi=kit.ABI)
 
 
 @pytest.mark.parametrize("name", FIXTURES)

@@ -1,20 +1,19 @@
 """CPU-side checks of the bus-system env: the counts model (tests/bus_model.py) reproduces, value for value, what the unmodified
 reference recorded (tests/golden/bus_*.npz, written by tests/golden/gen/gen_bus.py); the C ABI is declared, exported and bound; there
 is no CPU path; the spaces are the reference's."""
-import ctypes
 import json
 import os
-import re
+import types
 
 import numpy as np
 import pytest
 
+import _lane_kit as kit
 import bus_model as bm
 from conftest import ROOT, golden
 
 FIXTURES = ["bus_hash.npz", "bus_dwell.npz", "bus_short.npz"]
-ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
-       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
+SPEC = types.SimpleNamespace(kind="bus", env="BusVectorEnv", config=("BusConfig", 8, None), abi=kit.ABI)
 
 
 @pytest.mark.parametrize("name", FIXTURES)
@@ -55,27 +54,11 @@ def test_fixtures_cover_what_they_are_for():
 
 
 def test_abi_is_declared_exported_and_bound():
-    from custom_gymnasium_environments_amd import _native, build
-    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(cge_bus_[a-z0-9_]+)\s*\(", src))
-    assert declared == {f"cge_bus_{fn}" for fn in ABI}
-    assert {n for n in _native.SIGNATURES if n.startswith("cge_bus_")} == declared
-    build.build_native()
-    L = ctypes.CDLL(_native.LIB_PATH)
-    assert not [n for n in declared if not hasattr(L, n)]
-    assert ctypes.sizeof(_native.BusConfig) == 8
+    kit.abi_is_declared_exported_and_bound(SPEC)
 
 
 def test_no_cpu_path():
-    import torch
-    import custom_gymnasium_environments_amd as cge
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    with pytest.raises(cge.NativeLibraryError):
-        cge.BusVectorEnv(8)
-    with pytest.raises(cge.NativeLibraryError):
-        cge.BusVectorEnv(8, device="cpu")
+    kit.no_cpu_path(SPEC)
 
 
 @pytest.mark.parametrize("name", ["bus_hash.npz", "bus_short.npz"])

@@ -1,37 +1,26 @@
 """BusVectorEnv on the device against the unmodified reference (tests/golden/bus_*.npz) and, where the fixtures cannot reach, against
-the counts model that tests/test_bus_cpu.py pins to them (tests/bus_model.py).  Every comparison is bit-exact and skips no rows."""
+the counts model that tests/test_bus_cpu.py pins to them (tests/bus_model.py).  The helpers and the bodies shared with world builder
+and restaurant are in tests/_slab_kit.py.  Every comparison is bit-exact and skips no rows."""
+import types
+
 import numpy as np
 import pytest
 import torch
 
+import _slab_kit as kit
 import bus_model as bm
-from conftest import golden
+from _slab_kit import MODES, cge, dev, host, same, take, warm_up  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"NextStep": bm.NEXT_STEP, "SameStep": bm.SAME_STEP, "Disabled": bm.DISABLED}
-OFFSETS = np.cumsum([0] + [int(np.prod(bm.KEY_SHAPES[k])) for k in bm.KEYS])            # plane starts inside a slab, per env
-
-
-@pytest.fixture(scope="module")
-def cge():
-    import custom_gymnasium_environments_amd as m
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    m.native_lib()
-    return m
-
-
-def host(env, obs):
-    """observation dict of device views -> dict of numpy arrays, through ONE copy of the slab behind it"""
-    slab = env.obs_slab(obs).cpu().numpy()
-    n = env.num_envs
-    return {k: slab[..., OFFSETS[j] * n:OFFSETS[j + 1] * n].reshape(slab.shape[:-1] + (n,) + bm.KEY_SHAPES[k]) for j, k in enumerate(bm.KEYS)}
-
-
-def same(dev, ref, what, rows=None):
-    for k in bm.KEYS:
-        a, b = (dev[k], ref[k]) if rows is None else (dev[k][rows], ref[k][rows])
-        assert a.dtype == np.int32 and np.array_equal(a, b), (what, k)
+SPEC = types.SimpleNamespace(
+    m=bm, env="BusVectorEnv", model=bm.BusModel, limit="max_timesteps", from_fixture={"max_timesteps": "max_timesteps"}, flag="truncated",
+    keys=bm.KEYS, shapes=bm.KEY_SHAPES, dtypes=dict.fromkeys(bm.KEYS, np.int32), column=(), exact_reward=True,
+    rollout=types.SimpleNamespace(
+        n=300, limit=150, longest=600, ends=3, info=(),
+        given=lambda *a, **kw: (dev(bm.hash_actions(*a, **kw)) * 7 + 3) % 11,
+        pre=lambda n, env0: bm.hash_actions(1, 40, n, env0=env0)),                        # host arrays
+    sharding=types.SimpleNamespace(n=1000, k=520, kw={}, shards=[(0, 500), (500, 500)], ends=lambda dw: int(dw.min()) == 1))
 
 
 def test_observation_is_a_dict_of_views_of_one_slab(cge):
@@ -39,10 +28,12 @@ def test_observation_is_a_dict_of_views_of_one_slab(cge):
     obs, _ = env.reset(seed=1)
     assert list(obs) == list(bm.KEYS)
     base = obs["bus_stops"].data_ptr()
-    for j, k in enumerate(bm.KEYS):
+    start = 0                                                          # plane starts inside the slab, in ints
+    for k in bm.KEYS:
         t = obs[k]
         assert t.dtype == torch.int32 and t.is_cuda and tuple(t.shape) == (300,) + bm.KEY_SHAPES[k] and t.is_contiguous(), k
-        assert t.data_ptr() == base + 4 * 300 * int(OFFSETS[j]), k
+        assert t.data_ptr() == base + 4 * start, k
+        start += 300 * int(np.prod(bm.KEY_SHAPES[k]))
     assert tuple(env.obs_slab(obs).shape) == (300 * 56,)
     a = env.action_sampler(0).sample()
     assert a.dtype == torch.int32 and tuple(a.shape) == (300, 4) and int(a.min()) >= 0 and int(a.max()) <= 10
@@ -56,118 +47,26 @@ def test_observation_is_a_dict_of_views_of_one_slab(cge):
 
 @pytest.mark.parametrize("name", ["bus_hash.npz", "bus_dwell.npz", "bus_short.npz"])
 def test_fixtures_same_step(cge, name):
-    z = golden(name)
-    n, T = z["reward"].shape
-    env = cge.BusVectorEnv(n, autoreset_mode="SameStep", max_timesteps=int(z["max_timesteps"]))
-    obs, _ = env.reset(seed=int(z["seed0"]))
-    same(host(env, obs), {k: z["obs0_" + k].astype(np.int32) for k in bm.KEYS}, "reset")
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    acts = torch.from_numpy(z["actions"].transpose(1, 0, 2).copy()).cuda()
-    seen = 0
-    for t in range(T):
-        obs, rew, term, trunc, infos = env.step(acts[t])
-        o, f = host(env, obs), host(env, infos["final_obs"])
-        tr = trunc.cpu().numpy()
-        assert np.array_equal(rew.cpu().numpy().astype(np.float64), z["reward"][:, t]), t
-        assert not term.any() and np.array_equal(tr, z["truncated"][:, t].astype(bool)), t
-        assert np.array_equal(infos["_final_obs"].cpu().numpy(), tr)
-        live = ~tr
-        ref = {k: z["obs_" + k][:, t].astype(np.int32) for k in bm.KEYS}
-        same(o, ref, (t, "obs"), live)                                 # the reference's step() returns the terminal observation ...
-        same(f, ref, (t, "final_obs"), tr)                             # ... which SAME_STEP hands over as final_obs
-        for i in np.flatnonzero(tr):
-            j = where[(int(i), t)]
-            seen += 1
-            for k in bm.KEYS:                                          # and `obs` is what reset() then returned on the same stream
-                assert np.array_equal(o[k][i], z["reset_" + k][j]), (t, i, k)
-    assert seen == len(where) > 0
-    env.close()
+    kit.fixtures_same_step(cge, SPEC, name)
 
 
 @pytest.mark.parametrize("shape", [(4096, 1100, 500), (333, 260, 13)], ids=["4096x1100", "limit13"])
 @pytest.mark.parametrize("mode", list(MODES))
 def test_model_parity(cge, mode, shape):
     n, T, limit = shape
-    env0 = 70001
     seeds = (np.arange(n, dtype=np.int64) * 7919 + 12345) % 1000003    # a per-env seed array
-    env = cge.BusVectorEnv(n, autoreset_mode=mode, max_timesteps=limit, env_index0=env0)
-    m = bm.BusModel(seeds, limit, MODES[mode])
-    obs, _ = env.reset(seed=seeds)
-    same(host(env, obs), m.reset(), "reset")
-    acts = bm.hash_actions(5, T, n, env0=env0)
-    dacts = torch.from_numpy(acts).cuda()
-    ends = 0
-    for t in range(T):
-        if mode == "Disabled" and t in (limit + 3, 2 * limit + 7):     # the caller resets: half of the batch, then the other half
-            mask = (np.arange(n) % 2 == (t & 1)).astype(np.uint8)
-            obs, _ = env.reset(options={"reset_mask": mask})
-            same(host(env, obs), m.reset(mask), (t, "masked reset"))
-        obs, rew, term, trunc, infos = env.step(dacts[t])
-        mo, mr, mte, mtr, mf = m.step(acts[t])
-        same(host(env, obs), mo, (t, "obs"))
-        assert np.array_equal(rew.cpu().numpy().astype(np.float64), mr), t
-        tr = trunc.cpu().numpy()
-        assert not term.any() and np.array_equal(tr, mtr), t
-        if mode == "SameStep" and tr.any():
-            same(host(env, infos["final_obs"]), mf, (t, "final_obs"), tr)
-        ends += int(tr.sum())
-    assert ends >= 2 * n
-    assert env.invalid_action_count() == 0
-    env.close()
+    kit.model_parity(cge, SPEC, mode, limit, seeds, bm.hash_actions(5, T, n, env0=70001), (limit + 3, 2 * limit + 7), env0=70001)
 
 
 @pytest.mark.parametrize("k", [1, 20, 600])
 @pytest.mark.parametrize("given", [False, True], ids=["hash", "given"])
 @pytest.mark.parametrize("mode", ["SameStep", "NextStep"])
 def test_rollout_equals_k_steps(cge, mode, given, k):
-    n, env0, a_seed, t0 = 300, 4000, 17, 40
-    acts = torch.from_numpy(bm.hash_actions(a_seed, k, n, t0=t0, env0=env0)).cuda()
-    if given:
-        acts = (acts * 7 + 3) % 11
-    a, b = (cge.BusVectorEnv(n, autoreset_mode=mode, env_index0=env0, max_timesteps=150) for _ in range(2))
-    a.reset(seed=3); b.reset(seed=3)
-    pre = bm.hash_actions(1, 40, n, env0=env0)
-    for t in range(40):                                                # both start mid-episode
-        a.step(pre[t]); b.step(pre[t])
-    traj, rt, tt, rs, dc = a.rollout(k, actions=acts if given else None, action_seed=a_seed, t0=t0, trajectory=True, per_step=True)
-    th = host(a, traj)
-    assert tuple(traj["bus_passenger_destinations"].shape) == (k, n, 4, 4) and tuple(traj["timestep"].shape) == (k, n)
-    rsum, dcount = np.zeros(n, np.float64), np.zeros(n, np.int32)
-    for t in range(k):
-        obs, rew, term, trunc, _ = b.step(acts[t])
-        same({key: v[t] for key, v in th.items()}, host(b, obs), (t, "obs"))
-        assert torch.equal(rt[t], rew) and torch.equal(tt[t], trunc), t
-        rsum += rew.cpu().numpy().astype(np.float64)
-        dcount += trunc.cpu().numpy()
-    assert np.array_equal(rs.cpu().numpy(), rsum) and np.array_equal(dc.cpu().numpy(), dcount)
-    if k == 600:
-        assert dcount.min() >= 3
-    # the states agree as well: one more rollout without a trajectory returns the same last observation from both
-    oa, rsa, dca = a.rollout(7, action_seed=a_seed, t0=t0 + k)
-    ob, rsb, dcb = b.rollout(7, action_seed=a_seed, t0=t0 + k)
-    same(host(a, oa), host(b, ob), "last obs")
-    assert torch.equal(rsa, rsb) and torch.equal(dca, dcb)
-    a.close(); b.close()
+    kit.rollout_equals_k_steps(cge, SPEC, mode, given, k)
 
 
 def test_sharding_invariance(cge):
-    n, half, k = 1000, 500, 520
-    whole = cge.BusVectorEnv(n, autoreset_mode="SameStep")
-    parts = [cge.BusVectorEnv(half, autoreset_mode="SameStep", env_index0=j * half) for j in range(2)]
-    ow, _ = whole.reset(seed=77)
-    ow = host(whole, ow)
-    for j, p in enumerate(parts):
-        op, _ = p.reset(seed=77)
-        same(host(p, op), {key: v[j * half:(j + 1) * half] for key, v in ow.items()}, ("reset", j))
-    tw, rw, cw, sw, dw = whole.rollout(k, action_seed=9, trajectory=True, per_step=True)
-    tw = host(whole, tw)
-    for j, p in enumerate(parts):
-        tp, rp, cp, sp, dp = p.rollout(k, action_seed=9, trajectory=True, per_step=True)
-        s = slice(j * half, (j + 1) * half)
-        same(host(p, tp), {key: v[:, s] for key, v in tw.items()}, ("trajectory", j))
-        assert torch.equal(rp, rw[:, s]) and torch.equal(cp, cw[:, s]) and torch.equal(sp, sw[s]) and torch.equal(dp, dw[s])
-        p.close()
-    whole.close()
+    kit.sharding_invariance(cge, SPEC)
 
 
 def test_episode_statistics(cge):
@@ -251,12 +150,7 @@ def test_captured_steps_replay_and_match_the_model(cge, mode):
     m.reset()
     acts_h = bm.hash_actions(21, K, n)
     acts = torch.from_numpy(acts_h).cuda()
-    side = torch.cuda.Stream()                                         # warm-up on a side stream: the persistent buffers get allocated
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        w = env.step(acts[0])
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
+    w = warm_up(lambda: env.step(acts[0]))                             # on a side stream: the persistent buffers get allocated
     same(host(env, w[0]), m.step(acts_h[0])[0], "warm-up")
     hist = {"obs": torch.empty((K, n * 56), dtype=torch.int32, device="cuda"), "rew": torch.empty((K, n), device="cuda"),
             "trunc": torch.empty((K, n), dtype=torch.bool, device="cuda")}
@@ -268,11 +162,10 @@ def test_captured_steps_replay_and_match_the_model(cge, mode):
     for rep in range(2):                                               # the same graph twice: the state carries over, the actions repeat
         g.replay()
         torch.cuda.synchronize()
-        slabs = hist["obs"].cpu().numpy()
+        got = kit.decode(env, hist["obs"])
         for t in range(K):
             mo, mr, _, mtr, _ = m.step(acts_h[t])
-            dev = {k: slabs[t, OFFSETS[j] * n:OFFSETS[j + 1] * n].reshape((n,) + bm.KEY_SHAPES[k]) for j, k in enumerate(bm.KEYS)}
-            same(dev, mo, (rep, t))
+            same(take(got, t), mo, (rep, t))
             assert np.array_equal(hist["rew"][t].cpu().numpy().astype(np.float64), mr) and np.array_equal(hist["trunc"][t].cpu().numpy(), mtr)
     assert int(hist["trunc"].sum()) > 0                                # in-kernel resets happened inside the graph
     env.close()
@@ -285,7 +178,7 @@ def test_one_million_envs(cge):
     env = cge.BusVectorEnv(n, autoreset_mode="SameStep", reuse_buffers=True)
     m = bm.BusModel(seed + sample, 500, bm.SAME_STEP)
     obs, _ = env.reset(seed=seed)
-    same({k: v[sample] for k, v in host(env, obs).items()}, m.reset(), "reset")
+    same(take(host(env, obs), sample), m.reset(), "reset")
     total = obs["total_waiting"].clone()                               # waiting + onboard + delivered of the running episode
     assert int(total.min()) >= 50 and int(total.max()) <= 150 and int(obs["total_delivered"].max()) == 0
     acts = bm.hash_actions(a_seed, T, 512, envs=sample)
@@ -310,7 +203,7 @@ def test_one_million_envs(cge):
         rsub, tsub = rt[:, sidx].cpu().numpy(), tt[:, sidx].cpu().numpy()
         for j in range(chunk):
             mo, mr, _, mtr, _ = m.step(acts[t0 + j])
-            same({k: v[j] for k, v in sub.items()}, mo, t0 + j)
+            same(take(sub, j), mo, t0 + j)
             assert np.array_equal(rsub[j].astype(np.float64), mr) and np.array_equal(tsub[j], mtr), t0 + j
     assert ends == 1
     env.close()

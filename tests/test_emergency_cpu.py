@@ -21,7 +21,7 @@ FIXTURES = OLD_FIXTURES + ["emergency_day.npz"]
 SPEC = types.SimpleNamespace(
     m=em, kind="emergency", env="EmergencyVectorEnv", model=em.EmergencyModel, model_kw={}, limit="max_timesteps", actions=50,
     fixtures=FIXTURES, poked=None, recorded=276, info_keys=list(em.INFO),         # the six values, termination_reason as its code
-    config=("EmergencyConfig", 8, ["autoreset_mode", "max_timesteps"]))
+    config=("EmergencyConfig", 8, ["autoreset_mode", "max_timesteps"]), abi=kit.ABI)
 
 
 @pytest.mark.parametrize("name", FIXTURES)

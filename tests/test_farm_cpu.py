@@ -25,7 +25,7 @@ SPEC = types.SimpleNamespace(
     m=fm, kind="farm", env="AgriculturalFarmVectorEnv", model=fm.FarmModel, model_kw=dict(width=fm.LIVE), limit="max_years", actions=45,
     fixtures=FIXTURES, poked="farm_poked.npz", recorded=fm.LIVE,
     info_keys=list(fm.INFO) + [f"{k}_{f}" for k in fm.FIELD_INFO for f in range(4)],      # the eleven values and field_status
-    config=("FarmConfig", 16, ["autoreset_mode", "max_years", "compact_obs", "reserved"]), mangled="3cge4farm")
+    config=("FarmConfig", 16, ["autoreset_mode", "max_years", "compact_obs", "reserved"]), abi=kit.ABI, mangled="3cge4farm")
 HOST_CHECK = kit.host_check(SPEC)
 
 

@@ -86,9 +86,9 @@ def _model(name, cls, model, kw, steps, seed, pad, t0=0):
 
 
 for _h in (Hashed("bus"), Hashed("restaurant")):                          # limit 5: the hashed cases of test_slab_final_rows_gpu.py
-    _model({"bus": "Bus", "restaurant": "Restaurant"}[_h.type], _h.cls, _h.model, _h.kw, 5 + 3, 3, {"bus": 4, "restaurant": 1}[_h.type])
+    _model({"bus": "Bus", "restaurant": "Restaurant"}[_h.type], _h.spec.env, _h.spec.m, _h.kw, 5 + 3, 3, {"bus": 4, "restaurant": 1}[_h.type])
 for _h in (Hashed("wb-3-dict"), Hashed("wb-3-flat")):                     # no time limit: the 24 steps from t0 = 5 in which every env ends
-    _model("WorldBuilder-" + _h.kind.split("-")[2], _h.cls, _h.model, _h.kw, WB_K, 3, 1 if _h.flat else 16, t0=T0)
+    _model("WorldBuilder-" + _h.kind.split("-")[2], _h.spec.env, _h.spec.m, _h.kw, WB_K, 3, 1 if _h.flat else 16, t0=T0)
 for _s, _label in ((AIRLINE, "Airline"), (EMERGENCY, "Emergency"), (STATION, "SpaceStation")):
     _T, _seed, _limit, _ = _s.kernel                                      # the kit's kernel_equals_the_model: every env ends within T (airline: no limit keyword)
     _model(_label, _s.env, _s.m, {_s.limit: _limit} if _s.limit else {}, _T if _limit is None else _limit + 3, _seed, 4)

@@ -1,22 +1,21 @@
 """CPU-side checks of the restaurant env: the counts-and-lists model (tests/restaurant_model.py) reproduces, value for value and bit for
 bit, what the unmodified reference recorded (tests/golden/restaurant_*.npz, written by tests/golden/gen/gen_restaurant.py); the C ABI is
 declared, exported and bound; there is no CPU path; the spaces are the reference's."""
-import ctypes
 import json
 import os
-import re
 import subprocess
 import sys
+import types
 
 import numpy as np
 import pytest
 
+import _lane_kit as kit
 import restaurant_model as rm
 from conftest import ROOT, golden
 
 FIXTURES = ["restaurant_hash.npz", "restaurant_busy.npz", "restaurant_short.npz", "restaurant_short40.npz", "restaurant_long.npz"]
-ABI = ["create", "destroy", "seed", "reset", "step", "rollout", "info", "error_count", "episode_stats", "snapshot_bytes", "snapshot_get",
-       "snapshot_set", "device_bytes", "last_error", "last_kernel"]
+SPEC = types.SimpleNamespace(kind="restaurant", env="RestaurantVectorEnv", config=("RestaurantConfig", 8, None), abi=kit.ABI)
 
 
 def bits(x):
@@ -114,27 +113,11 @@ def test_kernel_dynamics_replay_the_fixtures_on_the_host():
 
 
 def test_abi_is_declared_exported_and_bound():
-    from custom_gymnasium_environments_amd import _native, build
-    src = open(os.path.join(ROOT, "include", "cge_amd.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(cge_restaurant_[a-z0-9_]+)\s*\(", src))
-    assert declared == {f"cge_restaurant_{fn}" for fn in ABI}
-    assert {n for n in _native.SIGNATURES if n.startswith("cge_restaurant_")} == declared
-    build.build_native()
-    L = ctypes.CDLL(_native.LIB_PATH)
-    assert not [n for n in declared if not hasattr(L, n)]
-    assert ctypes.sizeof(_native.RestaurantConfig) == 8
+    kit.abi_is_declared_exported_and_bound(SPEC)
 
 
 def test_no_cpu_path():
-    import torch
-    import custom_gymnasium_environments_amd as cge
-    if torch.cuda.is_available():
-        pytest.skip("GPU present")
-    with pytest.raises(cge.NativeLibraryError):
-        cge.RestaurantVectorEnv(8)
-    with pytest.raises(cge.NativeLibraryError):
-        cge.RestaurantVectorEnv(8, device="cpu")
+    kit.no_cpu_path(SPEC)
 
 
 @pytest.mark.parametrize("name", ["restaurant_hash.npz", "restaurant_long.npz"])

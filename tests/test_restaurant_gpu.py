@@ -1,51 +1,31 @@
 """RestaurantVectorEnv on the device against the unmodified reference (tests/golden/restaurant_*.npz) and, where the fixtures cannot
-reach, against the model that tests/test_restaurant_cpu.py pins to them (tests/restaurant_model.py).  Every comparison is array_equal
-and skips no rows; rewards are the reference's float64 sums rounded to the float32 of the output buffer."""
+reach, against the model that tests/test_restaurant_cpu.py pins to them (tests/restaurant_model.py).  The helpers and the bodies shared
+with bus and world builder are in tests/_slab_kit.py.  Every comparison is array_equal and skips no rows; rewards are the reference's
+float64 sums rounded to the float32 of the output buffer."""
 import json
+import types
 
 import numpy as np
 import pytest
 import torch
 
+import _slab_kit as kit
 import restaurant_model as rm
+from _slab_kit import MODES, cge, f32, host, same, take, warm_up  # noqa: F401
+from _slab_kit import dev as packed
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"NextStep": rm.NEXT_STEP, "SameStep": rm.SAME_STEP, "Disabled": rm.DISABLED}
-OFFSETS = np.cumsum([0] + [int(np.prod(rm.KEY_SHAPES[k])) for k in rm.KEYS])            # plane starts inside a slab, per env
 FIXTURES = ["restaurant_hash.npz", "restaurant_busy.npz", "restaurant_short.npz", "restaurant_short40.npz", "restaurant_long.npz"]
-
-
-@pytest.fixture(scope="module")
-def cge():
-    import custom_gymnasium_environments_amd as m
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    m.native_lib()
-    return m
-
-
-def split(slab, n):
-    return {k: slab[..., OFFSETS[j] * n:OFFSETS[j + 1] * n].reshape(slab.shape[:-1] + (n,) + rm.KEY_SHAPES[k]) for j, k in enumerate(rm.KEYS)}
-
-
-def host(env, obs):
-    """observation dict of device views -> dict of numpy arrays, through ONE copy of the slab behind it"""
-    return split(env.obs_slab(obs).cpu().numpy(), env.num_envs)
-
-
-def same(dev, ref, what, rows=None):
-    for k in rm.KEYS:
-        a, b = (dev[k], ref[k]) if rows is None else (dev[k][rows], ref[k][rows])
-        assert a.dtype == np.int32 and np.array_equal(a, b), (what, k)
-
-
-def f32(x):
-    return np.asarray(x, np.float64).astype(np.float32)
-
-
-def packed(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
+SPEC = types.SimpleNamespace(
+    m=rm, env="RestaurantVectorEnv", model=rm.RestaurantModel, limit="max_episode_steps", from_fixture={"max_episode_steps": "max_episode_steps"},
+    flag="truncated", keys=rm.KEYS, shapes=rm.KEY_SHAPES, dtypes=dict.fromkeys(rm.KEYS, np.int32), column=(), exact_reward=False,
+    rollout=types.SimpleNamespace(
+        n=200, limit=90, longest=125, ends=1, info=("total_reward", "wait_time_sum", "num_customers"),
+        given=lambda *a, **kw: packed(rm.busy_actions(*a, **kw)),
+        pre=lambda n, env0: packed(rm.busy_actions(1, 40, n, env0=env0))),
+    sharding=types.SimpleNamespace(n=333, k=130, kw={"max_episode_steps": 100}, shards=[(0, 167), (167, 166)], ends=lambda dw: int(dw.min()) == 1))
 
 
 def test_observation_is_a_dict_of_views_of_one_slab(cge):
@@ -53,10 +33,12 @@ def test_observation_is_a_dict_of_views_of_one_slab(cge):
     obs, _ = env.reset(seed=1)
     assert list(obs) == list(rm.KEYS)
     base = obs["waiting_customers"].data_ptr()
-    for j, k in enumerate(rm.KEYS):
+    start = 0                                                             # plane starts inside the slab, in ints
+    for k in rm.KEYS:
         t = obs[k]
         assert t.dtype == torch.int32 and t.is_cuda and tuple(t.shape) == (300,) + rm.KEY_SHAPES[k] and t.is_contiguous(), k
-        assert t.data_ptr() == base + 4 * 300 * int(OFFSETS[j]), k
+        assert t.data_ptr() == base + 4 * start, k
+        start += 300 * int(np.prod(rm.KEY_SHAPES[k]))
         assert not t.any(), k                                             # an empty restaurant
     assert tuple(env.obs_slab(obs).shape) == (300 * 341,)
     assert sorted(env.single_action_space.spaces) == sorted(rm.ACTION_KEYS)
@@ -82,60 +64,15 @@ def test_observation_is_a_dict_of_views_of_one_slab(cge):
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_fixtures_same_step(cge, name):
-    z = golden(name)
-    n, T = z["reward"].shape
-    env = cge.RestaurantVectorEnv(n, autoreset_mode="SameStep", max_episode_steps=int(z["max_episode_steps"]))
-    obs, _ = env.reset(seed=int(z["seed0"]))
-    same(host(env, obs), {k: z["obs0_" + k].astype(np.int32) for k in rm.KEYS}, "reset")
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
-    acts = packed(z["actions"].transpose(1, 0, 2))
-    seen = 0
-    for t in range(T):
-        obs, rew, term, trunc, infos = env.step(acts[t])
-        o = host(env, obs)
-        tr = trunc.cpu().numpy()
-        assert np.array_equal(rew.cpu().numpy(), f32(z["reward"][:, t])), t
-        assert not term.any() and np.array_equal(tr, z["truncated"][:, t].astype(bool)), t
-        assert np.array_equal(infos["_final_obs"].cpu().numpy(), tr)
-        ref = {k: z["obs_" + k][:, t].astype(np.int32) for k in rm.KEYS}
-        same(o, ref, (t, "obs"), ~tr)                                     # the reference's step() returns the terminal observation ...
-        if tr.any():
-            same(host(env, infos["final_obs"]), ref, (t, "final_obs"), tr)   # ... which SAME_STEP hands over as final_obs
-        for i in np.flatnonzero(tr):
-            j = where[(int(i), t)]
-            seen += 1
-            for k in rm.KEYS:                                             # and `obs` is what reset() then returned on the same stream
-                assert np.array_equal(o[k][i], z["reset_" + k][j]), (t, i, k)
-    assert seen == len(where) > 0 and env.invalid_action_count() == 0
-    env.close()
+    kit.fixtures_same_step(cge, SPEC, name)
 
 
 @pytest.mark.parametrize("name", ["restaurant_short.npz", "restaurant_short40.npz"])
 @pytest.mark.parametrize("mode", ["NextStep", "Disabled"])
 def test_short_fixture_in_the_other_modes(cge, mode, name):
     z = golden(name)
-    n, T = z["reward"].shape
-    limit = int(z["max_episode_steps"])
-    env = cge.RestaurantVectorEnv(n, autoreset_mode=mode, max_episode_steps=limit)
-    m = rm.RestaurantModel(int(z["seed0"]) + np.arange(n), limit, MODES[mode])
-    obs, _ = env.reset(seed=int(z["seed0"]))
-    same(host(env, obs), m.reset(), "reset")
-    acts = z["actions"].transpose(1, 0, 2).astype(np.int32)
-    dacts = packed(acts)
-    ends = 0
-    for t in range(T):
-        if mode == "Disabled" and t in (limit + 3, 3 * limit + 1):        # the caller resets: half of the batch, then the other half
-            mask = (np.arange(n) % 2 == (t & 1)).astype(np.uint8)
-            obs, _ = env.reset(options={"reset_mask": mask})
-            same(host(env, obs), m.reset(mask), (t, "masked reset"))
-        obs, rew, term, trunc, _ = env.step(dacts[t])
-        mo, mr, _, mtr, _ = m.step(acts[t])
-        same(host(env, obs), mo, (t, "obs"))
-        assert np.array_equal(rew.cpu().numpy(), f32(mr)) and not term.any() and np.array_equal(trunc.cpu().numpy(), mtr), t
-        ends += int(mtr.sum())
-    assert ends >= 2 * n
-    assert np.array_equal(env.info("needs_reset").cpu().numpy(), m.needs_reset().astype(np.float64))
-    env.close()
+    limit, seed, acts = int(z["max_episode_steps"]), int(z["seed0"]), z["actions"].transpose(1, 0, 2).astype(np.int32)
+    kit.model_parity(cge, SPEC, mode, limit, seed + np.arange(len(acts[0])), acts, (limit + 3, 3 * limit + 1), seed=seed)
 
 
 def test_info_parity_at_every_step(cge):
@@ -199,37 +136,7 @@ def test_kernel_against_the_model(cge, n):
 @pytest.mark.parametrize("given", [False, True], ids=["hash", "given"])
 @pytest.mark.parametrize("mode", ["SameStep", "NextStep"])
 def test_rollout_equals_k_steps(cge, mode, given, k):
-    n, env0, a_seed, t0 = 200, 4000, 17, 40
-    if given:
-        acts = packed(rm.busy_actions(a_seed, k, n, t0=t0, env0=env0))
-    else:
-        acts = packed(rm.hash_actions(a_seed, k, n, t0=t0, env0=env0))
-    a, b = (cge.RestaurantVectorEnv(n, autoreset_mode=mode, env_index0=env0, max_episode_steps=90) for _ in range(2))
-    a.reset(seed=3); b.reset(seed=3)
-    pre = packed(rm.busy_actions(1, 40, n, env0=env0))
-    for t in range(40):                                                   # both start mid-episode
-        a.step(pre[t]); b.step(pre[t])
-    traj, rt, tt, rs, dc = a.rollout(k, actions=acts if given else None, action_seed=a_seed, t0=t0, trajectory=True, per_step=True)
-    th = host(a, traj)
-    assert tuple(traj["waiting_customers"].shape) == (k, n, 50, 2) and tuple(traj["current_timestep"].shape) == (k, n, 1)
-    rsum, dcount = np.zeros(n, np.float64), np.zeros(n, np.int32)
-    for t in range(k):
-        obs, rew, term, trunc, _ = b.step(acts[t])
-        same({key: v[t] for key, v in th.items()}, host(b, obs), (t, "obs"))
-        assert torch.equal(rt[t], rew) and torch.equal(tt[t], trunc), t
-        rsum += rew.cpu().numpy().astype(np.float64)
-        dcount += trunc.cpu().numpy()
-    assert np.array_equal(rs.cpu().numpy(), rsum) and np.array_equal(dc.cpu().numpy(), dcount)
-    if k == 125:
-        assert dcount.min() >= 1
-    # the states agree as well: one more rollout without a trajectory returns the same last observation from both
-    oa, rsa, dca = a.rollout(7, action_seed=a_seed, t0=t0 + k)
-    ob, rsb, dcb = b.rollout(7, action_seed=a_seed, t0=t0 + k)
-    same(host(a, oa), host(b, ob), "last obs")
-    assert torch.equal(rsa, rsb) and torch.equal(dca, dcb)
-    for f in ("total_reward", "wait_time_sum", "num_customers"):
-        assert torch.equal(a.info(f), b.info(f)), f
-    a.close(); b.close()
+    kit.rollout_equals_k_steps(cge, SPEC, mode, given, k)
 
 
 def test_rollout_replays_the_busy_fixture(cge):
@@ -238,6 +145,7 @@ def test_rollout_replays_the_busy_fixture(cge):
     env = cge.RestaurantVectorEnv(n, autoreset_mode="SameStep")
     env.reset(seed=int(z["seed0"]))
     acts = packed(z["actions"].transpose(1, 0, 2))
+    recorded = kit.pieces(SPEC, z, "obs_")
     t0 = 0
     for k in (125, 125, 125, 125, 20):
         traj, rt, tt, rs, dc = env.rollout(k, actions=acts[t0:t0 + k], trajectory=True, per_step=True)
@@ -245,8 +153,8 @@ def test_rollout_replays_the_busy_fixture(cge):
         tr = tt.cpu().numpy()
         assert np.array_equal(rt.cpu().numpy(), f32(z["reward"][:, t0:t0 + k].T)) and np.array_equal(tr, z["truncated"][:, t0:t0 + k].T.astype(bool))
         for j in range(k):
-            ref = {key: z["obs_" + key][:, t0 + j].astype(np.int32) for key in rm.KEYS}
-            same({key: v[j] for key, v in th.items()}, ref, t0 + j, ~tr[j])
+            ref = take(recorded, slice(None), t0 + j)
+            same(take(th, j), ref, t0 + j, ~tr[j])
             if tr[j].any():                                               # the slot of a truncated step holds the reset observation
                 assert t0 + j == 499 and tr[j].all() and not th["waiting_customers"][j].any() and not th["current_timestep"][j].any()
         t0 += k
@@ -380,39 +288,13 @@ def test_episode_statistics(cge, mode):
 
 
 def test_sharding_invariance(cge):
-    n, k = 333, 130
-    whole = cge.RestaurantVectorEnv(n, autoreset_mode="SameStep", max_episode_steps=100)
-    parts = [cge.make_sharded(cge.RestaurantVectorEnv, n, rank=j, world_size=2, local_rank=0, autoreset_mode="SameStep", max_episode_steps=100)
-             for j in range(2)]
-    assert [p.shard for p in parts] == [(0, 167), (167, 166)]
-    whole.reset(seed=77)
-    tw, rw, cw, sw, dw = whole.rollout(k, action_seed=9, trajectory=True, per_step=True)
-    tw = host(whole, tw)
-    for p in parts:
-        s = slice(p.shard[0], p.shard[0] + p.shard[1])
-        p.reset(seed=77)
-        tp, rp, cp, sp, dp = p.rollout(k, action_seed=9, trajectory=True, per_step=True)
-        same(host(p, tp), {key: v[:, s] for key, v in tw.items()}, ("trajectory", p.shard))
-        assert torch.equal(rp, rw[:, s]) and torch.equal(cp, cw[:, s]) and torch.equal(sp, sw[s]) and torch.equal(dp, dw[s])
-        p.close()
-    assert int(dw.min()) == 1
-    whole.close()
+    kit.sharding_invariance(cge, SPEC)
 
 
 # ---------------------------------------------------------------------------------------------------------------- graph capture
 # the method of tests/test_graph_capture_gpu.py: reuse_buffers=True, a warm-up on a side stream, the calls captured into one
 # torch.cuda.CUDAGraph, replayed four times, every output compared with an eager twin that makes the same calls one by one
 REPLAYS = 4
-
-
-def _warm_up(fn):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        out = fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    return out
 
 
 @pytest.mark.parametrize("mode", ["SameStep", "NextStep"])
@@ -422,7 +304,7 @@ def test_captured_steps_replay_and_match_an_eager_twin(cge, mode):
     twin = cge.RestaurantVectorEnv(n, autoreset_mode=mode, max_episode_steps=limit)
     env.reset(seed=9); twin.reset(seed=9)
     acts = packed(rm.busy_actions(21, K, n))
-    w = _warm_up(lambda: env.step(acts[0]))
+    w = warm_up(lambda: env.step(acts[0]))
     t0 = twin.step(acts[0])
     assert torch.equal(env.obs_slab(w[0]), twin.obs_slab(t0[0])) and torch.equal(w[1], t0[1])
     hist = {"obs": torch.empty((K, n * 341), dtype=torch.int32, device="cuda"), "rew": torch.empty((K, n), device="cuda"),
@@ -455,7 +337,7 @@ def test_captured_rollout_replays_and_matches_an_eager_twin(cge, mode):
         traj, rt, tt, rs, dc = e.rollout(k, action_seed=77, t0=1000, trajectory=True, per_step=True)
         return [e.obs_slab(traj), rt, tt, rs, dc]
 
-    w = _warm_up(lambda: call(env))
+    w = warm_up(lambda: call(env))
     for x, y in zip(w, call(twin)):
         assert torch.equal(x, y)
     hist = [torch.empty_like(x) for x in w]
@@ -527,6 +409,6 @@ def test_one_million_envs(cge):
     rsub = rt[:, sidx].cpu().numpy()
     for j in range(T):
         mo, mr, _, mtr, _ = m.step(acts[j])
-        same({k: v[j] for k, v in sub.items()}, mo, j)
+        same(take(sub, j), mo, j)
         assert np.array_equal(rsub[j], f32(mr)) and not mtr.any(), j
     env.close()

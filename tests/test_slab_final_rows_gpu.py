@@ -6,75 +6,29 @@ observation as before.
 
 Every case runs 64 * 2 + 37 = 165 envs: two full waves and a ragged one.  The fixture cases tile a fixture (env i replays fixture env
 i % m: its seed, its actions) and compute what they expect from the fixture alone; the hashed cases compare with a twin stepped by
-step(), and world builder's with tests/world_builder_model.py as well.  A flat world-builder observation is handled as a dict with
-the one key "flat"."""
+step(), and world builder's with tests/world_builder_model.py as well.  The helpers are those of tests/_slab_kit.py (a flat world-builder
+observation is a dict with the one key "flat"), and what a type is made of comes from the SPEC of its own test file."""
 import numpy as np
 import pytest
 import torch
 
-import bus_model as bm
-import restaurant_model as rm
 import world_builder_model as wm
 from _guard_bands import GUARD, register_guarded
+from _slab_kit import as_dict, cge, fixture_kw, pieces, same, take, warm_up  # noqa: F401
 from conftest import golden
 from custom_gymnasium_environments_amd._slab import plane_views
+from test_bus_gpu import SPEC as BUS
+from test_restaurant_gpu import SPEC as RESTAURANT
+from test_world_builder_gpu import SPEC as WB
 
 pytestmark = pytest.mark.gpu
 
 N, SEG = 64 * 2 + 37, 64
 NSEG = -(-N // SEG)
-WB_DTYPES = {"grid": torch.int8, "resources": torch.float32, "population_capacity": torch.float32, "win_steps": torch.int32}
 
-
-@pytest.fixture(scope="module")
-def cge():
-    import custom_gymnasium_environments_amd as m
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    m.native_lib()
-    return m
-
-
-def as_dict(x):
-    return x if isinstance(x, dict) else {"flat": x}
-
-
-def host(x):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in as_dict(x).items()}
-
-
-def same(dev, ref, what):
-    dev, ref = host(dev), host(ref)
-    assert list(dev) == list(ref), what
-    for k in ref:
-        assert dev[k].dtype == ref[k].dtype and dev[k].shape == ref[k].shape, (what, k, dev[k].dtype, dev[k].shape, ref[k].dtype, ref[k].shape)
-        assert np.array_equal(dev[k].view(np.uint8), np.ascontiguousarray(ref[k]).view(np.uint8)), (what, k)
-
-
-def take(x, *idx):
-    return {k: v[idx] for k, v in as_dict(x).items()}
-
-
-def wb_pieces(z, prefix, flat):
-    """a world-builder fixture's recorded observation pieces in the reference's dtypes and shapes (as tests/test_world_builder_gpu.py)"""
-    if flat:
-        return {"flat": z[prefix + "flat"]}
-    return {"grid": z[prefix + "grid"], "resources": z[prefix + "resources"].astype(np.float32),
-            "population_capacity": z[prefix + "population_capacity"][..., None].astype(np.float32),
-            "win_steps": z[prefix + "win_steps"][..., None].astype(np.int32)}
-
-
-def int_pieces(keys):
-    return lambda z, prefix, flat: {k: z[prefix + k].astype(np.int32) for k in keys}
-
-
-# case -> (env class, fixture, the fixture's flag, constructor arguments read from the fixture, its pieces, steps replayed)
-CASES = {
-    "bus_short": ("BusVectorEnv", "bus_short.npz", "truncated", {"max_timesteps": "max_timesteps"}, int_pieces(bm.KEYS), None),
-    "restaurant_short": ("RestaurantVectorEnv", "restaurant_short.npz", "truncated", {"max_episode_steps": "max_episode_steps"}, int_pieces(rm.KEYS), None),
-    "wb_g2": ("WorldBuilderVectorEnv", "wb_g2.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, None),
-    "wb_builder": ("WorldBuilderVectorEnv", "wb_builder.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, 160),
-    "wb_flat": ("WorldBuilderVectorEnv", "wb_flat.npz", "terminated", {"grid_size": "grid_size", "flatten_obs": "flatten_obs"}, wb_pieces, None),
-}
+# case -> (the type's SPEC, fixture, steps replayed)
+CASES = {"bus_short": (BUS, "bus_short.npz", None), "restaurant_short": (RESTAURANT, "restaurant_short.npz", None),
+         "wb_g2": (WB, "wb_g2.npz", None), "wb_builder": (WB, "wb_builder.npz", 160), "wb_flat": (WB, "wb_flat.npz", None)}
 
 
 class Tiled:
@@ -82,18 +36,19 @@ class Tiled:
 
     def __init__(self, case):
         self.case = case
-        self.cls, name, flag, from_fixture, pieces, steps = CASES[case]
+        self.spec, name, steps = CASES[case]
+        spec, flag = self.spec, self.spec.flag
         z = golden(name)
         self.m = z["reward"].shape[0]
         self.T = T = z["reward"].shape[1] if steps is None else steps
-        self.kw = {k: (bool(z[v]) if z[v].dtype == bool else int(z[v])) for k, v in from_fixture.items()}
+        self.kw = fixture_kw(spec, z)
         flat = bool(self.kw.get("flatten_obs"))
         self.src = np.arange(N) % self.m                                  # env i replays fixture env src[i]
         self.seeds = int(z["seed0"]) + self.src
         self.actions = np.ascontiguousarray(np.moveaxis(z["actions"][:, :T], 0, 1)[:, self.src], dtype=np.int32)   # [T, N(, 4)]
         self.term = z[flag][:, :T].T[:, self.src].astype(bool)            # [T, N]
-        final = {k: v[:, :T] for k, v in pieces(z, "obs_", flat).items()}   # [m, T, ...]: what the reference's step() returned
-        resets = pieces(z, "reset_", flat)
+        final = {k: v[:, :T] for k, v in pieces(spec, z, "obs_", flat).items()}   # [m, T, ...]: what the reference's step() returned
+        resets = pieces(spec, z, "reset_", flat)
         traj = {k: v.copy() for k, v in final.items()}                    # slot t: the recorded observation, or the reset one at an end
         ends = 0
         for j, (i, t) in enumerate(z["reset_index"]):
@@ -107,7 +62,7 @@ class Tiled:
         self.traj = {k: np.moveaxis(v, 0, 1)[:, self.src] for k, v in traj.items()}
 
     def make(self, cge, mode="SameStep"):
-        env = getattr(cge, self.cls)(N, autoreset_mode=mode, **self.kw)
+        env = getattr(cge, self.spec.env)(N, autoreset_mode=mode, **self.kw)
         env.reset(seed=self.seeds)
         return env
 
@@ -153,17 +108,16 @@ class Hashed:
         if self.type == "wb":
             _, g, layout = kind.split("-")
             self.G, self.flat = int(g), layout == "flat"
-            self.cls, self.kw, self.k, self.model = "WorldBuilderVectorEnv", {"grid_size": self.G, "flatten_obs": self.flat}, WB_K, wm
-        elif self.type == "bus":
-            self.cls, self.kw, self.k, self.model = "BusVectorEnv", {"max_timesteps": 5}, 13, bm
+            self.spec, self.kw, self.k = WB, {"grid_size": self.G, "flatten_obs": self.flat}, WB_K
         else:
-            self.cls, self.kw, self.k, self.model = "RestaurantVectorEnv", {"max_episode_steps": 5}, 13, rm
+            self.spec = BUS if self.type == "bus" else RESTAURANT
+            self.kw, self.k = {self.spec.limit: 5}, 13
 
     def actions(self, k, t0=T0, a_seed=A_SEED):
-        return torch.from_numpy(np.ascontiguousarray(self.model.hash_actions(a_seed, k, N, t0=t0, env0=ENV0), dtype=np.int32)).cuda()
+        return torch.from_numpy(np.ascontiguousarray(self.spec.m.hash_actions(a_seed, k, N, t0=t0, env0=ENV0), dtype=np.int32)).cuda()
 
     def make(self, cge, mode="SameStep", **kw):
-        env = getattr(cge, self.cls)(N, autoreset_mode=mode, env_index0=ENV0, **self.kw, **kw)
+        env = getattr(cge, self.spec.env)(N, autoreset_mode=mode, env_index0=ENV0, **self.kw, **kw)
         env.reset(seed=3)
         if self.type != "wb":                                             # stagger the episodes: the ends fall on different steps for different lanes
             pre = self.actions(3, t0=0, a_seed=2)
@@ -259,13 +213,13 @@ def test_hashed_rollout_with_rows_equals_k_step_calls(cge, wb_model_run, kind):
         want = {k: np.stack([final[a][k][b] for a, b in zip(t, i)]) for k in wm.KEYS}
         same(rows, {"flat": wm.flatten(want)} if h.flat else want, (kind, "model"))
         if not h.flat:
-            assert list(rows) == list(wm.KEYS) and all(rows[k].dtype == WB_DTYPES[k] for k in rows)
+            assert list(rows) == list(wm.KEYS) and all(str(rows[k].dtype) == "torch." + np.dtype(WB.dtypes[k]).name for k in rows)
             assert tuple(rows["grid"].shape[1:]) == (h.G, h.G) and tuple(rows["resources"].shape[1:]) == (4,) and tuple(rows["win_steps"].shape[1:]) == (1,)
     else:
         full = flags[:, :2 * SEG].reshape(h.k, 2, SEG)
         assert not full.all(2).any(), "no step ends all lanes of a full wave"
         assert flags.any(0).all() and flags.any(1).sum() >= 4, "every env ends at least once, on different steps"
-        keys = bm.KEY_SHAPES if h.type == "bus" else rm.KEY_SHAPES
+        keys = h.spec.shapes
         assert all(rows[k].dtype == torch.int32 and tuple(rows[k].shape[1:]) == tuple(keys[k]) for k in keys) and list(rows) == list(keys)
     env.close(); twin.close()
 
@@ -398,12 +352,7 @@ def test_captured_rows_rollout_replays(cge):
         out = e.rollout(k, action_seed=A_SEED, t0=T0 + c * k, trajectory=True, per_step=True)
         return [out[1], out[2], e._fin[0], e._fin[1], e._fin[2], *out[0].values()]       # per key: the padding between planes is nobody's
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        w = call(env, 0)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
+    w = warm_up(lambda: call(env, 0))
     call(twin, 0)
     hist = [[torch.empty_like(x) for x in w] for _ in range(calls)]
     for c in range(1, calls):

@@ -24,7 +24,7 @@ FIXTURES = OLD_FIXTURES + ["station_poked.npz"]
 SPEC = types.SimpleNamespace(
     m=sm, kind="space_station", env="SpaceStationVectorEnv", model=sm.SpaceStationModel, model_kw={}, limit="max_steps", actions=40,
     fixtures=FIXTURES, poked="station_poked.npz", recorded=120, info_keys=list(sm.INFO) + ["system_failure_mask"],   # the nine values and the failure mask
-    config=("SpaceStationConfig", 8, ["autoreset_mode", "max_steps"]), mangled="3cge7station")
+    config=("SpaceStationConfig", 8, ["autoreset_mode", "max_steps"]), abi=kit.ABI, mangled="3cge7station")
 HOST_CHECK = kit.host_check(SPEC)
 
 

@@ -1,70 +1,38 @@
 """WorldBuilderVectorEnv on the device against the unmodified reference (tests/golden/wb_*.npz) and, where the fixtures cannot reach,
-against the NumPy model that tests/test_world_builder_cpu.py pins to them (tests/world_builder_model.py).  Every comparison is
-bit-exact, in both observation layouts."""
+against the NumPy model that tests/test_world_builder_cpu.py pins to them (tests/world_builder_model.py).  The helpers and the sharding
+body shared with bus and restaurant are in tests/_slab_kit.py; a flat observation is handled as a dict with the one key "flat".  Every
+comparison is bit-exact, in both observation layouts."""
 import functools
+import types
 
 import numpy as np
 import pytest
 import torch
 
+import _slab_kit as kit
 import world_builder_model as wm
+from _slab_kit import MODES, cge, host, same, take, warm_up, where_reset  # noqa: F401
 from conftest import golden
 from test_world_builder_cpu import checkpoint_records
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"NextStep": wm.NEXT_STEP, "SameStep": wm.SAME_STEP, "Disabled": wm.DISABLED}
 FIXTURES = ["wb_hash.npz", "wb_builder.npz", "wb_fill.npz", "wb_g7.npz", "wb_g3.npz", "wb_g2.npz", "wb_flat.npz"]
-DTYPES = {"grid": np.int8, "resources": np.float32, "population_capacity": np.float32, "win_steps": np.int32}
+SPEC = types.SimpleNamespace(
+    m=wm, env="WorldBuilderVectorEnv", model=wm.WorldBuilderModel, limit=None, from_fixture={"grid_size": "grid_size", "flatten_obs": "flatten_obs"},
+    flag="terminated", keys=wm.KEYS, shapes=None, column=("population_capacity", "win_steps"),
+    dtypes={"grid": np.int8, "resources": np.float32, "population_capacity": np.float32, "win_steps": np.int32},
+    sharding=types.SimpleNamespace(n=357, k=100, kw={}, shards=[(0, 179), (179, 178)], ends=lambda dw: int(dw.sum()) > 0))
 INFO_KEYS = ("steps", "win_steps", "reached_win_population", "food", "wood", "stone", "population", "population_capacity", "farm",
              "lumberyard", "quarry", "house")
 
 
-@pytest.fixture(scope="module")
-def cge():
-    import custom_gymnasium_environments_amd as m
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    m.native_lib()
-    return m
-
-
-def host(env, obs):
-    """device observation -> numpy: the dict of typed arrays through ONE copy of the slab behind it, or the flat rows"""
-    if env.flatten_obs:
-        return obs.cpu().numpy()
-    from custom_gymnasium_environments_amd import world_builder as wb
-    slab = env.obs_slab(obs).cpu().numpy()
-    n, out = env.num_envs, {}
-    for key, shape, dtype in wb.planes(env.grid_size):
-        o, w = env._offsets[key], n * int(np.prod(shape)) * np.dtype(dtype).itemsize
-        out[key] = np.ascontiguousarray(slab[..., o:o + w]).view(dtype).reshape(slab.shape[:-1] + (n,) + shape)
-    return out
-
-
-def pieces(z, prefix, idx=slice(None)):
-    """a fixture's recorded observation pieces [idx] as the reference returned them (dtypes and shapes of _get_observation)"""
-    return {"grid": z[prefix + "grid"][idx], "resources": z[prefix + "resources"][idx].astype(np.float32),
-            "population_capacity": z[prefix + "population_capacity"][idx][..., None].astype(np.float32),
-            "win_steps": z[prefix + "win_steps"][idx][..., None].astype(np.int32)}
-
-
 def layout(ref, flat):
-    return wm.flatten(ref) if flat else ref
+    return {"flat": wm.flatten(ref)} if flat else ref
 
 
-def take(x, rows):
-    return {k: v[rows] for k, v in x.items()} if isinstance(x, dict) else x[rows]
-
-
-def same(dev, ref, what, rows=None):
-    if rows is not None:
-        dev, ref = take(dev, rows), take(ref, rows)
-    if isinstance(ref, dict):
-        assert list(dev) == list(wm.KEYS)
-        for k in wm.KEYS:
-            assert dev[k].dtype == DTYPES[k] and dev[k].shape == ref[k].shape and np.array_equal(dev[k], ref[k]), (what, k)
-    else:
-        assert dev.dtype == np.float32 and ref.dtype == np.float32 and dev.shape == ref.shape and np.array_equal(dev, ref), what
+def swapped(x):
+    return {k: np.swapaxes(v, 0, 1) for k, v in x.items()}
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,9 +40,9 @@ def same_step_view(name):
     """What a SAME_STEP batch shows for a fixture: the recorded observation pieces [n, T, ...] with the post-reset observation in
     the slots of terminal steps, and the terminal ones as recorded."""
     z = golden(name)
-    final = pieces(z, "obs_")
+    final = kit.pieces(SPEC, z, "obs_")
     obs = {k: v.copy() for k, v in final.items()}
-    resets = pieces(z, "reset_")
+    resets = kit.pieces(SPEC, z, "reset_")
     for j, (i, t) in enumerate(z["reset_index"]):
         for k in obs:
             obs[k][i, t] = resets[k][j]
@@ -92,7 +60,7 @@ def make(cge, z, mode, flat, **kw):
     n = z["reward"].shape[0]
     env = cge.WorldBuilderVectorEnv(n, autoreset_mode=mode, grid_size=int(z["grid_size"]), flatten_obs=flat, **kw)
     obs, _ = env.reset(seed=int(z["seed0"]))
-    same(host(env, obs), layout(pieces(z, "obs0_"), flat), "reset")
+    same(host(env, obs), layout(kit.pieces(SPEC, z, "obs0_"), flat), "reset")
     return env, n
 
 
@@ -142,11 +110,11 @@ def test_fixtures_same_step(cge, name, flat):
     assert rew.dtype == np.float32 and np.array_equal(rew, z["reward"].astype(np.float32))
     want_obs, want_final = same_step_view(name)
     for t in range(T):
-        same(host(env, out[t][0]), layout(take(want_obs, (slice(None), t)), flat), ("obs", t))
+        same(host(env, out[t][0]), layout(take(want_obs, slice(None), t), flat), ("obs", t))
         fin = out[t][4]
         assert torch.equal(fin["_final_obs"], out[t][2])
         if term[:, t].any():
-            same(host(env, fin["final_obs"]), layout(take(want_final, (slice(None), t)), flat), ("final_obs", t), term[:, t])
+            same(host(env, fin["final_obs"]), layout(take(want_final, slice(None), t), flat), ("final_obs", t), term[:, t])
     if bool(z["flatten_obs"]) and flat:                                  # and as the reference itself returned the flat rows
         got = torch.stack([o[0] for o in out], 1).cpu().numpy()
         keep = ~term
@@ -163,9 +131,9 @@ def test_fixtures_next_step(cge, name, flat):
     z = golden(name)
     T = z["reward"].shape[1]
     env, n = make(cge, z, "NextStep", flat)
-    want_final = pieces(z, "obs_")
-    resets = pieces(z, "reset_")
-    where = {(int(i), int(t)): j for j, (i, t) in enumerate(z["reset_index"])}
+    want_final = kit.pieces(SPEC, z, "obs_")
+    resets = kit.pieces(SPEC, z, "reset_")
+    where = where_reset(z)
     at = np.zeros(n, int)                                                # the fixture step env i takes next
     done = np.zeros(n, bool)
     rows = np.arange(n)
@@ -197,11 +165,11 @@ def test_fixture_disabled_with_masked_resets(cge, flat):
     for t in range(T):
         obs, rew, term, _, infos = env.step(z["actions"][:, t])
         assert "final_obs" not in infos
-        same(host(env, obs), layout(take(want_final, (slice(None), t)), flat), ("obs", t))
+        same(host(env, obs), layout(take(want_final, slice(None), t), flat), ("obs", t))
         assert np.array_equal(rew.cpu().numpy(), z["reward"][:, t].astype(np.float32)) and np.array_equal(term.cpu().numpy(), z["terminated"][:, t].astype(bool))
         if term.any():
             obs, _ = env.reset(options={"reset_mask": term})
-            same(host(env, obs), layout(take(want_obs, (slice(None), t)), flat), ("masked reset", t))
+            same(host(env, obs), layout(take(want_obs, slice(None), t), flat), ("masked reset", t))
             seen += int(term.sum())
     assert seen == len(z["reset_index"]) >= 4
     env.close()
@@ -311,8 +279,7 @@ def test_fixture_as_fused_rollouts(cge, flat):
         acts = torch.from_numpy(np.ascontiguousarray(z["actions"][:, t0:t0 + 100].T)).cuda()
         traj, rt, ft, rs, dc = env.rollout(100, actions=acts, trajectory=True, per_step=True)
         got = host(env, traj)
-        ref = layout(take(want_obs, (slice(None), slice(t0, t0 + 100))), flat)
-        same(take(got, slice(None)), {k: np.swapaxes(v, 0, 1) for k, v in ref.items()} if isinstance(ref, dict) else np.swapaxes(ref, 0, 1), t0)
+        same(got, swapped(layout(take(want_obs, slice(None), slice(t0, t0 + 100)), flat)), t0)
         assert np.array_equal(rt.cpu().numpy().T, z["reward"][:, t0:t0 + 100].astype(np.float32))
         assert np.array_equal(ft.cpu().numpy().T, z["terminated"][:, t0:t0 + 100].astype(bool))
         assert np.array_equal(rs.cpu().numpy(), z["reward"][:, t0:t0 + 100].sum(1))
@@ -364,8 +331,7 @@ def test_recorded_checkpoints(cge, name):
             env.set_state(recs[j])
             assert np.array_equal(env.get_state(), recs[j]), s
             traj, rt, ft, _, _ = env.rollout(T - s, actions=acts[s:], trajectory=True, per_step=True)
-            ref = layout(take(want_obs, (slice(None), slice(s, T))), flat)
-            same(host(env, traj), {k: np.swapaxes(v, 0, 1) for k, v in ref.items()} if isinstance(ref, dict) else np.swapaxes(ref, 0, 1), s)
+            same(host(env, traj), swapped(layout(take(want_obs, slice(None), slice(s, T)), flat)), s)
             assert np.array_equal(rt.cpu().numpy().T, z["reward"][:, s:].astype(np.float32)) and np.array_equal(ft.cpu().numpy().T, z["terminated"][:, s:].astype(bool))
         env.close()
 
@@ -383,7 +349,7 @@ def test_state_round_trip_and_refusals(cge):
         oa, ra, ta, _, _ = a.step(acts[t])
         ob, rb, tb, _, _ = b.step(acts[t])
         assert torch.equal(ra, rb) and torch.equal(ta, tb), t
-        same(host(b, ob), wm.flatten(host(a, oa)), t)
+        same(host(b, ob), layout(host(a, oa), True), t)
     assert np.array_equal(a.get_state(), b.get_state())
     good = a.get_state()
     hdr = 13 * 4
@@ -435,12 +401,7 @@ def test_captured_steps_replay_and_match_the_model(cge, flat):
     env.reset(seed=9)
     sampler = env.action_sampler(seed=5)
     buf = sampler.sample()
-    side = torch.cuda.Stream()                                         # warm-up on a side stream: the persistent buffers get allocated
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        w = env.step(buf)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
+    w = warm_up(lambda: env.step(buf))                                 # on a side stream: the persistent buffers get allocated
     same(host(env, w[0]), layout(m.step(buf.cpu().numpy())[0], flat), "warm-up")
     raw = w[0] if flat else env.obs_slab(w[0])
     hist = {"obs": torch.empty((K,) + tuple(raw.shape), dtype=raw.dtype, device="cuda"), "rew": torch.empty((K, n), device="cuda"),
@@ -455,7 +416,7 @@ def test_captured_steps_replay_and_match_the_model(cge, flat):
         g.replay()
         torch.cuda.synchronize()
         acts = hist["act"].cpu().numpy()
-        got = host(env, hist["obs"] if flat else env._dict(hist["obs"]))
+        got = host(env, hist["obs"]) if flat else kit.decode(env, hist["obs"])
         for t in range(K):
             mo, mr, mt, _ = m.step(acts[t])
             same(take(got, t), layout(mo, flat), (rep, t))
@@ -467,22 +428,7 @@ def test_captured_steps_replay_and_match_the_model(cge, flat):
 # ---------------------------------------------------------------------------------------------- 7. sharding
 @pytest.mark.parametrize("flat", [False, True], ids=["dict", "flat"])
 def test_sharding_invariance(cge, flat):
-    n, k = 357, 100
-    whole = cge.WorldBuilderVectorEnv(n, autoreset_mode="SameStep", flatten_obs=flat)
-    parts = [cge.make_sharded(cge.WorldBuilderVectorEnv, n, rank=j, world_size=2, local_rank=0, autoreset_mode="SameStep", flatten_obs=flat) for j in range(2)]
-    assert [p.shard for p in parts] == [(0, 179), (179, 178)]
-    ow = host(whole, whole.reset(seed=77)[0])
-    tw, rw, cw, sw, dw = whole.rollout(k, action_seed=9, trajectory=True, per_step=True)
-    tw = host(whole, tw)
-    for p in parts:
-        s = slice(p.shard[0], p.shard[0] + p.shard[1])
-        same(host(p, p.reset(seed=77)[0]), take(ow, s), "reset")
-        tp, rp, cp, sp, dp = p.rollout(k, action_seed=9, trajectory=True, per_step=True)
-        same(host(p, tp), take(tw, (slice(None), s)), "trajectory")
-        assert torch.equal(rp, rw[:, s]) and torch.equal(cp, cw[:, s]) and torch.equal(sp, sw[s]) and torch.equal(dp, dw[s])
-        p.close()
-    assert int(dw.sum()) > 0
-    whole.close()
+    kit.sharding_invariance(cge, SPEC, flatten_obs=flat)
 
 
 # ---------------------------------------------------------------------------------------------- 8. what is refused
@@ -530,7 +476,7 @@ def test_one_million_envs(cge, flat):
     m = wm.WorldBuilderModel(seed + sample, 10, wm.SAME_STEP)
 
     def sub(obs):
-        return obs[..., sidx, :].cpu().numpy() if flat else {k: v.index_select(v.dim() - len(s) - 1, sidx).cpu().numpy() for (k, s, _), v in zip(planes, obs.values())}
+        return {"flat": obs[..., sidx, :].cpu().numpy()} if flat else {k: v.index_select(v.dim() - len(s) - 1, sidx).cpu().numpy() for (k, s, _), v in zip(planes, obs.values())}
 
     from custom_gymnasium_environments_amd import world_builder as wb
     planes = wb.planes(10)

@@ -10,8 +10,8 @@ Env i draws from `np.random.RandomState(seeds[i])`: the legacy stream `np.random
 import numpy as np
 
 import _lane_model
+from _lane_model import DISABLED, NEXT_STEP, SAME_STEP  # noqa: F401
 
-NEXT_STEP, SAME_STEP, DISABLED = 0, 1, 2
 KEYS = ("grid", "resources", "population_capacity", "win_steps")
 MAX_POPULATION, WIN_STEPS = 20, 50                                         # world_builder_env.py:45-46
 COST_WOOD = np.array([0, 5, 0, 5, 10])                                      # game_logic.py:15-20, by action
